@@ -3,12 +3,18 @@
 (zero_grad -> forward -> Dice -> backward -> Adam, + RCCL gradient all-reduce when N > 1),
 batch 2 per GPU, fp32, synthetic data, random-init weights  (BASELINE.json configs[1] / [3]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
-Prints ONE JSON line on rank 0 with the contract fields plus
-  "roofline":     the dominant kernel (3x3x3 conv, C=4 @ 64^3) timed live with HIP events
-  "cpu_baseline": the CPU oracle (oracle/, torch CPU = the reference's own arithmetic) on the host cores
+Prints ONE JSON line on rank 0 with the contract fields.  A plain run sets up, warms up, times the K steps and prints; --full adds
+  "roofline":         the dominant kernel (3x3x3 conv, C=4 @ 64^3) timed live with HIP events (and "roofline_c8")
+  "roofline_by_time": the per-entry-point time table of one step (tools/kernel_table.py)
+  "cpu_baseline":     the CPU oracle (oracle/, torch CPU = the reference's own arithmetic) on the host cores
+  "other_configs":    the search step and the 128^3 train steps (fp32, bf16 storage), timed after the headline run
+--dump-outputs DIR writes what the last timed step computed (loss, the updated parameters, their gradients) as DIR/<name>.npy.
+The inputs (batch, initial weights, dropout seeds) are the same in every run with the same arguments.  The arrays are bit-identical
+between runs that report the same "schedule" in the result line: the trainer picks the side-stream or the single-stream schedule
+by timing them, and the two round differently (Adam grows that to ~1e-3 within a few steps).
 """
 import argparse
 import json
@@ -212,8 +218,10 @@ def search_step_bench(args, device):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     tr.check_sync()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(loss_arch=la.reshape(1), loss_weight=lw.reshape(1), **step_outputs(net)))
     extra = {"sync_timeouts": tr.sync_timeouts(), "schedule": "three streams" if tr._use_side else "single stream"}
-    if not args.no_kernel_table:
+    if args.full and not args.no_kernel_table:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         try:
             import kernel_table
@@ -298,6 +306,22 @@ def other_configs(device, batch, no_graph, targets="f32"):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """Write the arrays the last timed step produced as OUT_DIR/<name>.npy, float32.  Parameters + gradients are 15 MB for the train
+    step and 55 MB for the search step whatever --size is (the architecture is fixed by CFG), so nothing is sampled."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def step_outputs(model):
+    """The updated parameters and the gradients of the last step, each flattened and concatenated in named_parameters() order."""
+    ps = [p for _, p in model.named_parameters()]
+    return {"params": torch.cat([p.detach().reshape(-1) for p in ps]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in ps])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -312,6 +336,10 @@ def main():
                     help="storage of the three target maps in HBM: f32 (the reference's cast, train.py:118; the contract default) or u8 "
                          "(the generator's booleans as bytes, n3d_patch_batch's N3D_PATCH_T_U8: same losses bit for bit)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline run, also measure roofline, roofline_c8, roofline_by_time, cpu_baseline "
+                    "and other_configs (each can be left out again with its --no-* option); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (loss, updated parameters, "
+                    "their gradients) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-kernel-table", action="store_true", help="skip roofline_by_time (the per-entry-point time table of one step)")
@@ -401,6 +429,8 @@ def main():
     if cm is not None:
         sync_timeouts = int(sum(cm.gather_floats(sync_timeouts)))
     trainer.check_sync()     # raises (no line) if a hand-off timed out
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(loss=loss.reshape(1), **step_outputs(net)))
 
     if rank == 0:
         patches = world * args.batch * args.steps
@@ -422,12 +452,12 @@ def main():
                                             "hbm_frac_of_8TBs": round(value * 3 * BYTES_FWD_PER_PATCH * vox * byt / 1e9 / world / PEAK_HBM_GBS, 4)})(
                 (args.size / 64.0) ** 3, 1.0 if args.dtype == "f32" else 1.0 - 0.94 / 2),
         }
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             out["roofline"] = conv_kernel_roofline(device, args.batch, args.size, bf16=args.dtype == "bf16")
             # the same kernel family one level down: C = 8 on the half-size volume (up-cell 3, 21 % of the net's FLOPs).  At 64^3 patches
             # that is (2,8,32^3): 1024 one-wave tiles on 1024 SIMDs -- its no-fetch bound is 0.26 (profiles/r05_conv_ab.log)
             out["roofline_c8"] = conv_kernel_roofline(device, args.batch, args.size // 2, bf16=args.dtype == "bf16", c=8)
-        if world == 1 and not args.no_kernel_table:
+        if args.full and world == 1 and not args.no_kernel_table:
             # what actually dominates the step: top entry points by measured microseconds per step, each against its roofline
             # (recorded on the single-stream schedule: one entry point = one launch of the dependent chain; the replay reuses the
             # recorded pointers, so a failure here must not cost the headline line)
@@ -444,9 +474,9 @@ def main():
                 out["roofline_by_time_schedule"] = "single stream, eager (one entry point = one launch of the dependent chain); the headline ran: " + out["config"]["schedule"]
             except Exception as e:
                 out["roofline_by_time"] = "failed: %s" % (str(e)[:200],)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.batch, args.size)
-        if world == 1 and not args.no_other_configs and args.size == 64 and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_other_configs and args.size == 64 and args.dtype == "f32":
             del trainer
             torch.cuda.empty_cache()
             out["other_configs"] = other_configs(device, args.batch, args.no_graph, args.targets)

@@ -239,3 +239,37 @@ def patching_cases():
     return [((155, 173, 140), (64, 64, 64), None, False), ((155, 173, 140), (64, 64, 64), 16, False),
             ((155, 173, 140), (64, 64, 64), (8, 16, 32), True), ((60, 64, 130), (64, 64, 64), None, False),
             ((128, 128, 128), (128, 128, 128), 0, True), ((200, 90, 65), (128, 128, 128), 32, False)]
+
+
+def dropin_encode(v):
+    """JSON form of a call argument or result of the drop-in record (make_golden.gen_dropin): tuples, named tuples and
+    arrays keep their type"""
+    if isinstance(v, np.ndarray):
+        return {"__ndarray__": v.tolist(), "dtype": str(v.dtype)}
+    if isinstance(v, tuple) and hasattr(v, "_fields"):
+        return {"__namedtuple__": {k: dropin_encode(x) for k, x in zip(v._fields, v)}}
+    if isinstance(v, tuple):
+        return {"__tuple__": [dropin_encode(x) for x in v]}
+    if isinstance(v, list):
+        return [dropin_encode(x) for x in v]
+    if isinstance(v, dict):
+        return {k: dropin_encode(x) for k, x in v.items()}
+    if isinstance(v, (np.integer, np.floating, np.bool_)):
+        return v.item()
+    assert v is None or isinstance(v, (bool, int, float, str)), type(v)
+    return v
+
+
+def dropin_decode(v):
+    """inverse of dropin_encode for call arguments (a named tuple comes back as a dict of its fields)"""
+    if isinstance(v, list):
+        return [dropin_decode(x) for x in v]
+    if isinstance(v, dict):
+        if "__ndarray__" in v:
+            return np.array(v["__ndarray__"], dtype=v["dtype"])
+        if "__tuple__" in v:
+            return tuple(dropin_decode(x) for x in v["__tuple__"])
+        if "__namedtuple__" in v:
+            return {k: dropin_decode(x) for k, x in v["__namedtuple__"].items()}
+        return {k: dropin_decode(x) for k, x in v.items()}
+    return v

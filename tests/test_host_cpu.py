@@ -1,9 +1,7 @@
 """CPU-only tests of the host side: C-ABI symbol coverage, module surface / state-dict parity, segment
 building, error behaviour, genotype decoding.  No kernel is launched here."""
-import importlib
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -108,58 +106,75 @@ def test_fresh_shellnet_genotype_is_the_degenerate_one():
     assert gene.up[0][0] == "identity"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference sources only exist in the build container")
-def test_dropin_under_the_reference_network_files():
-    """The reference's nas.py / searched.py, UNCHANGED, import this repo's prim_ops / cell:
-    the nets build, and their state_dicts equal those built on the reference's own modules."""
+def test_dropin_under_the_reference_network_files(golden):
+    """The reference's nas.py / searched.py, UNCHANGED, import this repo's prim_ops / cell / genotype.
+    tests/golden/dropin.npz (make_golden.gen_dropin) holds every call those files make into the three modules while they build
+    ShellNet(4,4,3,4,3), SearchedNet(4,4,3,4,3, G_ALL), SearchedNet(4,6,3,2,3, G_ALL) and run ShellNet.get_gene(): ConvOps(...),
+    OPS[name](c), Cell(...), GenoParser(n).parse(...), Genotype(down=, up=), with the reference's own arguments, the class and
+    state-dict inventory of what each returned and where it sits in the net.  Replayed on this repo's modules, every call must
+    accept those arguments and return the same; the blocks placed where the reference puts them, plus the files' own alphas
+    (sized by DownOps / UpOps / NormOps), must give each net's state_dict as built on the reference's own modules."""
+    import ast
+    import json
     import nas_3d_unet_amd.cell, nas_3d_unet_amd.genotype, nas_3d_unet_amd.prim_ops
-    saved = {k: sys.modules.get(k) for k in ("prim_ops", "cell", "genotype", "nas", "searched")}
-    sys.path.insert(0, "/root/reference")
-    try:
-        for k in saved:
-            sys.modules.pop(k, None)
-        ref_nas = importlib.import_module("nas")
-        ref_searched = importlib.import_module("searched")
-        ref_sd = {k: tuple(v.shape) for k, v in ref_nas.ShellNet(4, 4, 3, 4, 3, False, True).state_dict().items()}
-        ref_sd2 = {k: tuple(v.shape) for k, v in
-                   ref_searched.SearchedNet(4, 4, 3, 4, 3, True, ref_searched.Genotype(*orc.G_ALL)).state_dict().items()}
-        for k in saved:
-            sys.modules.pop(k, None)
-        sys.modules["prim_ops"] = nas_3d_unet_amd.prim_ops
-        sys.modules["cell"] = nas_3d_unet_amd.cell
-        sys.modules["genotype"] = nas_3d_unet_amd.genotype
-        drop_nas = importlib.import_module("nas")
-        drop_searched = importlib.import_module("searched")
-        assert drop_nas.Cell is nas_3d_unet_amd.cell.Cell
-        m = drop_nas.ShellNet(4, 4, 3, 4, 3, False, True)
-        assert {k: tuple(v.shape) for k, v in m.state_dict().items()} == ref_sd
-        m2 = drop_searched.SearchedNet(4, 4, 3, 4, 3, True, drop_searched.Genotype(*orc.G_ALL))
-        assert {k: tuple(v.shape) for k, v in m2.state_dict().items()} == ref_sd2
-        assert isinstance(m2.down_cells[0]._ops[0], nas_3d_unet_amd.prim_ops.SEConvOp)
-        # round 6: the reference takes ANY init_n_kernels (nas.py:13-49, searched.py:55-90).  Over this repo's prim_ops / cell such a net
-        # builds with the reference's parameter shapes; its ops and cells mark themselves for the zero-padded per-op path
-        # (prim_ops._OpTwin; the forward itself needs the GPU: tests/test_gpu_dropin.py), and the twin of an op keeps the op's names
-        m6 = drop_searched.SearchedNet(4, 6, 3, 2, 3, True, drop_searched.Genotype(*orc.G_ALL))
-        for k in saved:
-            sys.modules.pop(k, None)
-        ref6 = importlib.import_module("searched").SearchedNet(4, 6, 3, 2, 3, True, importlib.import_module("searched").Genotype(*orc.G_ALL))
-        assert {k: tuple(v.shape) for k, v in m6.state_dict().items()} == {k: tuple(v.shape) for k, v in ref6.state_dict().items()}
-        assert m6.stem0._odd_channels() and m6.up_cells[-1].preprocess0._odd_channels() and not m6.last_conv[0]._odd_channels()
-        assert not m6.down_cells[0].preprocess0._odd_channels()     # 18 -> 12 channels: a dense conv takes any input count as it is
-        for op in [m6.stem0, m6.stem1] + list(m6.up_cells[-1]._ops):
-            tw = nas_3d_unet_amd.prim_ops._OpTwin(op)
-            tw.embed(op)
-            tp = dict(tw.twin.named_parameters())
-            for n, r in op.named_parameters():
-                assert all(a % 4 == 0 or a == b or a in (1, 3) for a, b in zip(tp[n].shape, r.shape)), (n, tp[n].shape)
-                lead = tp[n].detach()[tuple(slice(0, k) for k in r.shape)]
-                assert torch.equal(lead, r.detach()) and float(tp[n].detach().abs().double().sum()) == float(r.detach().abs().double().sum())   # the rest zero
-    finally:
-        sys.path.remove("/root/reference")
-        for k, v in saved.items():
-            sys.modules.pop(k, None)
-            if v is not None:
-                sys.modules[k] = v
+    mods = {"prim_ops": nas_3d_unet_amd.prim_ops, "cell": nas_3d_unet_amd.cell, "genotype": nas_3d_unet_amd.genotype}
+    g = golden("dropin")
+    values = json.loads(str(g["values"]))
+    for name, v in values.items():                      # the lists nas.py sizes its alphas by
+        mod, attr = name.split(".")
+        assert list(getattr(mods[mod], attr)) == v, name
+    calls = json.loads(str(g["calls"]))
+    assert {r["callee"].split("[")[0] for r in calls} == {"prim_ops.ConvOps", "prim_ops.OPS", "cell.Cell", "genotype.GenoParser",
+                                                          "genotype.GenoParser.parse", "genotype.Genotype"}
+    results, placed = [], {}
+    for i, rec in enumerate(calls):
+        mod, _, attr = rec["callee"].partition(".")
+        if rec["on"] is not None:
+            fn = getattr(results[rec["on"]], attr.rsplit(".", 1)[1])
+        elif attr.startswith("OPS["):
+            fn = mods[mod].OPS[attr[4:-1]]
+        else:
+            fn = getattr(mods[mod], attr)
+        res = fn(*gc.dropin_decode(rec["args"]), **gc.dropin_decode(rec["kwargs"]))
+        results.append(res)
+        what = "call %d %s in %s at %s" % (i, rec["callee"], rec["net"], rec["prefix"])
+        assert type(res).__name__ == rec["type"], (what, type(res))
+        if "inventory" in rec:
+            assert isinstance(res, torch.nn.Module), what
+            assert [[k, list(v.shape)] for k, v in res.state_dict().items()] == rec["inventory"], what
+            placed[(rec["net"], rec["prefix"])] = res
+        if "result" in rec:
+            assert gc.dropin_encode(res) == rec["result"], what
+    alpha_len = {"alpha2_down": len(values["prim_ops.DownOps"]), "alpha2_up": len(values["prim_ops.UpOps"]),
+                 "alpha1_down": len(values["prim_ops.NormOps"]), "alpha1_up": len(values["prim_ops.NormOps"])}
+    for key in ("supernet", "searched_all", "searched_all_init6"):
+        want = dict(zip((str(k) for k in g["inventory/%s/names" % key]), (str(s) for s in g["inventory/%s/shapes" % key])))
+        blocks = {p: m for (n, p), m in placed.items() if n == key}
+        assert blocks, key
+        got = {p + "." + k: str(tuple(v.shape)) for p, m in blocks.items() for k, v in m.state_dict().items()}
+        own = {k: s for k, s in want.items() if not any(k.startswith(p + ".") for p in blocks)}
+        assert set(own) == (set(alpha_len) if key == "supernet" else set()), (key, sorted(own))
+        for k, s in own.items():
+            assert ast.literal_eval(s)[1] == alpha_len[k], (k, s)
+        assert {**got, **own} == want, key
+    assert isinstance(placed[("searched_all", "down_cells.0._ops.0")], nas_3d_unet_amd.prim_ops.SEConvOp)
+    # round 6: the reference takes ANY init_n_kernels (nas.py:13-49, searched.py:55-90).  Over this repo's prim_ops / cell such a net
+    # builds with the reference's parameter shapes; its ops and cells mark themselves for the zero-padded per-op path
+    # (prim_ops._OpTwin; the forward itself needs the GPU: tests/test_gpu_dropin.py), and the twin of an op keeps the op's names
+    m6 = {p: m for (n, p), m in placed.items() if n == "searched_all_init6"}
+    last_up = "up_cells.%d." % max(int(p.split(".")[1]) for p in m6 if p.startswith("up_cells."))
+    assert m6["stem0"]._odd_channels() and m6[last_up + "preprocess0"]._odd_channels() and not m6["last_conv.0"]._odd_channels()
+    assert not m6["down_cells.0.preprocess0"]._odd_channels()     # 18 -> 12 channels: a dense conv takes any input count as it is
+    up_ops = [m6[p] for p in sorted(m6, key=lambda p: int(p.rsplit(".", 1)[1]) if "._ops." in p else -1) if p.startswith(last_up + "_ops.")]
+    assert len(up_ops) == 6
+    for op in [m6["stem0"], m6["stem1"]] + up_ops:
+        tw = nas_3d_unet_amd.prim_ops._OpTwin(op)
+        tw.embed(op)
+        tp = dict(tw.twin.named_parameters())
+        for n, r in op.named_parameters():
+            assert all(a % 4 == 0 or a == b or a in (1, 3) for a, b in zip(tp[n].shape, r.shape)), (n, tp[n].shape)
+            lead = tp[n].detach()[tuple(slice(0, k) for k in r.shape)]
+            assert torch.equal(lead, r.detach()) and float(tp[n].detach().abs().double().sum()) == float(r.detach().abs().double().sum())   # the rest zero
 
 
 def test_plateau_lr_matches_torch_scheduler():

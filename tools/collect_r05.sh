@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run on the GPU box (gpurun): regenerates the round-5 evidence under gpurun_out/r05c/ (copied into profiles/r05_* afterwards):
-#   bench_line.log                 the default bench line (roofline, roofline_c8, roofline_by_time, cpu_baseline, other_configs, sync_timeouts)
+#   bench_line.log                 the --full bench line (roofline, roofline_c8, roofline_by_time, cpu_baseline, other_configs, sync_timeouts)
 #   {bench,search,p128_f32,p128_bf16}_kernel_stats.csv   rocprofv3 --kernel-trace --stats, one workload each (single-stream schedule: the
 #                                  kernel trace serialises the streams), stdout next to it
 #   {p128_f32,p128_bf16,search}_bench.log   the other workloads' own bench lines with their roofline_by_time tables
@@ -9,7 +9,7 @@
 #   pmc_conv_vox64_f32_2x4x64*.json/csv   PMC of the headline conv kernel on the round-5 build (tools/collect_pmc_r05.sh)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05c; mkdir -p $O
-python3 bench.py > $O/bench_line.log 2> $O/bench_line.err
+python3 bench.py --full > $O/bench_line.log 2> $O/bench_line.err
 prof() {  # prof <name> <bench args...>
   N=$1; shift
   rm -rf $O/trace_$N
@@ -18,13 +18,13 @@ prof() {  # prof <name> <bench args...>
   rm -rf $O/trace_$N
   grep metric $O/${N}_stdout_under_rocprof.log | cut -c1-200
 }
-prof bench --no-other-configs --no-kernel-table --no-cpu-baseline --steps 20 --warmup 5
+prof bench --full --no-other-configs --no-kernel-table --no-cpu-baseline --steps 20 --warmup 5
 prof search --workload search --steps 5 --warmup 2 --no-kernel-table --no-cpu-baseline
-prof p128_f32 --size 128 --steps 6 --warmup 2 --no-kernel-table --no-cpu-baseline --no-other-configs
-prof p128_bf16 --size 128 --dtype bf16 --steps 6 --warmup 2 --no-kernel-table --no-cpu-baseline --no-other-configs
-python3 bench.py --size 128 --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs > $O/p128_f32_bench.log 2>&1
-python3 bench.py --size 128 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs > $O/p128_bf16_bench.log 2>&1
-python3 bench.py --workload search --steps 10 --warmup 3 > $O/search_bench.log 2>&1
+prof p128_f32 --full --size 128 --steps 6 --warmup 2 --no-kernel-table --no-cpu-baseline --no-other-configs
+prof p128_bf16 --full --size 128 --dtype bf16 --steps 6 --warmup 2 --no-kernel-table --no-cpu-baseline --no-other-configs
+python3 bench.py --full --size 128 --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs > $O/p128_f32_bench.log 2>&1
+python3 bench.py --full --size 128 --dtype bf16 --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs > $O/p128_bf16_bench.log 2>&1
+python3 bench.py --full --workload search --steps 10 --warmup 3 > $O/search_bench.log 2>&1
 {
   echo "# data-parallel code path on a 1-rank RCCL group (N3D_FORCE_DP=1): ms per step, 30 steps after 5 warm-up, HIP-graph replay"
   for args in "" "--buckets 2" "--buckets 3" "--comm torch" "--comm torch --buckets 2"; do

@@ -1,5 +1,5 @@
 import sys, os, collections
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from nas_3d_unet_amd import kernels as K, searched, train, _lib
 from oracle import ref_path as orc

@@ -1,7 +1,8 @@
 """The launch sequence of the 64^3 train step's side-stream schedule per stream, from the C-ABI calls recorded while the trainer captures it: how many
 of the main chain's launches are flag launches (n3d_sync_*) and how many of those sit next to each other (profiles/r06_handoff_seq.log)."""
 import os, sys, collections
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch, bench
 from kernel_table import Recorder
 from nas_3d_unet_amd import searched

@@ -1,6 +1,7 @@
 """round 6 probe: gradient error of a padded-twin net against the fp64 oracle at 32^3 under single switches (bisects the kernel form)"""
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo/tests/golden")
+import os, sys, numpy as np, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from oracle import ref_path as orc
 import test_gpu_nets as T
 from nas_3d_unet_amd import loss, searched, unet, fused, programs as P_, kernels as K, _lib

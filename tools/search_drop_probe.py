@@ -1,6 +1,6 @@
 """probe: the search step with and without its deferred weight-gradient launches (upper bound of what a faster weight-gradient stream can buy)"""
 import sys, os, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import bench
 from nas_3d_unet_amd import nas, kernels as K
