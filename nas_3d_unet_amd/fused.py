@@ -12,6 +12,7 @@ _node_units (terms grouped so that launches can be shared), i.e. the same sum wi
 """
 from __future__ import annotations
 
+import contextlib
 
 import torch
 
@@ -23,6 +24,31 @@ from ._lib import ACCUMULATE
 PAIR_SUPERNET_TERMS = True  # pair the GroupNorm-type terms of a supernet node (False: one epilogue launch per primitive)
 GROUP_SUPERNET_TERMS = True  # ... and take them up to eight at a time where a node has three or more (P.group_forward)
 REUSE_GRAD_OUTPUT = False  # see _run_backward; switched on by the trainers for the duration of their backward pass
+
+
+@contextlib.contextmanager
+def switched(**values):
+    """with switched(REUSE_GRAD_OUTPUT=True): ... -- the named switches of this module set for the duration, then restored"""
+    g = globals()
+    prev = {k: g[k] for k in values}
+    g.update(values)
+    try:
+        yield
+    finally:
+        g.update(prev)
+
+
+@contextlib.contextmanager
+def padded_switches():
+    """while kernels of a zero-padded twin (unet.PaddedTwin) are launched: conv-bias gradients by summation, per-term GroupNorm
+    launches (the node-level ones share their element count with SE gates), no node-planar inner cells"""
+    global NODE_PHASES, NODE_APPLY, PLANAR_INNER
+    prev = (P.ANALYTIC_CONV_BIAS, NODE_PHASES, NODE_APPLY, P.NODE_FWD_COEFFS, PLANAR_INNER)
+    P.ANALYTIC_CONV_BIAS, NODE_PHASES, NODE_APPLY, P.NODE_FWD_COEFFS, PLANAR_INNER = False, False, False, False, False
+    try:
+        yield
+    finally:
+        P.ANALYTIC_CONV_BIAS, NODE_PHASES, NODE_APPLY, P.NODE_FWD_COEFFS, PLANAR_INNER = prev
 
 
 def _grouping(c_node):

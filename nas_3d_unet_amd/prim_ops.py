@@ -99,13 +99,13 @@ class _PaddedOpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, op, tw, need_grad, xin, *_params):
-        from .train import _padded_flags
+        from .fused import padded_switches
         tw.embed(op)
         cin, cout = tw.cin, tw.cout
         B, _c, D, H, W = xin.shape
         xp = torch.zeros((B, D, H, W, _pad4(cin)), dtype=xin.dtype, device=xin.device).permute(0, 4, 1, 2, 3)
         xp[:, :cin].copy_(xin)
-        with _padded_flags(), torch.set_grad_enabled(need_grad):
+        with padded_switches(), torch.set_grad_enabled(need_grad):
             xi = xp.requires_grad_(need_grad and xin.requires_grad)
             out = BaseOp._run_segments(tw.twin, xi)
         if need_grad:
@@ -114,14 +114,14 @@ class _PaddedOpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from .train import _padded_flags
+        from .fused import padded_switches
         op, tw, xi, out = ctx.saved
         tp = dict(tw.twin.named_parameters())
         reals = list(op.named_parameters())
         dp = torch.zeros_like(out)
         dp[:, :tw.cout].copy_(dout)
         wanted = ([xi] if xi.requires_grad else []) + [tp[n] for n, _ in reals]
-        with _padded_flags():
+        with padded_switches():
             gs = list(torch.autograd.grad([out], wanted, [dp], allow_unused=True))
         gx = gs.pop(0)[:, :tw.cin] if xi.requires_grad else None
         gpar = [None if g is None else g[tuple(slice(0, k) for k in r.shape)] for g, (_, r) in zip(gs, reals)]

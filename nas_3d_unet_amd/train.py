@@ -17,6 +17,7 @@ MI355X-first mechanics (none of which the reference has):
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import types
 import weakref
@@ -244,9 +245,9 @@ def _low_priority_stream(device):
         with torch.cuda.device(device):
             # (A CU mask on the side stream does not help: hipExtStreamCreateWithCUMask makes a BLOCKING stream -- next to torch's
             # legacy default stream every hand-off then takes a time slice, a 9.6 ms step -- and with the whole step moved to a
-            # non-blocking stream, a side stream held to 28 or 24 compute units of every XCD [mask bit i = CU i // 8 of XCD i % 8,
-            # tools/cumask_map.cpp; a mask that empties an XCD is ignored] leaves the chain's time under the side work where it
-            # was, 2.01 ms: what the side work costs the chain is not compute units.  profiles/r03_contention_probes.log)
+            # non-blocking stream, a side stream held to 28 or 24 compute units of every XCD [mask bit i = CU i // 8 of XCD i % 8;
+            # a mask that empties an XCD is ignored] leaves the chain's time under the side work where it was, 2.01 ms: what the side
+            # work costs the chain is not compute units.  profiles/r03_contention_probes.log)
             h = K.stream_create_low_priority()     # through libn3d: the HIP runtime that launches the kernels makes the stream
         return torch.cuda.ExternalStream(h, device=device)
     except K.N3DError:
@@ -290,7 +291,7 @@ class SideSchedule:
     that flag followed by the queued kernels, and publishes a 'done' flag; `finish()` (main stream) waits for it and runs the
     slab reduction.  Main chain, side work and tail are replayed as three separately launched HIP graphs: an event between
     graph launches costs ~190 us per hand-off on this stack and an intra-graph fork ~19 us per edge without overlapping, a
-    flag costs a ~2 us kernel on each side (tools/handoff_cost.cpp).
+    flag costs a ~2 us kernel on each side (profiles/r03_handoff_cost.log).
     Device words of `sync` (int32): [0] main-stream step, [1] time-outs, [2] side-stream step, [3] weight-gradient stream step,
     [4] time-outs the host has acknowledged, [8 + i] flag of cut i, [8 + JOIN] side work of this step done.
 
@@ -301,21 +302,21 @@ class SideSchedule:
     raises until `acknowledge()` (Trainer.recover) has been called, which also retires the side schedule."""
     JOIN = 400
 
-    def __init__(self, device, ctx, min_queue=None, wgrad_stream=False):
+    def __init__(self, device, ctx, min_queue=None, wgrad_stream=False, tail_inline=(2,), early_finalize=0):
         """wgrad_stream: a SECOND side stream for the weight-gradient launches (the supernet's weight pass keeps the first one busy
         with the preprocess-fed edges of its forward and backward); without it, or when no second stream passes the probe, the
-        weight gradients share the one side stream"""
+        weight gradients share the one side stream.  tail_inline, early_finalize: see below"""
         self.device, self.ctx = device, ctx
         self.min_queue = 5 if min_queue is None else int(min_queue)
         # cuts from the end at which the side stream reduces the slabs it has so far (0 = off, the default: measured at 64^3 the
         # tail shrinks 66 -> 49 us but the reduction takes 24 us out of the chain it runs beside)
-        self.early_finalize = 0
+        self.early_finalize = early_finalize
         # live cuts: the slabs launched so far are reduced on the weight-gradient stream behind the n-th group (0 = never, -1 = at 55 %
         # of the groups the fullest pass so far had).  64^3 train step: tail 0.078 -> 0.064 ms, chain +0.001 (n = 11 of 20)
         self.early_at = -1
         # weight-gradient groups, counted from the end of the walk, that go to the INLINE side stream instead (see cut()).  (Every k-th
         # group there, or a second weight-gradient stream, measured slower: profiles/r04_alternate_ab.log)
-        self.tail_inline = (2,)
+        self.tail_inline = tail_inline
         self._live_cuts = 0
         self._live_cuts_max = 0
         self.sync = torch.zeros(8 + self.JOIN + 8, dtype=torch.int32, device=device)
@@ -331,8 +332,6 @@ class SideSchedule:
         self.bwd_side_inputs = (0, 1)   # backward_mode(): the side stream takes the edges fed by these preprocess outputs
         self.arena = []        # every tensor made while forward_mode() / arena_mode() is on: held until finish()
         self.seen = 0
-        self.replays = 0
-        self.watch = None
         # N3D_SIDE_TRACE=1 (tools/side_timeline.py): wall-clock stamps next to every hand-off.  int64 words: [0] main: first cut,
         # [2 i + 2] main stored flag i, [2 i + 3] side passed wait i, [2 JOIN + 4] side done, [2 JOIN + 5] main passed the join,
         # [2 JOIN + 6] slab reduction launched behind it, [2 JOIN + 8 + i] the weight-gradient group behind cut i has been launched through
@@ -874,24 +873,270 @@ def _pad_mask_for(tw, real, fp, device):
     return mask
 
 
-def _padded_flags():
-    """context: while kernels of a padded twin are launched -- conv-bias gradients by summation, per-term GroupNorm launches (the node-level
-    ones share their element count with SE gates), no node-planar inner cells (unet.run_padded does the same)"""
-    import contextlib
-    from . import programs as _P
+class _GraphTrainer:
+    """What Trainer and SearchTrainer share: the zero-padded twin, the side-stream schedule (SideSchedule) and the ranks' agreement
+    on it, the guarded gradient exchange, the capture of the plain and the side-stream graphs and the choice between them, the
+    captured graphs' input buffers, and what follows a timed-out hand-off.  A subclass supplies its passes: _eager, _warm_up,
+    _capture_plain, _side_passes, _replay_plain / _replay_side (which _choose_schedule times) and _replay."""
 
-    @contextlib.contextmanager
-    def ctx():
-        prev = (_P.ANALYTIC_CONV_BIAS, _fused.NODE_PHASES, _fused.NODE_APPLY, _P.NODE_FWD_COEFFS, _fused.PLANAR_INNER)
-        _P.ANALYTIC_CONV_BIAS, _fused.NODE_PHASES, _fused.NODE_APPLY, _P.NODE_FWD_COEFFS, _fused.PLANAR_INNER = False, False, False, False, False
+    N_INPUTS = 2        # tensors step() takes
+    TIMING = (2, 6)     # (warm-up, timed) replays of each schedule in _choose_schedule
+
+    def __init__(self, model, kernel, lr, betas, eps, graph, process_group, side_wgrad):
+        """kernel: the module whose parameters the trainer trains (the model itself, or a shell's kernel net)"""
+        self.model = model
+        # channel counts that are not multiples of 4: the trainer trains the kernel module's zero-padded TWIN (unet.PaddedTwin; padded
+        # entries have exactly-zero gradients, so Adam never moves them) and cuts the parameters back into it at the host-visible
+        # points (check_sync() / sync_to_module()); sync_from_module() re-embeds after its parameters were written from outside
+        self._kernel = kernel
+        self._twin = None
+        if getattr(kernel, "_n3d_padded", False):
+            self._twin = kernel._n3d_make_twin()
+            self._twin.embed(kernel)
+        # side_wgrad (default: N3D_SIDE_WGRAD, on): weight-gradient kernels on side HIP streams (SideSchedule).  Graph mode captures
+        # BOTH schedules, times them on the real step and replays the faster one ("force": no comparison)
+        env = os.environ.get("N3D_SIDE_WGRAD", "1")
+        self.side_wgrad = (env != "0") if side_wgrad is None else bool(side_wgrad)
+        self._side_force = side_wgrad == "force" or (side_wgrad is None and env == "force")
+        self._side_explicit = side_wgrad is not None     # an eager Trainer (graph=False) takes the side schedule only when asked to
+        self.side = None
+        self._use_side = False
+        self._side_retired = False   # recover() after a timed-out hand-off: the rest of the run stays on one stream
+        self.schedule_times = None   # (plain seconds per step, side seconds per step) measured at capture
+        self.use_graph = graph
+        self._static = None          # the captured graphs' input buffers (input_buffers()); None: the next graph step captures
+        self._graph = None           # the plain schedule
+        self._side_graphs = None     # the side-stream schedule: per pass (main chain graph, raw side-stream graphs, tail graph)
+        self._side_losses = None
+        self._side_wsegs = 1         # segments of the last pass' weight-gradient stream graph (Trainer's bucketed exchange cuts it)
+        self._n_steps = 0            # step() calls, on every path
+        self.pg = process_group
+        self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
+        # N3D_FORCE_DP=1: take the multi-GPU code path (all-reduce + eager Adam after the graph) even in a 1-rank group --
+        # lets a single-GPU box exercise exactly what N > 1 runs
+        self.dp_path = self.world > 1 or (dist.is_initialized() and os.environ.get("N3D_FORCE_DP") == "1")
+        self.loss_fn = WeightedDiceLoss()
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.device = next(model.parameters()).device
+        reserve_side_streams(self.device)     # first thing on the GPU (see there), also when THIS trainer will not use them
+
+    def _init_side(self, comm, **options):
+        """the side-stream schedule (SideSchedule options: wgrad_stream, tail_inline, early_finalize; None without a side stream
+        that passes the probe) and the weight-gradient exchange.  Data parallel: the probe is rank-local and timing-based, but every
+        rank must take the same schedule decisions (they decide which graphs exist and in which order the collectives go out): the
+        side schedule is on only if EVERY rank has one"""
+        side = SideSchedule(self.device, self.ctx, **options) if (self.side_wgrad and self.device.type == "cuda") else None
+        self.side = side if side is not None and side.stream is not None else None
+        self.sync = GradSync(self.fp.grad, self.pg, 1, None, comm, header=self.fp.grad_full)
+        if not self.sync.all_true(self.side is not None):
+            self.side = None
+
+    def _side_ok(self):
+        return self.side is not None and not self._side_retired
+
+    # -- host-visible points ----------------------------------------------------------------------
+    def check_sync(self):
+        """synchronising check (call it at every host-visible point: before a checkpoint is written, at the end of an epoch, before
+        a loss is reported): raises if a device-side wait of the side-stream schedule has timed out.  The updates of such steps
+        were withheld on the device, so the weights are those of the last good step; `recover()` continues on one stream."""
+        if self.side is not None:
+            self.side.check()
+        self.sync_to_module()
+
+    def sync_to_module(self):
+        """padded twin: the trained parameters back into the user's module (reference shapes); nothing to do otherwise"""
+        if self._twin is not None:
+            tp = dict(self._twin.twin.named_parameters())
+            with torch.no_grad():
+                for n, r in self._kernel.named_parameters():
+                    r.copy_(self._twin.extract(n, tp[n].detach()))
+
+    def sync_from_module(self):
+        """padded twin: the user's module was written from outside (load_state_dict): embed its parameters again"""
+        if self._twin is not None:
+            self._twin.embed(self._kernel)
+
+    def sync_timeouts(self):
+        """device-side waits that have timed out since the trainer was built (synchronises; 0 without a side schedule)"""
+        return int(self.side.sync[1].item()) if self.side is not None else 0
+
+    def recover(self):
+        """after a time-out (check_sync / step raised): acknowledge it and go on WITHOUT the side-stream schedule.  Nothing has to
+        be restored -- the guarded updates of the affected steps never ran -- but those batches are lost to training."""
+        if self.side is None:
+            return
+        self.side.acknowledge()
+        self._use_side = False
+        self._retire_side_graphs()
+        self._side_retired = True
+        if self._graph is None:
+            self._static = None      # "force" had no plain graph: the next step captures one
+
+    def _retire_side_graphs(self):
+        gs, self._side_graphs = self._side_graphs, None
+        for g in gs or ():
+            SideSchedule.raw_destroy(g[1])
+
+    def close(self):
+        """release the raw HIP graphs of the side streams (torch's own graphs and pools go with the object)"""
         try:
-            yield
+            self._retire_side_graphs()
+        except Exception:
+            pass
+
+    def __del__(self):
+        self.close()
+
+    # -- exchange and update guard ----------------------------------------------------------------
+    def _exchange(self, sync):
+        """data parallel: SUM all-reduce of sync's gradient buffer.  Word 0 of its header: "a hand-off of THIS rank timed out" --
+        summed over the ranks with the gradients, so that every rank withholds the same update (a rank without a side schedule
+        contributes 0)"""
+        if sync.active:
+            if self.side is not None:
+                K.guard_flag(self.side.ptr(1), self.side.ptr(4), sync.header.data_ptr())
+            else:
+                sync.header[:1].zero_()
+        sync.all_reduce()
+
+    def _guard(self, loss, sync):
+        """UpdateGuard of an optimizer launch on sync's gradients (None without a side schedule: nothing can time out)"""
+        if self.side is None:
+            return None
+        return self.side.guard(loss, sync.header.data_ptr() if self.dp_path else None)
+
+    # -- step -------------------------------------------------------------------------------------
+    def step(self, *batch):
+        """Trainer.step(x, t) -> loss, SearchTrainer.step(x, t, val_x, val_t) -> (architecture-pass loss, weight-pass loss): device
+        scalars, no host sync.  With graph=True the first call captures, later calls replay."""
+        if self._twin is None:
+            return self._step(*batch)
+        with _fused.padded_switches():
+            return self._step(*batch)
+
+    def _step(self, *batch):
+        if self.side is not None:
+            self.side.poll()     # host-only: a withheld update (timed-out hand-off) is fatal until recover()
+        self._n_steps += 1
+        if not self.use_graph:
+            return self._eager(*batch)
+        self._side_verdict()
+        if self._static is None or (self._graph is None and self._side_graphs is None):
+            self._capture(batch)
+        if not self._copy_in(batch):
+            # a batch of another shape (the reference's generator yields a smaller last batch of an epoch) or dtype: the captured
+            # graphs are for one only, so this step runs eagerly (same kernels, same update) -- on ONE stream (see Trainer._eager)
+            return self._eager(*batch, allow_side=False)
+        return self._replay()
+
+    def _copy_in(self, batch):
+        """the batch into the captured graphs' input buffers; False (nothing copied) when it does not fit them in shape or dtype.  A
+        caller that fills the trainer's own buffers (input_buffers(): the data step writes the batch straight into them) has no
+        copy to pay; any other tensor is copied in"""
+        for src, dst in zip(batch, self._static):
+            if src.shape != dst.shape or src.dtype != dst.dtype:
+                return False
+        for src, dst in zip(batch, self._static):
+            if src is not dst:
+                dst.copy_(src)
+        return True
+
+    def input_buffers(self):
+        """the device buffers the captured graphs read: Trainer (x, t), SearchTrainer (x, t, val_x, val_t); None before the first
+        graph step.  A data step that writes a batch straight into them (datastep.patch_batch(out=...)) and passes THESE tensors to
+        step() skips the per-step input copy."""
+        return self._static if self._static is not None else (None,) * self.N_INPUTS
+
+    def _side_verdict(self):
+        """start of a graph step, before anything of it is issued: the replay monitor's verdict (Trainer); nothing here"""
+
+    # -- capture ----------------------------------------------------------------------------------
+    def _capture(self, batch):
+        """capture (and, with a side stream, choose the schedule); the Dropout3d generators come out as they went in, so the
+        masks of the training run do not depend on how many warm-up / timing passes the capture needed"""
+        snap = _dropout_snapshot(self.net, self.device)
+        try:
+            self._static = tuple(a.clone() for a in batch)
+            sided = self._side_ok()
+            # warm-up on the capture stream (allocator + lazy module state) WITHOUT the optimizer launches: the weights, Adam moments
+            # and step counters -- possibly just loaded from a checkpoint (search.py:108-127) -- stay as they are
+            s = capture_stream(self.device)
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self._warm_up(sided)
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            if sided:
+                self._capture_side(s)
+                if self._side_force:
+                    self._use_side = True
+                    return
+            self._capture_plain()
+            if sided:
+                self._choose_schedule()
         finally:
-            _P.ANALYTIC_CONV_BIAS, _fused.NODE_PHASES, _fused.NODE_APPLY, _P.NODE_FWD_COEFFS, _fused.PLANAR_INNER = prev
-    return ctx()
+            snap.restore()
+
+    def _capture_side(self, s):
+        """The side-stream schedule, per pass (_side_passes: (run the pass' main-stream part, update)) three HIP graphs: the main
+        chain (torch capture: forward, Dice, backward with a flag store at every hand-off), the side streams' work behind their
+        device-side waits -- captured AT THE SAME TIME as a raw HIP graph, since its launches are issued in the middle of the main
+        chain's -- and the tail (wait for the side streams' 'done' flags, slab reduction, Adam unless an exchange sits in between).
+        The tail is a graph of its own because the slab-reduction job table is complete only once every weight-gradient launch
+        has been issued."""
+        import gc
+        gc.collect()
+        pool = torch.cuda.graph_pool_handle()
+        sd = self.side
+        torch.cuda.synchronize()
+        graphs, losses = [], []
+        for run, update in self._side_passes():
+            g_main, g_tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            sd.raw_capture_begin()
+            try:
+                with torch.cuda.stream(s):
+                    g_main.capture_begin(pool=pool, capture_error_mode="thread_local")
+                    losses.append(run())
+                    g_main.capture_end()
+                sd.launch_side(redirect=True)
+            finally:
+                side_exec = sd.raw_capture_end()
+            with torch.cuda.stream(s):
+                g_tail.capture_begin(pool=pool, capture_error_mode="thread_local")
+                sd.finish()
+                if not self.dp_path:
+                    update(losses[-1])
+                g_tail.capture_end()
+            graphs.append((g_main, side_exec, g_tail))
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._side_graphs, self._side_losses, self._side_wsegs = graphs, tuple(losses), sd.wseg_count
+
+    def _state(self):
+        """optimizer-visible state the schedule timing must leave as it found it"""
+        return [self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full]
+
+    def _choose_schedule(self):
+        """time the two captured schedules on the real step (state saved and restored around it) and keep the faster one.  Data
+        parallel: the timing runs replay the graphs only -- no collective, no update -- so a rank whose timing differs (or whose
+        side streams misbehave) cannot mispair all-reduces with its peers; the DECISION is then agreed on (MIN over ranks)"""
+        snap = _Snapshot(self._state() + _dropout_states(self.net))
+        tp = _time_schedule(lambda: self._replay_plain(exchange=False), self.device, *self.TIMING)
+        ts = _time_schedule(lambda: self._replay_side(exchange=False), self.device, *self.TIMING)
+        bad = self.side.sync_timeouts_now() != self.side.seen
+        snap.restore()
+        if bad:
+            # hand-offs timed out while the side schedule was being timed: the state is restored, the schedule is not used
+            self.side.acknowledge()
+        torch.cuda.synchronize(self.device)
+        self.schedule_times = (tp, ts)
+        self._use_side = self.sync.all_true(ts < tp and not bad)
+        if not self._use_side:
+            self._retire_side_graphs()     # the plain graph won: the side graphs (and their raw HIP executables) are released
 
 
-class Trainer:
+class Trainer(_GraphTrainer):
     """One searched-net (or any model built from nas_3d_unet_amd ops) training step.
 
     step(x, t): x (B,4,S,S,S), t (B,3,S,S,S) fp32 device tensors -> loss (0-d device tensor,
@@ -900,76 +1145,44 @@ class Trainer:
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None,
                  n_buckets=None, params=None, comm=None, storage=None, side_wgrad=None):
-        self.model = model
-        # channel counts that are not multiples of 4: the trainer trains the net's zero-padded TWIN (unet.PaddedTwin; padded entries have
-        # exactly-zero gradients, so Adam never moves them) and cuts the parameters back into `model` at the host-visible points
-        # (check_sync() / sync_to_module()); sync_from_module() re-embeds after `model`'s parameters were written from outside
-        self._twin = None
-        if getattr(model, "_n3d_padded", False):
-            from . import unet as _unet
-            tw = self._twin = model._n3d_make_twin()
-            tw.embed(model)
-            tw.twin.forward_loss = lambda x, t, smooth=1e-6, _tw=tw.twin: _unet.run_loss(_tw, x, t, None, smooth)
-            model = tw.twin
+        super().__init__(model, model, lr, betas, eps, graph, process_group, side_wgrad)
         self.net = model      # the module whose kernels run (the model itself, or its padded twin)
-        # side_wgrad (default: N3D_SIDE_WGRAD, on): the weight-gradient kernels of the C in {4, 8} levels -- nothing on the
-        # backward chain waits for them -- are queued during the backward walk and launched on a SIDE HIP stream at a few cut
-        # points (cell boundaries), as separately launched graphs tied to the main chain by events; the streams join once,
-        # in front of the slab reduction + Adam.  (Round 3: two per-SAMPLE chains measured no gain -- batching already is that
-        # overlap -- while the step's DAG has this slack: tools/two_chain_probe.py, tools/seg_overlap.cpp.)
-        env = os.environ.get("N3D_SIDE_WGRAD", "1")
-        self.side_wgrad = (env != "0") if side_wgrad is None else bool(side_wgrad)
-        # graph mode captures BOTH schedules, times them on the real step and replays the faster one ("force": no comparison);
-        # a replayed step is re-timed every 256 steps and the trainer falls back to the plain graph if the side schedule degrades
-        # (e.g. another library created hardware queues and the two streams are time-sliced)
-        self._side_force = side_wgrad == "force" or (side_wgrad is None and env == "force")
-        self._side_explicit = side_wgrad is not None     # an eager trainer (graph=False) takes the side schedule only when asked to
-        self._use_side = False
+        if self._twin is not None:
+            from . import unet as _unet
+            tw = self.net = self._twin.twin
+            tw.forward_loss = lambda x, t, smooth=1e-6, _tw=tw: _unet.run_loss(_tw, x, t, None, smooth)
+        # side_wgrad: the weight-gradient kernels of the C in {4, 8} levels -- nothing on the backward chain waits for them -- are
+        # queued during the backward walk and launched on a SIDE HIP stream at a few cut points (cell boundaries), as separately
+        # launched graphs tied to the main chain by events; the streams join once, in front of the slab reduction + Adam.  (Round 3:
+        # two per-SAMPLE chains measured no gain -- batching already is that overlap -- while the step's DAG has this slack:
+        # profiles/r03_two_chain_probe.log, profiles/r03_seg_overlap.log.)  A replayed side schedule is re-timed every 256 steps and
+        # the trainer falls back to the plain graph if it degrades (e.g. another library created hardware queues and the two
+        # streams are time-sliced): _side_verdict
         self._capturing_side = False
-        self._side_wsegs = 1
-        self._side_retired = False   # recover() after a timed-out hand-off: the rest of the run stays on one stream
-        self._n_steps = 0            # step() calls, on every path (the replay monitor's collective verdict is placed by this count)
-        self._bracket_now = False
-        self.schedule_times = None   # (plain seconds per step, side seconds per step) measured at capture
+        self._bracket_now = False    # this step's replay is bracketed with events ...
+        self._watch = None           # ... which are read at the start of the next step
+        self._recheck = 0            # 1: a slow sample is measured again at the next step
+        self._slow_run = 0           # slow samples in a row
+        self._static_loss = None
         if storage is not None:
             from . import unet as _unet
-            _unet.set_storage(model, storage)   # "bf16": bf16 activation storage on the HBM-bound levels (BASELINE configs[4])
-        self.loss_fn = WeightedDiceLoss()
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.device = next(model.parameters()).device
-        reserve_side_streams(self.device)     # first thing on the GPU (see there), also when THIS trainer will not use them
-        plist = list(params) if params is not None else list(model.parameters())
+            _unet.set_storage(self.net, storage)   # "bf16": bf16 activation storage on the HBM-bound levels (BASELINE configs[4])
+        plist = list(params) if params is not None else list(self.net.parameters())
         self.fp = FlatParams(plist, self.device)
         self._pad_mask = None
         if self._twin is not None:
             # gradients of the twin's PADDED parameter entries are not zero (GroupNorm couples a padded channel to its group) and Adam would
             # move them by lr per step: they are masked in front of every update, so the padded entries stay exactly 0
             self._pad_mask = _pad_mask_for(self._twin, self.model, self.fp, self.device)
-        self.use_graph = graph
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
-        # N3D_FORCE_DP=1: take the multi-GPU code path (all-reduce + eager Adam after the graph) even in a 1-rank group --
-        # lets a single-GPU box exercise exactly what N > 1 runs
-        self.dp_path = self.world > 1 or (dist.is_initialized() and os.environ.get("N3D_FORCE_DP") == "1")
         if n_buckets is None:
             n_buckets = int(os.environ.get("N3D_DP_BUCKETS", "1"))
         self.n_buckets = max(1, n_buckets)
-        self._graph = None
-        self._side_graphs = None
-        self._static_x = self._static_t = self._static_loss = None
         self.ctx = K.StepContext(self.device)  # batched weight packing + deferred wgrad reductions
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=self.device)  # read by the Adam kernel
         self._one = torch.ones((), dtype=torch.float32, device=self.device)
         self.scheduler = _plateau_for(self, "lr", "set_lr")  # train.py:50: ReduceLROnPlateau(factor=0.5)
         # (a weight-gradient stream of its own lets the side stream run data gradients of the C <= 8 cells inline: fused.SIDE_PAIRS_BWD)
-        self.side = SideSchedule(self.device, self.ctx, wgrad_stream=_fused.SIDE_PAIRS_BWD) if (self.side_wgrad and self.device.type == "cuda") else None
-        if self.side is not None and self.side.stream is None:
-            self.side = None
-        self.sync = GradSync(self.fp.grad, self.pg, 1, None, comm, header=self.fp.grad_full)
-        # data parallel: the side-stream probe is rank-local and timing-based, but every rank must take the same schedule decisions
-        # (they decide which graphs exist and in which order the collectives go out): the side schedule is on only if EVERY rank has one
-        if not self.sync.all_true(self.side is not None):
-            self.side = None
+        self._init_side(comm, wgrad_stream=_fused.SIDE_PAIRS_BWD)
         # the bucketed, overlapped exchange rides on the side-stream schedule (a closed bucket is reduced and sent from the
         # weight-gradient stream); without one the exchange is a single bucket behind the step
         self._buckets = self._bucket_plan() if (self.dp_path and self.n_buckets > 1 and self.side is not None) else None
@@ -1024,11 +1237,8 @@ class Trainer:
         with K.step_context(self.ctx):
             self.ctx.pack_all()            # one launch packs every conv weight for this step
             loss = _loss_of(self.net, self.loss_fn, x, t)
-            prev, _fused.REUSE_GRAD_OUTPUT = _fused.REUSE_GRAD_OUTPUT, True   # this backward is all ours (no hooks, no retain)
-            try:
+            with _fused.switched(REUSE_GRAD_OUTPUT=True):   # this backward is all ours (no hooks, no retain)
                 loss.backward(self._one)  # seed gradient kept resident: no fill launch per step
-            finally:
-                _fused.REUSE_GRAD_OUTPUT = prev
             self.ctx.flush_final()         # one launch finishes every weight-gradient reduction
         if not self.ctx.frozen:
             self.ctx.freeze()              # first pass only recorded which weights / layouts are needed
@@ -1044,26 +1254,18 @@ class Trainer:
         if not _fused.current(plan):
             plan = m._net_plan = _fused.net_plan(m, supernet=False)
         op = m.last_conv[0]
-        hook = cell_hook
         with torch.no_grad(), K.step_context(self.ctx):
             self.ctx.pack_all()
             nctx = _Ctx((False, False) + (False,) * 4 + (True,) * len(plan.params))
-            prev_pl, _fused.PLANAR_OUT = _fused.PLANAR_OUT, _fused.PLANAR_LAST     # (_direct_ok: the head is the fused one)
-            try:
+            with _fused.switched(PLANAR_OUT=_fused.PLANAR_LAST):     # (_direct_ok: the head is the fused one)
                 body = _fused.NetFn.forward(nctx, plan, x, None, None, None, None, *plan.params)
-            finally:
-                _fused.PLANAR_OUT = prev_pl
             gate = _P.draw_gate(op.dropout, op.training, *_head.feat_shape(body), body.device)
             hctx = _Ctx((False, False, True, False, True, True))
             hctx.skip_p = True        # the step returns the loss only: the head does not write the probabilities
             loss, _ = _head.HeadDiceFn.forward(hctx, gate, float(self.loss_fn.smooth), body, t, op.conv.weight, op.conv.bias)
             dbody = _head.HeadDiceFn.backward(hctx, self._one, None)[2]
-            prev, _fused.REUSE_GRAD_OUTPUT = _fused.REUSE_GRAD_OUTPUT, True
-            prev_hook, _fused.CELL_DONE_HOOK = _fused.CELL_DONE_HOOK, hook
-            try:
+            with _fused.switched(REUSE_GRAD_OUTPUT=True, CELL_DONE_HOOK=cell_hook):
                 _fused.NetFn.backward(nctx, dbody)
-            finally:
-                _fused.REUSE_GRAD_OUTPUT, _fused.CELL_DONE_HOOK = prev, prev_hook
         if not self.ctx.frozen:
             self.ctx.freeze()
         return loss
@@ -1077,75 +1279,7 @@ class Trainer:
                 and _head.fusable(m.last_conv, torch.empty((1, m.last_conv[0].conv.weight.shape[1], 1, 1, 1), device="meta")))
 
     def _side_ok(self):
-        return self.side is not None and not getattr(self, "_side_retired", False) and self._direct_ok()
-
-    def check_sync(self):
-        """synchronising check (call it at every host-visible point: before a checkpoint is written, at the end of an epoch, before
-        a loss is reported): raises if a device-side wait of the side-stream schedule has timed out.  The updates of such steps
-        were withheld on the device, so the weights are those of the last good step; `recover()` continues on one stream."""
-        if self.side is not None:
-            self.side.check()
-        self.sync_to_module()
-
-    def sync_to_module(self):
-        """padded twin: the trained parameters back into the user's module (reference shapes); nothing to do otherwise"""
-        if self._twin is not None:
-            tp = dict(self._twin.twin.named_parameters())
-            with torch.no_grad():
-                for n, r in self.model.named_parameters():
-                    r.copy_(self._twin.extract(n, tp[n].detach()))
-
-    def sync_from_module(self):
-        """padded twin: the user's module was written from outside (load_state_dict): embed its parameters again"""
-        if self._twin is not None:
-            self._twin.embed(self.model)
-
-    def _padctx(self):
-        """while kernels of a padded twin are being launched: conv-bias gradients by summation, per-term GroupNorm launches (the node-level
-        ones share their element count with SE gates), no node-planar inner cells (unet.run_padded does the same)"""
-        import contextlib
-        return _padded_flags() if self._twin is not None else contextlib.nullcontext()
-
-    def sync_timeouts(self):
-        """device-side waits that have timed out since the trainer was built (synchronises; 0 without a side schedule)"""
-        return int(self.side.sync[1].item()) if self.side is not None else 0
-
-    def _poll(self):
-        if self.side is not None:
-            self.side.poll()
-
-    def recover(self):
-        """after a time-out (check_sync / step raised): acknowledge it and go on WITHOUT the side-stream schedule.  Nothing has to
-        be restored -- the guarded updates of the affected steps never ran -- but those batches are lost to training."""
-        if self.side is None:
-            return
-        self.side.acknowledge()
-        self._use_side = False
-        self._retire_side_graphs()
-        self._side_retired = True
-        if self._graph is None:
-            self._static_x = self._static_t = None      # "force" had no plain graph: the next step captures one
-
-    def _retire_side_graphs(self):
-        g, self._side_graphs = self._side_graphs, None
-        if g is not None:
-            SideSchedule.raw_destroy(g[1])
-
-    def close(self):
-        """release the raw HIP graphs of the side streams (torch's own graphs and pools go with the object)"""
-        try:
-            self._retire_side_graphs()
-        except Exception:
-            pass
-
-    def __del__(self):
-        self.close()
-
-    def _guard(self, loss=None):
-        """UpdateGuard of this trainer's optimizer launches (None without a side schedule: nothing can time out)"""
-        if self.side is None:
-            return None
-        return self.side.guard(loss, self.fp.grad_full.data_ptr() if self.dp_path else None)
+        return super()._side_ok() and self._direct_ok()
 
     def _side_pass(self, x, t):
         """the autograd-free pipeline on two streams (SideSchedule): every deferrable weight-gradient launch is queued and handed to
@@ -1192,20 +1326,10 @@ class Trainer:
             K.guard_flag(self.side.ptr(1), self.side.ptr(4), self.fp.grad_full.data_ptr())
             self.sync.reduce_range(len(self.sync.ranges) - 1)
 
-    def _allreduce(self):
-        # word 0 of the gradient header: "a hand-off of THIS rank timed out" -- summed over the ranks with the gradients, so that
-        # every rank withholds the same update (a rank without a side schedule contributes 0)
-        if self.sync.active:
-            if self.side is not None:
-                K.guard_flag(self.side.ptr(1), self.side.ptr(4), self.fp.grad_full.data_ptr())
-            else:
-                self.fp.grad_full[:1].zero_()
-        self.sync.all_reduce()
-
     def _update(self, loss=None):
         if self._pad_mask is not None:
             self.fp.grad.mul_(self._pad_mask)
-        self.fp.adam(self.lr, self.betas, self.eps, 0.0, 1.0 / self.world, self.lr_dev, self._guard(loss))
+        self.fp.adam(self.lr, self.betas, self.eps, 0.0, 1.0 / self.world, self.lr_dev, self._guard(loss, self.sync))
 
     def set_lr(self, lr):
         """new learning rate for the following steps (also inside an already captured graph)"""
@@ -1223,64 +1347,68 @@ class Trainer:
                 if self._buckets is not None:
                     self._allreduce_last()
                 else:
-                    self._allreduce()
+                    self._exchange(self.sync)
         else:
             loss = self._fwd_bwd(x, t)
             if self.dp_path:
-                self._allreduce()
+                self._exchange(self.sync)
         self._update(loss)
         return loss
 
-    # -- public ---------------------------------------------------------------------------------
-    def step(self, x, t):
-        with self._padctx():
-            return self._step(x, t)
+    # -- capture and replay -----------------------------------------------------------------------
+    def _warm_up(self, sided):
+        if sided:
+            self._side_step_eager(*self._static)
+        if not (sided and self._side_force):
+            self._fwd_bwd(*self._static)
 
-    def _step(self, x, t):
-        self._poll()     # host-only: a withheld update (timed-out hand-off) is fatal until recover()
-        self._n_steps += 1
-        if not self.use_graph:
-            return self._eager(x, t)
-        self._side_verdict()
-        if self._static_x is None or (self._graph is None and self._side_graphs is None):
-            self._capture(x, t)
-        if x.shape != self._static_x.shape or t.shape != self._static_t.shape:
-            # a batch of another shape (the reference's generator yields a smaller last batch of an epoch): the captured
-            # graph is for one shape only, so this step runs eagerly (same kernels, same update) -- on ONE stream (see _eager)
-            return self._eager(x, t, allow_side=False)
-        # a caller that fills the trainer's own input buffers (input_buffers(): the data step writes the batch straight into them)
-        # has no copy to pay; any other tensor is copied in
-        if x is not self._static_x:
-            self._static_x.copy_(x)
-        if t is not self._static_t:
-            self._static_t.copy_(t)
-        if self._use_side:
-            self._watched_side_replay()
-            return self._side_loss
-        self._graph.replay()
-        if self.dp_path:
-            self._allreduce()
-            self._update(self._static_loss)
-        return self._static_loss
+    def _capture_plain(self):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):  # RCCL's watchdog thread may touch the runtime meanwhile
+            self._static_loss = self._fwd_bwd(*self._static)
+            if not self.dp_path:
+                self._update(self._static_loss)
+        self._graph = g
 
-    def input_buffers(self):
-        """(x, t) device buffers the captured graphs read (None before the first graph step).  A data step that writes a batch
-        straight into them (datastep.patch_batch(out=...)) and passes THESE tensors to step() skips the per-step input copy."""
-        return self._static_x, self._static_t
+    def _side_passes(self):
+        return [(self._captured_side_pass, self._update)]
+
+    def _captured_side_pass(self):
+        self._capturing_side = True     # (_bucket_closed: a closed bucket cuts the weight-gradient stream's graph)
+        try:
+            return self._side_pass(*self._static)
+        finally:
+            self._capturing_side = False
+
+    def _replay(self):
+        if not self._use_side:
+            self._replay_plain()
+            return self._static_loss
+        if self._bracket_now:
+            # every 256th STEP (counted by step() on every path: a rank that ran an eager step for an odd-shaped last batch, or
+            # recaptured, still counts it) is bracketed with events; the verdict on that sample is taken at the start of the next step
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            self._replay_side()
+            e1.record()
+            self._watch = (e0, e1)
+        else:
+            self._replay_side()
+        return self._side_losses[0]
 
     def _replay_side(self, exchange=True):
         # three graphs, no host-side cross-stream dependency: the streams meet through device flags (SideSchedule)
         # (the side graph goes first: its device-side waits are then in place when the main chain reaches its cuts, also when the
         # host is slower at launching than the GPU at running, e.g. under a profiler)
-        g_main, side_exec, g_tail = self._side_graphs
+        g_main, side_exec, g_tail = self._side_graphs[0]
         nseg = self._side_wsegs
         if nseg <= 1:
             self.side.raw_replay(side_exec)
             g_main.replay()
             g_tail.replay()
             if self.dp_path and exchange:
-                self._allreduce()
-                self._update(self._side_loss)
+                self._exchange(self.sync)
+                self._update(self._side_losses[0])
             return
         # bucketed exchange on flags: the weight-gradient stream's graph comes in segments, bucket j's all-reduce between segment j
         # and j + 1 on that stream (no host-side dependency: the segments wait for the chain's flags on the device)
@@ -1295,28 +1423,13 @@ class Trainer:
         g_tail.replay()
         if exchange:
             self._allreduce_last()
-            self._update(self._side_loss)
+            self._update(self._side_losses[0])
 
     def _replay_plain(self, exchange=True):
         self._graph.replay()
         if self.dp_path and exchange:
-            self._allreduce()
+            self._exchange(self.sync)
             self._update(self._static_loss)
-
-    def _watched_side_replay(self):
-        """one replayed step of the side schedule.  Every 256th STEP (counted by step() on every path: a rank that ran an eager step
-        for an odd-shaped last batch, or recaptured, still counts it) is bracketed with events; the verdict on that sample is taken
-        at the start of the next step (_side_verdict)."""
-        sd = self.side
-        sd.replays += 1
-        if self._bracket_now:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self._replay_side()
-            e1.record()
-            sd.watch = (e0, e1)
-            return
-        self._replay_side()
 
     def _side_verdict(self):
         """start of a step, one step after a bracketed one: the trainer checks the time-outs of the device-side waits (raises) and the
@@ -1330,14 +1443,14 @@ class Trainer:
         n = self._n_steps
         due, self._bracket_now = self._bracket_now, False
         # is THIS step a bracketed one?  (uniform over the ranks: the step count, or a re-check every rank agreed on one step ago)
-        want = sd is not None and self._use_side and (n % 256 == 0 or getattr(sd, "recheck", 0) > 0)
+        want = sd is not None and self._use_side and (n % 256 == 0 or self._recheck > 0)
         if want:
-            sd.recheck = 0
+            self._recheck = 0
         if sd is not None and self._use_side and due:
             fast, ms = True, None
-            if sd.watch is not None:
-                e0, e1 = sd.watch
-                sd.watch = None
+            if self._watch is not None:
+                e0, e1 = self._watch
+                self._watch = None
                 e1.synchronize()
                 sd.check()      # (the per-step poll() has seen a withheld update long before; this also catches a time-out whose
                                 # step was not followed by an update yet)
@@ -1347,9 +1460,9 @@ class Trainer:
             # ONE slow sample proves nothing -- the bracket also holds whatever the host did between the three graph launches (a
             # 100 000-step soak dropped a healthy schedule on a single 3.5 ms sample): a slow sample is measured again, three in a row
             # retire the schedule
-            sd.slow_run = (getattr(sd, "slow_run", 0) + 1) if slow else 0
-            sd.recheck = 1 if (slow and sd.slow_run < 3) else 0
-            if sd.slow_run >= 3:
+            self._slow_run = (self._slow_run + 1) if slow else 0
+            self._recheck = 1 if (slow and self._slow_run < 3) else 0
+            if self._slow_run >= 3:
                 import warnings
                 warnings.warn("nas_3d_unet_amd: the side-stream schedule degraded (%s ms per step on this rank against %.2f ms for the plain "
                               "graph, three samples in a row%s); falling back to the plain graph"
@@ -1359,103 +1472,11 @@ class Trainer:
                     torch.cuda.synchronize(self.device)
                     self._retire_side_graphs()
                     self._side_retired = True
-                    self._static_x = self._static_t = None
+                    self._static = None
         self._bracket_now = bool(want and self._use_side)
 
-    def _choose_schedule(self):
-        """time the two captured schedules on the real step (state saved and restored around it) and keep the faster one"""
-        if self._side_force:
-            self._use_side = True
-            return
-        snap = _Snapshot([self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full] + _dropout_states(self.net))
-        # data parallel: the timing runs replay the graphs only -- no collective, no update -- so a rank whose timing differs (or
-        # whose side streams misbehave) cannot mispair all-reduces with its peers; the DECISION is then agreed on (MIN over ranks)
-        tp = _time_schedule(lambda: self._replay_plain(exchange=False), self.device)
-        ts = _time_schedule(lambda: self._replay_side(exchange=False), self.device)
-        bad = self.side.sync_timeouts_now() != self.side.seen
-        snap.restore()
-        if bad:
-            # hand-offs timed out while the side schedule was being timed: the state is restored, the schedule is not used
-            self.side.acknowledge()
-        torch.cuda.synchronize(self.device)
-        self.schedule_times = (tp, ts)
-        self._use_side = self.sync.all_true(ts < tp and not bad)
-        if not self._use_side:
-            self._retire_side_graphs()     # the plain graph won: the side graphs (and their raw HIP executables) are released
 
-    def _capture(self, x, t):
-        """capture (and, with a side stream, choose the schedule); the Dropout3d generators come out as they went in, so the
-        masks of the training run do not depend on how many warm-up / timing passes the capture needed"""
-        snap = _dropout_snapshot(self.net, self.device)
-        try:
-            self._capture_impl(x, t)
-        finally:
-            snap.restore()
-
-    def _capture_impl(self, x, t):
-        self._static_x = x.clone()
-        self._static_t = t.clone()
-        sided = self._side_ok()
-        # warm-up on a side stream (allocator + lazy module state); no optimizer launch, the weights stay as they are
-        s = capture_stream(self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                if sided:
-                    self._side_step_eager(self._static_x, self._static_t)
-                if not (sided and self._side_force):
-                    self._fwd_bwd(self._static_x, self._static_t)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        if sided:
-            self._capture_side(s)
-            if self._side_force:
-                self._use_side = True
-                return
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):  # RCCL's watchdog thread may touch the runtime meanwhile
-            self._static_loss = self._fwd_bwd(self._static_x, self._static_t)
-            if not self.dp_path:
-                self._update(self._static_loss)
-        self._graph = g
-        if sided:
-            self._choose_schedule()
-
-    def _capture_side(self, s):
-        """The side-stream schedule as three HIP graphs: the main chain (torch capture: forward, Dice, backward with a flag store at
-        every hand-off), the side stream's work behind its device-side waits -- captured AT THE SAME TIME as a raw HIP graph, since
-        its launches are issued in the middle of the main chain's -- and the tail (wait for the side stream's 'done' flag, slab
-        reduction, Adam).  The tail is a graph of its own because the slab-reduction job table is complete only once every
-        weight-gradient launch has been issued."""
-        import gc
-        gc.collect()
-        pool = torch.cuda.graph_pool_handle()
-        sd = self.side
-        g_main, g_tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        sd.raw_capture_begin()
-        self._capturing_side = True
-        try:
-            with torch.cuda.stream(s):
-                g_main.capture_begin(pool=pool, capture_error_mode="thread_local")
-                self._side_loss = self._side_pass(self._static_x, self._static_t)
-                g_main.capture_end()
-            sd.launch_side(redirect=True)
-        finally:
-            self._capturing_side = False
-            side_exec = sd.raw_capture_end()
-        with torch.cuda.stream(s):
-            g_tail.capture_begin(pool=pool, capture_error_mode="thread_local")
-            sd.finish()
-            if not self.dp_path:
-                self._update(self._side_loss)
-            g_tail.capture_end()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._side_graphs = (g_main, side_exec, g_tail)
-        self._side_wsegs = sd.wseg_count
-
-class SearchTrainer:
+class SearchTrainer(_GraphTrainer):
     """Supernet search step, first-order DARTS as in the reference (search.py:211-238):
     architecture pass on the validation batch (Adam on the four alpha matrices), then weight pass on the
     training batch (Adam on the kernel weights); both Adam instances use torch defaults (search.py:103-104).
@@ -1464,34 +1485,25 @@ class SearchTrainer:
     (the reference computes and discards them, search.py:231) and the weight pass does not compute alpha
     gradients -- requires_grad is switched per pass, so the corresponding kernels are simply not launched."""
 
+    N_INPUTS = 4
+    TIMING = (1, 3)
+
     def __init__(self, shell, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None, comm=None, side_wgrad=None):
-        self.model = shell
-        # a kernel net with channel counts that are not multiples of 4: the trainer trains its zero-padded twin (see Trainer)
-        self._twin = None
-        self.net = shell
-        if getattr(getattr(shell, "kernel", None), "_n3d_padded", False):
-            tw = self._twin = shell.kernel._n3d_make_twin()
-            tw.embed(shell.kernel)
-            self.net = _TwinShell(shell, tw.twin)
+        super().__init__(shell, shell.kernel, lr, betas, eps, graph, process_group, side_wgrad)
+        # a kernel net with channel counts that are not multiples of 4: the shell's own alphas around its zero-padded twin
+        self.net = shell if self._twin is None else _TwinShell(shell, self._twin.twin)
         # the weight pass queues its weight-gradient kernels for the side stream (SideSchedule); the architecture pass has none
-        env = os.environ.get("N3D_SIDE_WGRAD", "1")
-        self.side_wgrad = (env != "0") if side_wgrad is None else bool(side_wgrad)
-        self._side_force = side_wgrad == "force" or (side_wgrad is None and env == "force")   # as in Trainer: no comparison
-        self._side_active = True     # _pass: use the side stream (when there is one)
+        self._side_active = True     # _pass: use the side stream (when there is one; off while the plain graphs are captured)
         self.side_forward = True    # ... also for the off-chain edges of the forward passes
         self.side_backward = True   # ... and for the preprocess-fed edges of the backward passes
         # which preprocess-fed edges the side stream takes in the backward: the second input's only (round 4; "01" = both until then --
         # since the node levels' phases are single launches the chain absorbs the first input's terms in its own, wider, launches
         # and the side stream's last node level -- which the chain waits for at the end of every cell -- is half as long:
-        # architecture pass 5.45 -> 5.25 ms, tools/search_phases.py)
+        # architecture pass 5.45 -> 5.25 ms, profiles/r04_search_phases.log)
         self.side_backward_inputs = (1,)
         self.side_backward_weight = ()      # (weight pass without a weight-gradient stream of its own: none)
-        self._use_side = False
-        self.schedule_times = None
-        self.loss_fn = WeightedDiceLoss()
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.device = next(shell.parameters()).device
-        reserve_side_streams(self.device)
+        self._replays = 0            # replays of the side schedule: every 256th is followed by a check()
+        self._losses = None
         self.kparams = list(shell.kernel.parameters()) if self._twin is None else list(self._twin.twin.parameters())
         self.aparams = list(shell.alphas())
         self.fp = FlatParams(self.kparams, self.device)
@@ -1504,20 +1516,11 @@ class SearchTrainer:
         self.afp = types.SimpleNamespace(params=self.aparams, offsets=aoffs, exp_avg=self.a_m, exp_avg_sq=self.a_v, step=self.a_step)
         self._one = torch.ones((), dtype=torch.float32, device=self.device)
         self.ctx = K.StepContext(self.device)
-        self.side = SideSchedule(self.device, self.ctx, wgrad_stream=True) if (self.side_wgrad and self.device.type == "cuda") else None
-        if self.side is not None:
-            # the weight pass' weight-gradient stream (219 launches) ends ~0.5 ms behind the chain: every other group of the walk's last
-            # eleven goes to the inline side stream instead, which has little else to do in the backward (weight pass 5.57 + 0.51 ->
-            # 5.78 + 0.09 ms; more groups there slow the chain by more than they take off the tail: tools/search_phases.py sweeps,
-            # DESIGN.md section 5)
-            self.side.tail_inline = (1, 3, 5, 7, 9, 11)
-        if self.side is not None and self.side.stream is None:
-            self.side = None
-        if self.side is not None:
-            self.side.early_finalize = 6      # 384 slab jobs per weight pass: reducing most of them early shrinks the tail 0.23 -> 0.15 ms
-        self.use_graph = graph
-        self._graph = None
-        self._side_graphs = None
+        # the weight pass' weight-gradient stream (219 launches) ends ~0.5 ms behind the chain: every other group of the walk's last
+        # eleven goes to the inline side stream instead, which has little else to do in the backward (weight pass 5.57 + 0.51 ->
+        # 5.78 + 0.09 ms; more groups there slow the chain by more than they take off the tail: profiles/r04_search_phases.log,
+        # DESIGN.md section 5).  384 slab jobs per weight pass: reducing most of them early shrinks the tail 0.23 -> 0.15 ms
+        self._init_side(comm, wgrad_stream=True, tail_inline=(1, 3, 5, 7, 9, 11), early_finalize=6)
         # two learning rates (search.py:103-106): alphas ("shell") and kernel weights, each on its own plateau schedule
         self.lr_shell, self.lr_kernel = float(lr), float(lr)
         self.lr_shell_dev = torch.full((1,), float(lr), dtype=torch.float32, device=self.device)
@@ -1525,17 +1528,15 @@ class SearchTrainer:
         self.shell_scheduler = _plateau_for(self, "lr_shell", "set_shell_lr")
         self.kernel_scheduler = _plateau_for(self, "lr_kernel", "set_kernel_lr")
         # data parallel: two exchanges per step -- the alpha gradients (180 floats) after the architecture pass,
-        # the kernel-weight gradients (27.4 MB) after the weight pass; weights and alphas broadcast once from rank 0
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
-        self.dp_path = self.world > 1 or (dist.is_initialized() and os.environ.get("N3D_FORCE_DP") == "1")
+        # the kernel-weight gradients (27.4 MB, sync_kernel) after the weight pass; weights and alphas broadcast once from rank 0
         self.sync_alpha = GradSync(self.agrad, self.pg, 1, None, comm, header=self.agrad._n3d_full)
-        self.sync_kernel = GradSync(self.fp.grad, self.pg, 1, None, comm, header=self.fp.grad_full)
-        self._graphs = None
-        if not self.sync_kernel.all_true(self.side is not None):     # every rank the same schedule (see Trainer)
-            self.side = None
         self.sync_kernel.broadcast(self.fp.flat)
         self.sync_kernel.broadcast(self.aflat)
+
+    @property
+    def sync_kernel(self):
+        """the kernel-weight exchange (the base class' `sync`, which also carries the schedule agreements)"""
+        return self.sync
 
     def set_shell_lr(self, lr):
         self.lr_shell = float(lr)
@@ -1558,7 +1559,7 @@ class SearchTrainer:
             self.agrad.zero_()  # alpha gradients arrive through autograd accumulation (softmax backward)
         # with a side stream BOTH passes use it: the forward of either pass runs the off-chain edges of every supernet cell there
         # (fused._run_forward_side), the weight pass also queues its weight-gradient launches for it
-        sided = self.side is not None and self._side_active
+        sided = self._side_active and self._side_ok()
         from . import programs as _P
         _P.PASS_TAG = "arch" if arch else "weight"
         with K.step_context(self.ctx):
@@ -1569,22 +1570,18 @@ class SearchTrainer:
                     loss = _loss_of(self.net, self.loss_fn, x, t)
             else:
                 loss = _loss_of(self.net, self.loss_fn, x, t)
-            prev, _fused.REUSE_GRAD_OUTPUT = _fused.REUSE_GRAD_OUTPUT, True
-            try:
-                import contextlib
-                # architecture pass: the side stream takes both preprocess-fed edges of every node (6 of a cell's 9: 7.8 -> 6.9 ms);
-                # weight pass: it already carries every weight gradient -- with both edge sets on top the pass takes 9.6 instead of
-                # 8.1 ms, with one 9.1 -- so its backward stays on one stream
-                # -- unless they run on a stream of their own (SideSchedule.split): then the weight pass does the same, 8.1 -> 7.1 ms
-                bwd_inputs = self.side_backward_inputs if (arch or (sided and self.side.split)) else self.side_backward_weight
+            # architecture pass: the side stream takes both preprocess-fed edges of every node (6 of a cell's 9: 7.8 -> 6.9 ms);
+            # weight pass: it already carries every weight gradient -- with both edge sets on top the pass takes 9.6 instead of
+            # 8.1 ms, with one 9.1 -- so its backward stays on one stream
+            # -- unless they run on a stream of their own (SideSchedule.split): then the weight pass does the same, 8.1 -> 7.1 ms
+            bwd_inputs = self.side_backward_inputs if (arch or (sided and self.side.split)) else self.side_backward_weight
+            with _fused.switched(REUSE_GRAD_OUTPUT=True):
                 with (self.side.backward_mode(bwd_inputs) if (sided and self.side_backward and bwd_inputs) else contextlib.nullcontext()):
                     if sided and not arch:
                         with self.side.deferring():
                             loss.backward(self._one)
                     else:
                         loss.backward(self._one)  # seed gradient kept resident: no fill launch per step
-            finally:
-                _fused.REUSE_GRAD_OUTPUT = prev
             if not sided:
                 self.ctx.flush_final()
         if sided and side == "main":
@@ -1598,55 +1595,12 @@ class SearchTrainer:
             self._update(arch, loss.detach())
         return loss.detach()
 
-    def check_sync(self):
-        """synchronising check for timed-out hand-offs (see Trainer.check_sync)"""
-        if self.side is not None:
-            self.side.check()
-        self.sync_to_module()
-
-    def sync_timeouts(self):
-        return int(self.side.sync[1].item()) if self.side is not None else 0
-
-    def recover(self):
-        """after a time-out: acknowledge it and go on without the side-stream schedule (see Trainer.recover)"""
-        if self.side is None:
-            return
-        self.side.acknowledge()
-        self._use_side = False
-        self._retire_side_graphs()
-        self._side_active = False
-        self._side_retired = True
-        if self._graph is None and self._graphs is None:
-            self._sx = None      # "force" had no plain graphs: the next step captures them
-
-    def _retire_side_graphs(self):
-        gs, self._side_graphs = self._side_graphs, None
-        for g in gs or ():
-            SideSchedule.raw_destroy(g[1])
-
-    def close(self):
-        """release the raw HIP graphs of the side streams"""
-        try:
-            self._retire_side_graphs()
-        except Exception:
-            pass
-
-    def __del__(self):
-        self.close()
-
     def _update(self, arch, loss=None):
         """exchange (data parallel) + Adam of the pass that just ran; guarded: a timed-out hand-off (on any rank) withholds it"""
-        sd = self.side
-        gbuf = self.agrad._n3d_full if arch else self.fp.grad_full
         sync = self.sync_alpha if arch else self.sync_kernel
         if self.dp_path:
-            if sync.active:
-                if sd is not None:
-                    K.guard_flag(sd.ptr(1), sd.ptr(4), gbuf.data_ptr())
-                else:
-                    gbuf[:1].zero_()
-            sync.all_reduce()
-        guard = sd.guard(loss, gbuf.data_ptr() if self.dp_path else None) if sd is not None else None
+            self._exchange(sync)
+        guard = self._guard(loss, sync)
         if arch:
             K.adam_step(self.aflat, self.agrad, self.a_m, self.a_v, self.a_step, self.lr_shell, self.betas[0], self.betas[1], self.eps,
                         grad_scale=1.0 / self.world, lr_dev=self.lr_shell_dev, guard=guard)
@@ -1660,157 +1614,75 @@ class SearchTrainer:
         lw = self._pass(x, t, False, update, pack=False)   # same weights as the architecture pass just packed
         return la, lw
 
-    def _capture_side(self, s):
-        """Per pass three graphs: the main chain (torch capture), the side stream's work -- the forward's off-chain edges, then
-        (weight pass) the queued weight-gradient groups -- captured on the side stream AT THE SAME TIME as a raw HIP graph, and
-        the tail (join, slab reduction, Adam unless an exchange sits in between)."""
-        import gc
-        gc.collect()
-        pool = torch.cuda.graph_pool_handle()
-        sd = self.side
-        torch.cuda.synchronize()
-        graphs, losses = [], []
-        for arch, (bx, bt) in ((True, (self._svx, self._svt)), (False, (self._sx, self._st))):
-            g_main, g_tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            sd.raw_capture_begin()
-            try:
-                with torch.cuda.stream(s):
-                    g_main.capture_begin(pool=pool, capture_error_mode="thread_local")
-                    losses.append(self._pass(bx, bt, arch, update=False, pack=arch, side="main"))
-                    g_main.capture_end()
-                sd.launch_side(redirect=True)
-            finally:
-                side_exec = sd.raw_capture_end()
-            with torch.cuda.stream(s):
-                g_tail.capture_begin(pool=pool, capture_error_mode="thread_local")
-                sd.finish()
-                if not self.dp_path:
-                    self._update(arch, losses[-1])
-                g_tail.capture_end()
-            graphs.append((g_main, side_exec, g_tail))
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._side_losses, self._side_graphs = tuple(losses), graphs
+    @contextlib.contextmanager
+    def _one_stream(self):
+        was, self._side_active = self._side_active, False
+        try:
+            yield
+        finally:
+            self._side_active = was
 
-    def step(self, x, t, val_x, val_t):
-        """returns (architecture-pass loss, weight-pass loss) as device scalars"""
-        if self._twin is not None:
-            with _padded_flags():
-                return self._step(x, t, val_x, val_t)
-        return self._step(x, t, val_x, val_t)
-
-    def sync_to_module(self):
-        """padded twin: the trained kernel weights back into shell.kernel (reference shapes)"""
-        if self._twin is not None:
-            tp = dict(self._twin.twin.named_parameters())
-            with torch.no_grad():
-                for n, r in self.model.kernel.named_parameters():
-                    r.copy_(self._twin.extract(n, tp[n].detach()))
-
-    def sync_from_module(self):
-        if self._twin is not None:
-            self._twin.embed(self.model.kernel)
-
-    def _step(self, x, t, val_x, val_t):
-        if self.side is not None:
-            self.side.poll()     # host-only: a withheld update (timed-out hand-off) is fatal until recover()
-        if not self.use_graph:
+    def _eager(self, x, t, val_x, val_t, allow_side=True):
+        """allow_side=False: on ONE stream (Trainer._eager says why)"""
+        if allow_side:
             return self._both(x, t, val_x, val_t)
-        if getattr(self, "_sx", None) is None or (self._graph is None and self._graphs is None and self._side_graphs is None):
-            drop_snap = _dropout_snapshot(self.net, self.device)   # restored below: masks independent of the warm-up passes
-            self._sx, self._st, self._svx, self._svt = x.clone(), t.clone(), val_x.clone(), val_t.clone()
-            # warm-up on a side stream (allocator + lazy module state) WITHOUT the optimizer launches: weights, alphas,
-            # Adam moments and step counters -- possibly just loaded from a checkpoint (search.py:108-127) -- stay untouched
-            s = capture_stream(self.device)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._both(self._sx, self._st, self._svx, self._svt, update=False)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            sided = self.side is not None and not getattr(self, "_side_retired", False)
-            if sided:
-                self._capture_side(s)
-            if sided and self._side_force:
-                self._use_side = True
-            else:
-                self._side_active = False
-                if self.dp_path:
-                    # one graph per pass (forward + backward only); the exchange and Adam of each pass run eagerly behind it
-                    pool = torch.cuda.graph_pool_handle()
-                    ga, gw = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(ga, pool=pool, capture_error_mode="thread_local"):
-                        la = self._pass(self._svx, self._svt, True, update=False)
-                    with torch.cuda.graph(gw, pool=pool, capture_error_mode="thread_local"):
-                        lw = self._pass(self._sx, self._st, False, update=False, pack=False)
-                    self._losses, self._graphs = (la, lw), (ga, gw)
-                else:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):  # RCCL's watchdog thread may touch the runtime meanwhile
-                        self._losses = self._both(self._sx, self._st, self._svx, self._svt)
-                    self._graph = g
-                self._side_active = sided
-                if sided:
-                    self._choose_schedule()
-            drop_snap.restore()
-        if any(a.shape != b.shape for a, b in ((x, self._sx), (t, self._st), (val_x, self._svx), (val_t, self._svt))):
-            # remainder batch of an epoch: eager step (the graph is for one shape), on ONE stream (Trainer._eager says why)
-            was, self._side_active = self._side_active, False
-            try:
-                return self._both(x, t, val_x, val_t)
-            finally:
-                self._side_active = was
-        for dst, src in ((self._sx, x), (self._st, t), (self._svx, val_x), (self._svt, val_t)):
-            if src is not dst:      # input_buffers(): a caller that fills the trainer's own buffers has no copy to pay
-                dst.copy_(src)
-        if self._use_side:
-            self._replay_side()
-            sd = self.side
-            sd.replays += 1
-            if sd.replays % 256 == 0:
-                sd.check()
-            return self._side_losses
-        self._replay_plain()
-        return self._losses
+        with self._one_stream():
+            return self._both(x, t, val_x, val_t)
 
-    def input_buffers(self):
-        """(x, t, val_x, val_t) device buffers the captured graphs read (see Trainer.input_buffers)"""
-        return self._sx, self._st, self._svx, self._svt
+    # -- capture and replay -----------------------------------------------------------------------
+    def _warm_up(self, sided):
+        self._both(*self._static, update=False)
+
+    def _capture_plain(self):
+        x, t, vx, vt = self._static
+        with self._one_stream():
+            if self.dp_path:
+                # one graph per pass (forward + backward only); the exchange and Adam of each pass run eagerly behind it
+                pool = torch.cuda.graph_pool_handle()
+                ga, gw = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                with torch.cuda.graph(ga, pool=pool, capture_error_mode="thread_local"):
+                    la = self._pass(vx, vt, True, update=False)
+                with torch.cuda.graph(gw, pool=pool, capture_error_mode="thread_local"):
+                    lw = self._pass(x, t, False, update=False, pack=False)
+                self._losses, self._graph = (la, lw), (ga, gw)
+            else:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):  # RCCL's watchdog thread may touch the runtime meanwhile
+                    self._losses = self._both(x, t, vx, vt)
+                self._graph = g
+
+    def _side_passes(self):
+        x, t, vx, vt = self._static
+        return [(lambda: self._pass(vx, vt, True, update=False, side="main"), lambda loss: self._update(True, loss)),
+                (lambda: self._pass(x, t, False, update=False, pack=False, side="main"), lambda loss: self._update(False, loss))]
+
+    def _state(self):
+        return super()._state() + [self.aflat, self.agrad._n3d_full, self.a_m, self.a_v, self.a_step]
+
+    def _replay(self):
+        if not self._use_side:
+            self._replay_plain()
+            return self._losses
+        self._replay_side()
+        self._replays += 1
+        if self._replays % 256 == 0:
+            self.side.check()
+        return self._side_losses
 
     def _replay_side(self, exchange=True):
-        for k, (arch, (g_main, side_exec, g_tail)) in enumerate(zip((True, False), self._side_graphs)):
+        for arch, loss, (g_main, side_exec, g_tail) in zip((True, False), self._side_losses, self._side_graphs):
             self.side.raw_replay(side_exec)      # first: see Trainer._replay_side
             g_main.replay()
             g_tail.replay()
             if self.dp_path and exchange:
-                self._update(arch, self._side_losses[k])
+                self._update(arch, loss)
 
     def _replay_plain(self, exchange=True):
-        if self._graphs is not None:
-            self._graphs[0].replay()
-            if exchange:
-                self._update(True, self._losses[0])
-            self._graphs[1].replay()
-            if exchange:
-                self._update(False, self._losses[1])
+        """the plain graph; data parallel one graph per pass, each followed by its exchange and update"""
+        if not self.dp_path:
+            self._graph.replay()
             return
-        self._graph.replay()
-
-    def _choose_schedule(self):
-        """time the two captured schedules on the real step (state saved and restored around it) and keep the faster one"""
-        snap = _Snapshot([self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full, self.aflat, self.agrad._n3d_full,
-                          self.a_m, self.a_v, self.a_step] + _dropout_states(self.net))
-        # data parallel: graphs only, no collective and no update while timing; the decision is agreed on (Trainer._choose_schedule)
-        ex = not self.dp_path
-        tp = _time_schedule(lambda: self._replay_plain(exchange=ex), self.device, warm=1, reps=3)
-        ts = _time_schedule(lambda: self._replay_side(exchange=ex), self.device, warm=1, reps=3)
-        bad = self.side.sync_timeouts_now() != self.side.seen
-        snap.restore()
-        if bad:
-            self.side.acknowledge()
-        torch.cuda.synchronize(self.device)
-        self.schedule_times = (tp, ts)
-        self._use_side = self.sync_kernel.all_true(ts < tp and not bad)
-        if not self._use_side:
-            self._retire_side_graphs()
-
+        for arch, loss, g in zip((True, False), self._losses, self._graph):
+            g.replay()
+            if exchange:
+                self._update(arch, loss)

@@ -162,21 +162,6 @@ class PaddedTwin:
         return g
 
 
-class _padded_switches:
-    """while kernels of a padded twin are launched: conv-bias gradients by summation, per-term GroupNorm launches (the node-level ones
-    share their element count with SE gates), no node-planar inner cells (train._padded_flags is the same set)"""
-
-    def __enter__(self):
-        from . import programs as P
-        self.prev = (P.ANALYTIC_CONV_BIAS, fused.NODE_PHASES, fused.NODE_APPLY, P.NODE_FWD_COEFFS, fused.PLANAR_INNER)
-        P.ANALYTIC_CONV_BIAS, fused.NODE_PHASES, fused.NODE_APPLY, P.NODE_FWD_COEFFS, fused.PLANAR_INNER = False, False, False, False, False
-
-    def __exit__(self, *exc):
-        from . import programs as P
-        P.ANALYTIC_CONV_BIAS, fused.NODE_PHASES, fused.NODE_APPLY, P.NODE_FWD_COEFFS, fused.PLANAR_INNER = self.prev
-        return False
-
-
 def _padded_net_fn():
     """the autograd node of run_padded (built on first use: torch is imported lazily in this module)"""
     global _PaddedNetFn
@@ -191,7 +176,7 @@ def _padded_net_fn():
         def forward(ctx, net, tw, need_grad, loss_target, smooth, n_al, xin, *rest):
             al = rest[:n_al]
             tw.embed(net)
-            with _padded_switches(), torch.set_grad_enabled(need_grad):
+            with fused.padded_switches(), torch.set_grad_enabled(need_grad):
                 xi = xin.detach().requires_grad_(need_grad and xin.requires_grad)
                 ali = tuple(a.detach().requires_grad_(need_grad and a.requires_grad) for a in al)
                 if loss_target is None:
@@ -211,7 +196,7 @@ def _padded_net_fn():
             wanted += [tp[n] for n in tw.names]
             outs = [o for o, d in zip(out, douts) if d is not None and o.requires_grad]
             gouts = [d for o, d in zip(out, douts) if d is not None and o.requires_grad]
-            with _padded_switches():
+            with fused.padded_switches():
                 gs = list(torch.autograd.grad(outs, wanted, gouts, allow_unused=True))
             gx = gs.pop(0) if xi.requires_grad else None
             gal = [gs.pop(0) if a.requires_grad else None for a in ali]

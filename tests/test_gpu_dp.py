@@ -48,7 +48,7 @@ def test_trainer_dp_schedules_match_single_gpu(one_rank_group, graph, buckets, c
         # the bucketed exchange replays the single-stream schedule (graph segments), everything else the side-stream one: the
         # reference trainer is given the same schedule, so the comparison is bit for bit (the two schedules differ by an fp32
         # rounding of the preprocess epilogue backward, and Adam turns 1e-6 on a weight into 1e-3 within three steps:
-        # tools/chaos_probe.py, profiles/r04_chaos_probe.log; tests/test_gpu_side.py compares the schedules themselves)
+        # profiles/r04_chaos_probe.log; tests/test_gpu_side.py compares the schedules themselves)
         # (graph, one bucket: both trainers are PINNED to the side schedule -- left to themselves each would pick by its own
         # wall-clock timing, and the comparison below is bit for bit)
         sched = "force" if graph else (True if buckets > 1 else None)
@@ -275,7 +275,7 @@ def test_two_processes_on_one_gpu_equal_the_global_batch(tmp_path, graph, bucket
         # the bucketed exchange replays the single-stream schedule (graph segments), everything else the side-stream one: the
         # reference trainer is given the same schedule, so the comparison is bit for bit (the two schedules differ by an fp32
         # rounding of the preprocess epilogue backward, and Adam turns 1e-6 on a weight into 1e-3 within three steps:
-        # tools/chaos_probe.py, profiles/r04_chaos_probe.log; tests/test_gpu_side.py compares the schedules themselves)
+        # profiles/r04_chaos_probe.log; tests/test_gpu_side.py compares the schedules themselves)
         # (graph, one bucket: both trainers are PINNED to the side schedule -- left to themselves each would pick by its own
         # wall-clock timing, and the comparison below is bit for bit)
         sched = "force" if graph else (True if buckets > 1 else None)

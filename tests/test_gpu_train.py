@@ -84,7 +84,7 @@ def test_lr_schedule_follows_through_graph_replay():
     for graph in (False, True):
         net, _ = build_net(kind, gname, depth)
         # (the same single-stream schedule on both sides: the side-stream schedule differs from it by an fp32 rounding of the
-        # preprocess epilogue backward, which Adam turns into 1e-3 on some weights within three steps -- tools/chaos_probe.py, profiles/r04_chaos_probe.log)
+        # preprocess epilogue backward, which Adam turns into 1e-3 on some weights within three steps -- profiles/r04_chaos_probe.log)
         tr = Trainer(net, graph=graph, side_wgrad=False)
         tr.step(x, t)
         tr.step(x, t)
@@ -136,6 +136,29 @@ def test_byte_targets_train_exactly_like_float_targets(graph):
         if graph:
             assert tr.input_buffers()[1].dtype == t.dtype
     assert losses[0] == losses[1], losses
+
+
+def test_targets_of_another_dtype_than_the_captured_ones_run_eagerly():
+    """a trainer captured on byte targets must not copy later float targets into its byte buffer (that truncates them):
+    such a step runs eagerly on one stream, as a remainder batch does, and trains like a trainer captured on float targets"""
+    from nas_3d_unet_amd.train import Trainer
+    key, kind, gname, depth, size, batch, adam = [c for c in gc.net_cases() if c[6] and c[1] == "searched"][0]
+    xn, tn = gc.net_batch(key, batch, size)
+    tb = (tn > 0.5)
+    x = dev(xn)
+    soft = dev(np.where(tb, 0.75, 0.25).astype(np.float32))    # (0 everywhere once truncated to bytes)
+    losses, eager = [], []
+    for t in (dev(tb.astype(np.float32)), dev(tb.astype(np.uint8))):
+        net, _ = build_net(kind, gname, depth)
+        tr = Trainer(net, graph=True, side_wgrad=False)
+        real = tr._eager
+        tr._eager = lambda *a, **k: (eager.append(k), real(*a, **k))[1]
+        losses.append([float(tr.step(x, t))] + [float(tr.step(x, soft)) for _ in range(2)])
+        del tr._eager          # (no trainer <-> wrapper cycle: the trainer goes by reference counting)
+        assert tr.input_buffers()[1].dtype == t.dtype
+    assert eager == [{"allow_side": False}] * 2
+    assert torch.equal(tr.input_buffers()[1], dev(tb.astype(np.uint8)))       # nothing was copied in
+    np.testing.assert_allclose(losses[1], losses[0], rtol=0, atol=2e-6)
 
 
 def test_data_parallel_property_on_the_hip_path():

@@ -47,7 +47,7 @@ timed(K, "graph_launch", "raw graph launch (side stream head / weight-gradient s
 timed(tr.sync, "reduce_range", "bucket all-reduce (ncclAllReduce on a stream)")
 timed(K, "guard_flag", "guard flag launch")
 timed(tr.fp, "adam", "guarded Adam launch")
-g_main, side_exec, g_tail = tr._side_graphs
+g_main, side_exec, g_tail = tr._side_graphs[0]
 for g, lab in ((g_main, "main-chain graph launch"), (g_tail, "tail graph launch")):
     timed(g, "replay", lab)
 per_step = []

@@ -30,7 +30,7 @@ def run(tag):
     return res
 
 import contextlib
-from nas_3d_unet_amd.train import _padded_flags
+from nas_3d_unet_amd.fused import padded_switches
 def setup(cfgt_, shape_, B=2, seed=17):
     global cfg, gene, P, xn, tn, total
     cfg = orc.NetCfg(*cfgt_); gene = T._genotype_for(cfg.n_nodes)
