@@ -477,6 +477,22 @@ int n3d_head_fwd(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t 
 int n3d_head_bwd(const n3d_head* h, const float* dp, int64_t dsb, int64_t dsc, int64_t dsv, const void* t, int64_t tsb, int64_t tsc,
                  int64_t tsv, float smooth, const double* sums, const float* dloss, void* dx, int64_t dxld, int dx_dtype, int flags,
                  float* dw, float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred, void* stream);
+/* ---- evaluation head (train.py:138-157 validate(); prediction.py:150-170 thresholds at >= 0.5): the head of n3d_head_fwd in eval
+ * mode -- no Dropout3d gate (h->gate must be NULL) -- with the Dice loss AND the region counts of the thresholded prediction in the
+ * same pass over (x, t), then ONE finalize launch that forms the batch loss exactly as n3d_head_fwd does (bit for bit) and adds the
+ * batch into a device accumulator.  Same input forms as n3d_head_fwd (pitched or node-planar x, fp32 / bf16, fp32 / byte t).
+ *   p: probabilities written when not NULL (strides as n3d_head_fwd); the evaluation pass of the trainers passes NULL.
+ *   thr: a voxel is predicted in class c when p >= thr.  B * Co <= 256.
+ *   partial: double[B][Co][n3d_head_rows(N)][3], hpartial: double[B][Co][n3d_head_rows(N)][2] scratch; sums: double[B][Co][3] and
+ *   *loss as n3d_head_fwd.
+ *   acc: double[N3D_EVAL_ACC_LEN(Co)], zeroed by the caller at the start of an epoch; each call adds (fixed order, no atomics)
+ *     acc[0] += loss, acc[1] += 1 (batches), acc[2] += B (samples), acc[3] unused;
+ *     per class c at acc[4 + 4c]: += (sum_b I, sum_b P, sum_b T, sum_b Dice_b) with I = sum [p >= thr] * t, P = sum [p >= thr],
+ *     T = sum t over the sample's voxels and Dice_b = 2 I / (P + T), = 1 when P + T == 0 (both regions empty).
+ *   The counts are integers held in fp64 (exact in any order); the accumulator of several ranks is their SUM. */
+#define N3D_EVAL_ACC_LEN(co) (4 + 4 * (co))
+int n3d_head_eval(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t psv, const void* t, int64_t tsb, int64_t tsc, int64_t tsv,
+                  float smooth, float thr, double* partial, double* hpartial, double* sums, float* loss, double* acc, void* stream);
 
 /* ---- layout: NCDHW <-> NDHWC (caller tensors arrive NCDHW: train.py:118-119) ---------------------- */
 int n3d_ncdhw_to_ndhwc(const float* src, float* dst, int64_t dld, int B, int C, int64_t N, void* stream);
@@ -518,6 +534,7 @@ int n3d_comm_available(void);
 int n3d_comm_unique_id(void* id_out /* N3D_COMM_ID_BYTES */);
 int n3d_comm_init(const void* id, int world, int rank, void** comm_out);
 int n3d_comm_allreduce_sum(void* comm, float* buf, int64_t n, void* stream);
+int n3d_comm_allreduce_sum_f64(void* comm, double* buf, int64_t n, void* stream);   /* the same in fp64 (the evaluation accumulator) */
 /* in-place broadcast of n floats from rank `root` (the one-off weight broadcast when a trainer is built), stream-ordered */
 int n3d_comm_broadcast(void* comm, float* buf, int64_t n, int root, void* stream);
 int n3d_comm_destroy(void* comm);

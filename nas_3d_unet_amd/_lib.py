@@ -192,6 +192,7 @@ PROTOTYPES = {
     "n3d_head_fwd": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _f, _p, _p, _p, _p]),
     "n3d_head_bwd": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _sz,
                           C.POINTER(FinalJob), _p]),
+    "n3d_head_eval": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f, _f, _p, _p, _p, _p, _p, _p]),
     "n3d_ncdhw_to_ndhwc": (_i, [_p, _p, _i64, _i, _i, _i64, _p]),
     "n3d_ndhwc_to_ncdhw": (_i, [_p, _i64, _p, _i, _i, _i64, _p]),
     "n3d_patch_batch": (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(PatchDesc), _i, _i, _i, _p, _i64, _p, _p]),
@@ -201,6 +202,7 @@ PROTOTYPES = {
     "n3d_comm_unique_id": (_i, [_p]),
     "n3d_comm_init": (_i, [_p, _i, _i, C.POINTER(C.c_void_p)]),
     "n3d_comm_allreduce_sum": (_i, [_p, _p, _i64, _p]),
+    "n3d_comm_allreduce_sum_f64": (_i, [_p, _p, _i64, _p]),
     "n3d_comm_broadcast": (_i, [_p, _p, _i64, _i, _p]),
     "n3d_comm_destroy": (_i, [_p]),
     "n3d_adam_step": (_i, [_p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _i, _p]),

@@ -77,7 +77,12 @@ class Comm:
         _lib.check(_lib.load().n3d_comm_allreduce_sum(self._h, C.c_void_p(ptr), n, self._stream(stream)), "n3d_comm_allreduce_sum")
 
     def allreduce_sum(self, t, stream=None):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        """in-place SUM all-reduce of a contiguous fp32 tensor -- or fp64 (the trainers' evaluation accumulator)"""
+        assert t.is_cuda and t.dtype in (torch.float32, torch.float64) and t.is_contiguous()
+        if t.dtype == torch.float64:
+            _lib.check(_lib.load().n3d_comm_allreduce_sum_f64(self._h, C.c_void_p(t.data_ptr()), t.numel(), self._stream(stream)),
+                       "n3d_comm_allreduce_sum_f64")
+            return
         self.allreduce_sum_ptr(t.data_ptr(), t.numel(), stream)
 
     def broadcast(self, t, root=0, stream=None):

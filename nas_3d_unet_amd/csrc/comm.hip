@@ -9,7 +9,7 @@
 
 namespace n3d {
 
-// the six entry points used, with RCCL's (= NCCL's) C signatures; enums passed as ints (ncclFloat32 = 7, ncclSum = 0)
+// the six entry points used, with RCCL's (= NCCL's) C signatures; enums passed as ints (ncclFloat32 = 7, ncclFloat64 = 8, ncclSum = 0)
 struct Id128 { char b[128]; };   // ncclUniqueId (NCCL_UNIQUE_ID_BYTES = 128), passed by value
 struct Rccl {
   void* h = nullptr;
@@ -88,6 +88,14 @@ int n3d_comm_allreduce_sum(void* comm, float* buf, int64_t n, void* stream) {
   Rccl* r = rccl();
   if (!r) N3D_UNSUPPORTED("comm_allreduce_sum: RCCL not loaded");
   if (int e = r->AllReduce(buf, buf, (size_t)n, /* ncclFloat32 */ 7, /* ncclSum */ 0, comm, (hipStream_t)stream)) return rccl_fail("ncclAllReduce", e);
+  return N3D_OK;
+}
+
+int n3d_comm_allreduce_sum_f64(void* comm, double* buf, int64_t n, void* stream) {
+  N3D_CHECK_ARG(comm && buf && n > 0, "comm_allreduce_sum_f64: bad args");
+  Rccl* r = rccl();
+  if (!r) N3D_UNSUPPORTED("comm_allreduce_sum_f64: RCCL not loaded");
+  if (int e = r->AllReduce(buf, buf, (size_t)n, /* ncclFloat64 */ 8, /* ncclSum */ 0, comm, (hipStream_t)stream)) return rccl_fail("ncclAllReduce", e);
   return N3D_OK;
 }
 

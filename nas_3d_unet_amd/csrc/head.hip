@@ -66,6 +66,7 @@ struct HeadFwdArgs {
   const void* t; int64_t tsb, tsc, tsv;      // targets: float, or bytes {0, 1} (TT = uint8_t; strides in elements)
   double* partial; int rows; int Ci, Co;
   int t_quad;   // byte targets, dense and 4-aligned, whole chunks: a lane fetches FOUR voxels' bytes (head_target_quads)
+  double* hpartial; float thr;   // evaluation form (EVAL): hard sums (sum [p >= thr] * t, sum [p >= thr]) per (b, c, row)
 };
 
 // thread = voxel; lanes walk consecutive voxels (x: Ci * sizeof(TX) contiguous bytes per voxel, p / t: strided per channel)
@@ -73,7 +74,9 @@ struct HeadFwdArgs {
 // weights, no run-time channel tests), HEAD_COMAX = any count up to four
 // TT: storage of the targets -- float, or uint8_t holding exactly {0, 1} (generator.py:230-248 yields booleans): a quarter of the
 // target bytes, the same sums bit for bit
-template <typename TX, int CIQ, int NCO, typename TT = float>
+// EVAL: the evaluation form (n3d_head_eval) -- the same conv, sigmoid and soft sums, plus the two hard sums of the thresholded
+// prediction (prediction.py:157-164: p >= thr) per row; two compares and two adds per voxel and channel on an HBM-bound pass
+template <typename TX, int CIQ, int NCO, typename TT = float, bool EVAL = false>
 __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
   N3D_CHAIN_PRIO();
   constexpr int CI = CIQ * 4;
@@ -96,6 +99,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
   float spt[HEAD_COMAX], sp[HEAD_COMAX], st[HEAD_COMAX];
 #pragma unroll
   for (int co = 0; co < HEAD_COMAX; ++co) spt[co] = sp[co] = st[co] = 0.f;     // (a channel that is not computed stays 0)
+  float shi[HEAD_COMAX], shp[HEAD_COMAX];     // EVAL: hard intersection and predicted voxels (integers, exact in fp32 per lane)
+#pragma unroll
+  for (int co = 0; co < HEAD_COMAX; ++co) shi[co] = shp[co] = 0.f;
   const int64_t v0 = (int64_t)blockIdx.x * HEAD_CHUNK;
   // every operand of the workgroup's four voxel rounds is requested before the first use (predicated, no early exit: a `break` in
   // the loop kept each round's loads behind the previous round's stores -- 2.6 TB/s on a 37 MB pass)
@@ -144,6 +150,10 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
         if (a.p) a.p[b * a.psb + co * a.psc + v * a.psv] = pr;
         if (a.logits) a.logits[b * a.psb + co * a.psc + v * a.psv] = z[co];
         spt[co] = fmaf(pr, tv[co], spt[co]); sp[co] += pr; st[co] += tv[co];
+        if constexpr (EVAL) {
+          const float hard = pr >= a.thr ? 1.f : 0.f;
+          shi[co] = fmaf(hard, tv[co], shi[co]); shp[co] += hard;
+        }
       }
     }
   }
@@ -157,10 +167,57 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
     const int co = classsum4_sel(lane);
     if ((lane & 15) == 0) { red[co * 3][wave] = d0; red[co * 3 + 1][wave] = d1; red[co * 3 + 2][wave] = d2; }
   }
+  __shared__ double hred[EVAL ? HEAD_COMAX * 2 : 1][4];
+  if constexpr (EVAL) {
+    const double d3 = wave_sum4_d(shi[0], shi[1], shi[2], shi[3]), d4 = wave_sum4_d(shp[0], shp[1], shp[2], shp[3]);
+    const int co = classsum4_sel(lane);
+    if ((lane & 15) == 0) { hred[co * 2][wave] = d3; hred[co * 2 + 1][wave] = d4; }
+  }
   __syncthreads();
   if (tid < a.Co * 3) {
     const int co = tid / 3, k = tid - co * 3;
     a.partial[(((int64_t)b * a.Co + co) * a.rows + blockIdx.x) * 3 + k] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+  }
+  if constexpr (EVAL) {
+    if (tid < a.Co * 2) {
+      const int co = tid >> 1, k = tid & 1;
+      a.hpartial[(((int64_t)b * a.Co + co) * a.rows + blockIdx.x) * 2 + k] = hred[tid][0] + hred[tid][1] + hred[tid][2] + hred[tid][3];
+    }
+  }
+}
+
+// Evaluation accumulator (n3d_head_eval; layout in include/n3d.h): after the batch loss is formed, thread 0 adds the batch in a
+// fixed order -- loss, batch and sample counts, then per class the hard intersection / predicted / target voxels and the per-sample
+// hard Dice (1 when prediction and target are both empty).  The hard sums hs of the (b, c) pairs (integers held in fp64: exact in any
+// order) come from the finalize's flat walk over the partial rows (rows % 256 == 0, BC <= 64) or, for other shapes, from one wave
+// per pair (head_eval_hard_walk).  BC <= 256.
+struct HeadEvalAcc { const double* hpartial; int Co; double* acc; };
+
+__device__ __forceinline__ void head_eval_hard_walk(const HeadEvalAcc& ev, int rows, int BC, double (*hs)[2]) {
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  for (int i = wave; i < BC; i += 4) {
+    double s0 = 0, s1 = 0;
+    for (int r = lane; r < rows; r += 64) { s0 += ev.hpartial[((int64_t)i * rows + r) * 2]; s1 += ev.hpartial[((int64_t)i * rows + r) * 2 + 1]; }
+    s0 = wave_sum_d(s0); s1 = wave_sum_d(s1);
+    if (lane == 0) { hs[i][0] = s0; hs[i][1] = s1; }
+  }
+}
+
+// thread 0, behind a barrier that orders the hs / sums / loss stores of the finalize
+__device__ __forceinline__ void head_eval_add(const HeadEvalAcc& ev, int BC, const double (*hs)[2], const double* sums, const float* loss) {
+  const int Co = ev.Co, B = BC / Co;
+  double* acc = ev.acc;
+  acc[0] += (double)*loss;
+  acc[1] += 1.0;
+  acc[2] += (double)B;
+  for (int c = 0; c < Co; ++c) {
+    double* ac = acc + 4 + 4 * c;
+    for (int b = 0; b < B; ++b) {
+      const int i = b * Co + c;
+      const double I = hs[i][0], P = hs[i][1], T = sums[i * 3 + 2];
+      ac[0] += I; ac[1] += P; ac[2] += T;
+      ac[3] += (P + T == 0.0) ? 1.0 : 2.0 * I / (P + T);
+    }
   }
 }
 
@@ -169,35 +226,55 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
 // the records t, t + 256, ... , eight of them requested before the first add -- and a (b, c) pair ends every rows / 256 records
 // (uniform over the workgroup).  The one-wave-per-pair walk below paid one memory latency per 64 rows: 19 us at 128^3 (2048 rows),
 // 4.6 us at 64^3, between the head's forward and backward passes.
+// EVAL: the flat walk also reduces the hard sums of n3d_head_eval (same record index, [BC][rows][2]), and the batch is then added
+// into the evaluation accumulator (head_eval_add); the loss is formed by the same code.
+template <bool EVAL = false>
 __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* __restrict__ partial, int rows, int BC, double smooth,
-                                                                 double* __restrict__ sums, float* __restrict__ loss) {
+                                                                 double* __restrict__ sums, float* __restrict__ loss, HeadEvalAcc ev) {
   __shared__ double ratio[256];
   __shared__ double red[64][3][4];
+  __shared__ double hred[EVAL ? 64 : 1][2][4];
+  __shared__ double hs[EVAL ? 256 : 1][2];
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   if ((rows & 255) == 0 && BC <= 64) {
     const int per = rows >> 8, M = BC * per;
     double s[3] = {0, 0, 0};
+    double h[2] = {0, 0};
     int left = per, pair = 0;
     for (int m0 = 0; m0 < M; m0 += 8) {
       double v[8][3];
+      double hv[EVAL ? 8 : 1][2];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const bool ok = m0 + u < M;
         const double* rec = partial + ((int64_t)(ok ? m0 + u : 0) * 256 + t) * 3;
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[u][k] = rec[k];
+        if constexpr (EVAL) {
+          const double* hrec = ev.hpartial + ((int64_t)(ok ? m0 + u : 0) * 256 + t) * 2;
+          hv[u][0] = hrec[0]; hv[u][1] = hrec[1];
+        }
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         if (m0 + u >= M) break;
 #pragma unroll
         for (int k = 0; k < 3; ++k) s[k] += v[u][k];
+        if constexpr (EVAL) { h[0] += hv[u][0]; h[1] += hv[u][1]; }
         if (--left == 0) {
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             const double w = wave_sum_d(s[k]);
             if (lane == 0) red[pair][k][wave] = w;
             s[k] = 0;
+          }
+          if constexpr (EVAL) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const double w = wave_sum_d(h[k]);
+              if (lane == 0) hred[pair][k][wave] = w;
+              h[k] = 0;
+            }
           }
           left = per; ++pair;
         }
@@ -210,6 +287,10 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
 #pragma unroll
       for (int k = 0; k < 3; ++k) { q[k] = (red[t][k][0] + red[t][k][1]) + (red[t][k][2] + red[t][k][3]); sums[t * 3 + k] = q[k]; }
       r = (2.0 * q[0] + smooth) / (q[1] + q[2] + smooth);
+      if constexpr (EVAL) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) hs[t][k] = (hred[t][k][0] + hred[t][k][1]) + (hred[t][k][2] + hred[t][k][3]);
+      }
     }
     ratio[t] = r;
     __syncthreads();
@@ -217,9 +298,11 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
       double a = 0;
       for (int i = 0; i < BC; ++i) a += ratio[i];
       *loss = (float)(1.0 - a / BC);
+      if constexpr (EVAL) head_eval_add(ev, BC, hs, sums, loss);
     }
     return;
   }
+  if constexpr (EVAL) head_eval_hard_walk(ev, rows, BC, hs);
   double acc = 0;
   for (int i = wave; i < BC; i += 4) {
     double s[3] = {0, 0, 0};
@@ -240,6 +323,7 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
     double s = 0;
     for (int i = 0; i < 256; i += 64) s += ratio[i];
     *loss = (float)(1.0 - s / BC);
+    if constexpr (EVAL) head_eval_add(ev, BC, hs, sums, loss);
   }
 }
 
@@ -402,15 +486,15 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
 }
 
 // (byte targets: the three-channel form only -- the reference's out_channels, the generator's three boolean maps)
-template <typename TX>
+template <typename TX, bool EVAL = false>
 static bool launch_head_fwd(const HeadFwdArgs& a, int B, bool t_u8, hipStream_t s) {
   const dim3 grid((unsigned)a.rows, (unsigned)B), blk(256);
   const bool three = a.Co == 3;
   if (t_u8 && !three) return false;
 #define N3D_HEAD_FWD(Q_)                                                                                                     \
-  case Q_: if (t_u8) hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, 3, uint8_t>), grid, blk, 0, s, a);                           \
-           else if (three) hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, 3>), grid, blk, 0, s, a);                              \
-           else hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, HEAD_COMAX>), grid, blk, 0, s, a);                                \
+  case Q_: if (t_u8) hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, 3, uint8_t, EVAL>), grid, blk, 0, s, a);                     \
+           else if (three) hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, 3, float, EVAL>), grid, blk, 0, s, a);                 \
+           else hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, HEAD_COMAX, float, EVAL>), grid, blk, 0, s, a);                   \
            break;
   switch (a.Ci / 4) {
     N3D_HEAD_FWD(1) N3D_HEAD_FWD(2) N3D_HEAD_FWD(3) N3D_HEAD_FWD(4) N3D_HEAD_FWD(6) N3D_HEAD_FWD(8)
@@ -489,13 +573,37 @@ int n3d_head_fwd(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t 
   a.qn = h->node_c / 4; a.xns = h->x_node_stride;
   a.p = p; a.psb = psb; a.psc = psc; a.psv = psv; a.logits = logits;
   a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv; a.partial = t ? partial : nullptr; a.rows = (int)cdiv(h->N, HEAD_CHUNK);
-  a.Ci = h->Ci; a.Co = h->Co;
+  a.Ci = h->Ci; a.Co = h->Co; a.hpartial = nullptr; a.thr = 0.f;
   hipStream_t s = (hipStream_t)stream;
   const bool u8 = t && h->t_dtype == N3D_U8;
   a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
   const bool ok = h->x_dtype == N3D_BF16 ? launch_head_fwd<bf16_t>(a, h->B, u8, s) : launch_head_fwd<float>(a, h->B, u8, s);
   if (!ok) N3D_UNSUPPORTED("head_fwd: Ci=%d", h->Ci);
-  if (t) hipLaunchKernelGGL(head_dice_finalize_kernel, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss);
+  if (t) hipLaunchKernelGGL(head_dice_finalize_kernel<>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
+                           HeadEvalAcc{});
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_head_eval(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t psv, const void* t, int64_t tsb, int64_t tsc, int64_t tsv,
+                  float smooth, float thr, double* partial, double* hpartial, double* sums, float* loss, double* acc, void* stream) {
+  if (int e = check_head(h, "head_eval")) return e;
+  N3D_CHECK_ARG(!h->gate, "head_eval: the evaluation head has no Dropout3d gate (eval mode)");
+  N3D_CHECK_ARG(t && partial && hpartial && sums && loss && acc, "head_eval: needs t, partial, hpartial, sums, loss and acc");
+  N3D_CHECK_ARG(h->B * h->Co <= 256, "head_eval: B * Co <= 256 (B=%d Co=%d)", h->B, h->Co);
+  HeadFwdArgs a;
+  a.x = h->x; a.xld = h->xld; a.N = h->N; a.w = h->w; a.bias = h->bias; a.gate = nullptr;
+  a.qn = h->node_c / 4; a.xns = h->x_node_stride;
+  a.p = p; a.psb = psb; a.psc = psc; a.psv = psv; a.logits = nullptr;
+  a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv; a.partial = partial; a.rows = (int)cdiv(h->N, HEAD_CHUNK);
+  a.Ci = h->Ci; a.Co = h->Co; a.hpartial = hpartial; a.thr = thr;
+  hipStream_t s = (hipStream_t)stream;
+  const bool u8 = h->t_dtype == N3D_U8;
+  a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
+  const bool ok = h->x_dtype == N3D_BF16 ? launch_head_fwd<bf16_t, true>(a, h->B, u8, s) : launch_head_fwd<float, true>(a, h->B, u8, s);
+  if (!ok) N3D_UNSUPPORTED("head_eval: Ci=%d", h->Ci);
+  hipLaunchKernelGGL(head_dice_finalize_kernel<true>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
+                     HeadEvalAcc{hpartial, h->Co, acc});
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }

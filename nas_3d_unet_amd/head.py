@@ -4,11 +4,16 @@ dropout_rate=p, ops_order='weight'), nn.Sigmoid())`, and loss.py:12-14 behind it
 `run(head, x)` = Dropout3d -> 1x1x1 conv -> sigmoid in ONE kernel (n3d_head_fwd) with a one-pass backward (n3d_head_bwd);
 `run_loss(head, x, t, smooth)` additionally forms the Dice sums in the forward pass and the Dice gradient inside the
 backward pass, so the trainers' step has no separate sigmoid / Dice passes over (B, n_out, D, H, W).
+`run_eval(head, x, t, acc)` is the evaluation form (n3d_head_eval, no autograd): eval-mode head, Dice loss and the region counts of
+the thresholded prediction in one pass, added into a device accumulator that `eval_figures` turns into an `EvalResult`.
 The modules (and their state-dict names `last_conv.0.conv.*`) stay the reference's; only what runs underneath differs.
 Shapes the fused kernels do not take (see include/n3d.h) fall back to the op-by-op path.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -118,3 +123,44 @@ def run_loss(head, x, t, smooth=1e-6):
         return WeightedDiceLoss(smooth=smooth)(p, t if t.dtype == torch.float32 else t.to(torch.float32)), p.detach()
     op = head[0]
     return HeadDiceFn.apply(_gate(op, x), float(smooth), x, t, op.conv.weight, op.conv.bias)
+
+
+class EvalResult(NamedTuple):
+    """figures of an evaluation pass (trainers' eval_result()): loss = mean batch Dice loss (unrounded); dice = per class the mean
+    over samples of the hard Dice of the region p >= thr (1 when prediction and target are both empty); dice_global = per class
+    2 I / (P + T) over every voxel of the pass (1 when both are empty)"""
+    loss: float
+    dice: np.ndarray
+    dice_global: np.ndarray
+    n_batches: int
+    n_samples: int
+
+
+def eval_figures(acc):
+    """EvalResult of an evaluation accumulator (host array of N3D_EVAL_ACC_LEN(co) doubles, include/n3d.h: loss sum, batches,
+    samples, unused, then per class (I, P, T, sum of per-sample hard Dice))"""
+    a = np.asarray(acc, dtype=np.float64).reshape(-1)
+    if a.size < 8 or (a.size - 4) % 4:
+        raise ValueError("eval_figures: an accumulator holds 4 + 4 * out_channels values, got %d" % a.size)
+    nb, ns = a[1], a[2]
+    if nb <= 0 or ns <= 0:
+        raise ValueError("eval_figures: no batch was evaluated")
+    per = a[4:].reshape(-1, 4)
+    i, p, t, dsum = per[:, 0], per[:, 1], per[:, 2], per[:, 3]
+    den = p + t
+    glob = np.where(den > 0, 2.0 * i / np.where(den > 0, den, 1.0), 1.0)
+    return EvalResult(float(a[0] / nb), dsum / ns, glob, int(round(nb)), int(round(ns)))
+
+
+def run_eval(head, x, t, acc, smooth=1e-6, thr=0.5):
+    """eval-mode head on features x (no Dropout3d, no autograd): the Dice loss against t -- bit for bit run_loss's in eval mode --
+    with the region counts of p >= thr, both added into acc (kernels.eval_acc).  Returns the batch loss (0-d device tensor).
+    Only the fused head kernel takes this path: another head shape is an error."""
+    op = head[0]
+    if not fusable(head, x):
+        raise K.N3DError("evaluate: the head is not one the fused evaluation kernel takes (1x1x1 conv of 4..32 channels to <= 4, sigmoid)")
+    if not (t.dtype == torch.float32 or (t.dtype == torch.uint8 and op.conv.weight.shape[0] == 3)):
+        raise K.N3DError("evaluate: targets are float32, or uint8 {0, 1} bytes for a three-channel head (got %s)" % t.dtype)
+    if K._bcv_strides(t) is None:
+        t = t.contiguous()
+    return K.head_eval(_feat_view(x), op.conv.weight, op.conv.bias, t, acc, smooth, thr)[0]

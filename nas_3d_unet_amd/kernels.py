@@ -1581,6 +1581,43 @@ def head_fwd(x, w, bias, gate, t=None, smooth=1e-6, want_logits=False, want_p=Tr
     return p, logits, sums, loss
 
 
+def eval_acc_len(co):
+    """doubles of an evaluation accumulator for a head of co output channels (N3D_EVAL_ACC_LEN, include/n3d.h)"""
+    return 4 + 4 * int(co)
+
+
+def eval_acc(co, device):
+    """a zeroed evaluation accumulator (n3d_head_eval adds every batch into it)"""
+    return torch.zeros(eval_acc_len(co), dtype=torch.float64, device=device)
+
+
+def eval_acc_reset(acc):
+    """zero the accumulator IN PLACE (a captured evaluation graph keeps its address)"""
+    acc.zero_()
+
+
+def head_eval(x, w, bias, t, acc, smooth=1e-6, thr=0.5, want_p=False):
+    """evaluation head (no Dropout3d gate): Dice loss of sigmoid(conv1x1x1(x) + bias) against t -- bit for bit the loss of head_fwd --
+    and the region counts of the prediction p >= thr, all added into the accumulator acc (eval_acc) by the same launches.
+    t: float32, or uint8 bytes {0, 1} (three channels).  Returns (loss 0-d device tensor, p | None)."""
+    lib = _lib.load()
+    h = _head_desc(x, w, bias, None, t=t)
+    dev = x.t.device
+    Co = int(w.shape[0])
+    if acc.dtype != torch.float64 or acc.numel() != eval_acc_len(Co) or not acc.is_contiguous():
+        raise N3DError("head_eval: the accumulator must be a contiguous float64 tensor of %d elements" % eval_acc_len(Co))
+    p = torch.empty((x.B, Co, x.D, x.H, x.W), dtype=torch.float32, device=dev) if want_p else None
+    ts = _bcv_strides(t)
+    rows = int(lib.n3d_head_rows(x.N))
+    partial = torch.empty((x.B, Co, rows, 3), dtype=torch.float64, device=dev)
+    hpartial = torch.empty((x.B, Co, rows, 2), dtype=torch.float64, device=dev)
+    sums = torch.empty((x.B, Co, 3), dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    check(lib.n3d_head_eval(C.byref(h), ptr(p), Co * x.N, x.N, 1, ptr(t), ts[0], ts[1], ts[2], float(smooth), float(thr), ptr(partial),
+                            ptr(hpartial), ptr(sums), ptr(loss), ptr(acc), stream_ptr()), "n3d_head_eval")
+    return loss, p
+
+
 def head_bwd(x, w, bias, gate, dx, dw, dbias, dp=None, t=None, sums=None, dloss=None, smooth=1e-6, accumulate=False):
     """backward of head_fwd in one pass: dx (+)=, dw, dbias.  Either dp (gradient w.r.t. p, any uniform strides) or
     (t, sums[, dloss]) for the fused Dice gradient.  x / dx: Views, or both Planar."""

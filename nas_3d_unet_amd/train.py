@@ -918,6 +918,12 @@ class _GraphTrainer:
         self.loss_fn = WeightedDiceLoss()
         self.lr, self.betas, self.eps = lr, betas, eps
         self.device = next(model.parameters()).device
+        # evaluation pass (evaluate / eval_result): its accumulator, weight packing, and captured graph with its input buffers
+        self._eval_acc = None
+        self._eval_ctx = None
+        self._eval_static = None
+        self._eval_graph = None
+        self._eval_loss = None
         reserve_side_streams(self.device)     # first thing on the GPU (see there), also when THIS trainer will not use them
 
     def _init_side(self, comm, **options):
@@ -1049,6 +1055,120 @@ class _GraphTrainer:
 
     def _side_verdict(self):
         """start of a graph step, before anything of it is issued: the replay monitor's verdict (Trainer); nothing here"""
+
+    # -- evaluation -------------------------------------------------------------------------------
+    EVAL_THRESHOLD = 0.5     # a voxel is predicted in a region when p >= 0.5 (prediction.py:157-164)
+
+    def evaluate(self, x, t):
+        """Evaluation of one validation batch (train.py:138-157 validate(); search.py:251-271): the module the step trains -- its
+        padded twin, its storage configuration, the shell's current softmaxed alphas -- in eval mode (no Dropout3d, no generator
+        advances), forward only (no autograd graph, no gradient or optimizer state touched), with the Dice loss and the region
+        counts of the prediction p >= 0.5 added into the trainer's device accumulator.  Returns the batch loss as a 0-d device
+        tensor (no host sync; overwritten by the next replay).  With graph=True the first call captures an evaluation graph of its own
+        (one stream, weight packing included, so it reads the weights as they are at replay) and later calls of that shape and dtype
+        replay it; another batch shape runs eagerly into the same accumulator.  Not a step: the step count is unchanged."""
+        if self._twin is None:
+            return self._evaluate(x, t)
+        with _fused.padded_switches():
+            return self._evaluate(x, t)
+
+    def eval_result(self, reset=True):
+        """host-visible point of the evaluation pass (synchronises): the accumulated figures as a head.EvalResult(loss, dice,
+        dice_global, n_batches, n_samples); reset=True then zeroes the accumulator in place for the next epoch.  Data parallel:
+        COLLECTIVE -- every rank calls it; the accumulators are SUM-all-reduced over the ranks first, so every rank returns the
+        figures of all the batches evaluated on any of them."""
+        from . import head as _head
+        acc = self._eval_accumulator()
+        tot = acc
+        if self.dp_path:
+            tot = acc.clone()
+            if self.sync._comm is not None:
+                self.sync._comm.allreduce_sum(tot)
+            else:
+                dist.all_reduce(tot, group=self.pg)
+        host = tot.cpu().numpy()
+        if reset:
+            K.eval_acc_reset(acc)
+        return _head.eval_figures(host)
+
+    def eval_accumulator(self):
+        """the device accumulator evaluate() adds into (float64, layout of N3D_EVAL_ACC_LEN in include/n3d.h: loss sum, batches, samples,
+        then per class hard intersection, predicted and target voxels and the sum of per-sample hard Dice); this rank's only"""
+        return self._eval_accumulator()
+
+    def _eval_accumulator(self):
+        if self._eval_acc is None:
+            self._eval_acc = K.eval_acc(self._kernel.last_conv[0].conv.weight.shape[0], self.device)
+        return self._eval_acc
+
+    def _eval_net(self):
+        """(the net whose kernels the evaluation runs, its alphas as a callable returning the softmaxed four, or None)"""
+        return self.net, None
+
+    def _eval_modules(self):
+        seen = {}
+        for root in (self.model, self.net):
+            for m in root.modules():
+                seen.setdefault(id(m), m)
+        return list(seen.values())
+
+    def _evaluate(self, x, t):
+        self._eval_accumulator()
+        if not self.use_graph:
+            return self._eval_pass(x, t)
+        if self._eval_static is None:
+            self._eval_capture(x, t)
+        xs, ts = self._eval_static
+        if x.shape != xs.shape or x.dtype != xs.dtype or t.shape != ts.shape or t.dtype != ts.dtype:
+            return self._eval_pass(x, t)      # (the validation generator's short last batch)
+        if x is not xs:
+            xs.copy_(x)
+        if t is not ts:
+            ts.copy_(t)
+        self._eval_graph.replay()
+        return self._eval_loss
+
+    def _eval_pass(self, x, t):
+        """one evaluation pass on the current stream: weight packing, body, evaluation head + accumulation"""
+        from . import head as _head, unet as _unet
+        if self._eval_ctx is None:
+            self._eval_ctx = K.StepContext(self.device)     # the step's packing context stays as the step left it
+        net, alphas = self._eval_net()
+        mods = self._eval_modules()
+        was = [m.training for m in mods]
+        try:
+            for m in mods:
+                m.training = False
+            with torch.no_grad(), K.step_context(self._eval_ctx):
+                self._eval_ctx.pack_all()
+                # (the input layout of the head as unet.run_loss chooses it: node-planar for float targets)
+                planar = _unet._head_takes_planar(net) and t.dtype == torch.float32
+                body = _unet.body(net, x, alphas() if alphas is not None else None, planar=planar)
+                loss = _head.run_eval(net.last_conv, body, t, self._eval_acc, self.loss_fn.smooth, self.EVAL_THRESHOLD)
+            if not self._eval_ctx.frozen:
+                self._eval_ctx.freeze()
+        finally:
+            for m, w in zip(mods, was):
+                m.training = w
+        return loss
+
+    def _eval_capture(self, x, t):
+        """warm-up passes (allocator, net plan, packing jobs) on the capture stream, then the evaluation graph on one stream; the
+        accumulator comes out as it went in"""
+        keep = self._eval_acc.clone()
+        self._eval_static = (x.clone(), t.clone())
+        s = capture_stream(self.device)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._eval_pass(*self._eval_static)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._eval_acc.copy_(keep)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._eval_loss = self._eval_pass(*self._eval_static)
+        self._eval_graph = g
 
     # -- capture ----------------------------------------------------------------------------------
     def _capture(self, batch):
@@ -1532,6 +1652,10 @@ class SearchTrainer(_GraphTrainer):
         self.sync_alpha = GradSync(self.agrad, self.pg, 1, None, comm, header=self.agrad._n3d_full)
         self.sync_kernel.broadcast(self.fp.flat)
         self.sync_kernel.broadcast(self.aflat)
+
+    def _eval_net(self):
+        """the kernel net (or its padded twin) under the shell's current softmaxed alphas (search.py:154: validate() runs the shell)"""
+        return (self.model.kernel if self._twin is None else self._twin.twin), self.model._soft
 
     @property
     def sync_kernel(self):
