@@ -512,6 +512,39 @@ typedef struct n3d_patch_desc { int32_t corner[3]; int32_t perm[3]; int32_t flip
 int n3d_patch_batch(const float* vol, int Cv, const uint8_t* truth, int X, int Y, int Z, const n3d_patch_desc* descs, int B, int P,
                     int flags, float* x_out, int64_t xld, void* t_out, void* stream);
 
+/* ---- the generator's epoch around that gather (generator.py:68-217): which candidate patches an epoch uses, and batches that
+ * mix volumes.  A patch is "empty" when all of its modalities are zero and "healthy" when all of its labels are zero
+ * (generator.py:202-207); "zero" is numpy's `== 0`: -0.0 is zero, NaN / inf / denormals are not ((bits & 0x7fffffff) != 0).
+ *
+ * Summed-area tables: sat is (X+1, Y+1, Z+1) int32 pairs, (mask 0, mask 1) interleaved, with a zero plane at the low end of every
+ * axis: entry (i, j, k) counts the voxels x < i, y < j, z < k where some channel is nonzero (mask 0) / the label is nonzero
+ * (mask 1; 0 throughout when truth is NULL).  Built once per volume; exact integers, equal to np.cumsum of the masks.
+ * X * Y * Z < 2^31.  sat: 8 * (X+1) * (Y+1) * (Z+1) bytes of device memory. */
+int n3d_volume_sat(const float* vol, int Cv, const uint8_t* truth, int X, int Y, int Z, int32_t* sat, void* stream);
+
+/* A volume of a set (device-resident table of records: n3d_patch_qualify / n3d_patch_gather read it on the device).
+ * data: (Cv, X, Y, Z) contiguous fp32 (Cv common to the set); truth: (X, Y, Z) uint8 labels or NULL; sat: its n3d_volume_sat table. */
+typedef struct n3d_patch_volume {
+  const float* data;
+  const uint8_t* truth;
+  const int32_t* sat;
+  int32_t dims[3];
+  int32_t pad_;
+} n3d_patch_volume;
+
+/* Qualification of N candidate patches of edge P: cand is a DEVICE int32 (N, 4) table of (volume index, corner x, y, z); each
+ * patch [c, c + P) is clipped to its volume and answered from the tables by inclusion-exclusion (8 lookups per mask).
+ * flags[i] (uint8, device): bit 0 = some modality is nonzero, bit 1 = some label is nonzero; 0 for a patch wholly outside its
+ * volume and for a volume index outside [0, nvol). */
+int n3d_patch_qualify(const n3d_patch_volume* vols, int nvol, const int32_t* cand, int64_t N, int P, uint8_t* flags, void* stream);
+
+/* n3d_patch_batch for a batch whose patches come from different volumes of a set: descriptor = n3d_patch_desc + volume index.
+ * Output bit-identical to n3d_patch_batch on each patch's own volume.  vols: the DEVICE table of nvol records; descs: HOST array
+ * of at most N3D_PATCH_MAX_BATCH (perm and volume index checked here).  With t_out, a record without truth gives label 0. */
+typedef struct n3d_patch_gdesc { n3d_patch_desc d; int32_t vol; } n3d_patch_gdesc;
+int n3d_patch_gather(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_gdesc* descs, int B, int P, int flags,
+                     float* x_out, int64_t xld, void* t_out, void* stream);
+
 /* ---- step after the hot path (prediction.py:120-170): stitch the per-patch predictions into the brain-wide volume with
  * mean blending (patches.py:172-207) and fuse the three sigmoid channels into one label volume.
  * n3d_stitch: patches element (b, c, voxel v = (lx*P+ly)*P+lz) at patches[b*sb + c*sc + v*sv] (any of the layouts the

@@ -100,6 +100,16 @@ class PatchDesc(C.Structure):
     _fields_ = [("corner", C.c_int32 * 3), ("perm", C.c_int32 * 3), ("flip", C.c_int32 * 3)]
 
 
+class GatherDesc(C.Structure):
+    """n3d_patch_gdesc (include/n3d.h)"""
+    _fields_ = [("d", PatchDesc), ("vol", C.c_int32)]
+
+
+class PatchVolume(C.Structure):
+    """n3d_patch_volume (include/n3d.h)"""
+    _fields_ = [("data", C.c_void_p), ("truth", C.c_void_p), ("sat", C.c_void_p), ("dims", C.c_int32 * 3), ("pad_", C.c_int32)]
+
+
 _p = C.c_void_p
 _i = C.c_int
 _i64 = C.c_int64
@@ -196,6 +206,9 @@ PROTOTYPES = {
     "n3d_ncdhw_to_ndhwc": (_i, [_p, _p, _i64, _i, _i, _i64, _p]),
     "n3d_ndhwc_to_ncdhw": (_i, [_p, _i64, _p, _i, _i, _i64, _p]),
     "n3d_patch_batch": (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(PatchDesc), _i, _i, _i, _p, _i64, _p, _p]),
+    "n3d_volume_sat": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
+    "n3d_patch_qualify": (_i, [_p, _i, _p, _i64, _i, _p, _p]),
+    "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_stitch": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "n3d_tumor_labels": (_i, [_p, _i64, C.c_double, _i, _p, _p]),
     "n3d_comm_available": (_i, []),

@@ -8,19 +8,17 @@
 namespace n3d {
 
 struct PatchDescs { n3d_patch_desc d[N3D_PATCH_MAX_BATCH]; };
+struct GatherDescs { n3d_patch_gdesc d[N3D_PATCH_MAX_BATCH]; };
 
-// one thread = one output voxel (b, i0, i1, i2); writes are lane-consecutive along i2 (x: Cv floats per voxel)
+// one output voxel (b, i0, i1, i2) of patch d drawn from the volume (vol, truth, X, Y, Z): the index mapping shared by
+// patch_batch_kernel (one volume per launch) and patch_gather_kernel (a volume per patch).  v < P^3.
 // TT: storage of the three target maps -- float, or uint8_t (N3D_PATCH_T_U8: the generator's booleans as bytes, what n3d_head_fwd /
 // n3d_head_bwd read with t_dtype = N3D_U8)
 template <typename TT>
-__global__ __launch_bounds__(256) void patch_batch_kernel(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
-                                                          PatchDescs descs, int P, int inclusive, float* __restrict__ x_out, int64_t xld,
-                                                          TT* __restrict__ t_out, FastDiv fP, FastDiv fPP) {
-  const int b = blockIdx.y;
-  const n3d_patch_desc d = descs.d[b];
-  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void patch_voxel(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
+                                            const n3d_patch_desc& d, int b, uint32_t v, int P, int inclusive, float* __restrict__ x_out,
+                                            int64_t xld, TT* __restrict__ t_out, FastDiv fP, FastDiv fPP) {
   const uint32_t P3 = (uint32_t)P * P * P;
-  if (v >= P3) return;
   uint32_t i0, r, i1, i2;
   fPP.divmod(v, i0, r);
   fP.divmod(r, i1, i2);
@@ -43,7 +41,8 @@ __global__ __launch_bounds__(256) void patch_batch_kernel(const float* __restric
     for (int c = 0; c < Cv; ++c) xo[c] = in ? vol[c * XYZ + sv] : 0.f;
   }
   if (t_out) {
-    const int l = in ? (int)truth[sv] : 0;
+    // (a gathered patch whose volume has no truth reads as label 0 everywhere; n3d_patch_batch never gets here without truth)
+    const int l = (in && truth) ? (int)truth[sv] : 0;
     // generator.py:241-243 -- the inclusive "whole tumour" channel is labels {1, 2}: np.logical_or's third argument
     // is its OUT array there, so label 4 does not enter (reproduced, not corrected)
     const TT c0 = inclusive ? (TT)(l == 1 || l == 4) : (TT)(l == 1);
@@ -52,6 +51,31 @@ __global__ __launch_bounds__(256) void patch_batch_kernel(const float* __restric
     TT* to = t_out + (int64_t)b * 3 * P3 + v;
     to[0] = c0; to[P3] = c1; to[2 * (int64_t)P3] = c2;
   }
+}
+
+// one thread = one output voxel (b, i0, i1, i2); writes are lane-consecutive along i2 (x: Cv floats per voxel)
+template <typename TT>
+__global__ __launch_bounds__(256) void patch_batch_kernel(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
+                                                          PatchDescs descs, int P, int inclusive, float* __restrict__ x_out, int64_t xld,
+                                                          TT* __restrict__ t_out, FastDiv fP, FastDiv fPP) {
+  const int b = blockIdx.y;
+  const n3d_patch_desc d = descs.d[b];
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= (uint32_t)P * P * P) return;
+  patch_voxel<TT>(vol, Cv, truth, X, Y, Z, d, b, v, P, inclusive, x_out, xld, t_out, fP, fPP);
+}
+
+// the same voxels for a batch whose patches come from different volumes of one set (the reference's shuffled candidate list
+// mixes volumes, generator.py:170-193): patch b reads the volume record vols[descs.d[b].vol] (the host checked the index)
+template <typename TT>
+__global__ __launch_bounds__(256) void patch_gather_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, GatherDescs descs, int P, int inclusive,
+                                                           float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out, FastDiv fP, FastDiv fPP) {
+  const int b = blockIdx.y;
+  const n3d_patch_gdesc g = descs.d[b];
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= (uint32_t)P * P * P) return;
+  const n3d_patch_volume r = vols[g.vol];
+  patch_voxel<TT>(r.data, Cv, r.truth, r.dims[0], r.dims[1], r.dims[2], g.d, b, v, P, inclusive, x_out, xld, t_out, fP, fPP);
 }
 
 }  // namespace n3d
@@ -84,6 +108,37 @@ extern "C" int n3d_patch_batch(const float* vol, int Cv, const uint8_t* truth, i
                        (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   else
     hipLaunchKernelGGL(patch_batch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cv, truth, X, Y, Z, pd, P, inclusive, x_out, xld,
+                       (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_patch_gather(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_gdesc* descs, int B, int P, int flags,
+                                float* x_out, int64_t xld, void* t_out, void* stream) {
+  N3D_CHECK_ARG(vols && descs && x_out && nvol >= 1 && Cv >= 1 && P > 0 && B >= 1 && xld >= Cv, "patch_gather: bad args");
+  N3D_CHECK_ARG(B <= N3D_PATCH_MAX_BATCH, "patch_gather: at most %d patches per call", N3D_PATCH_MAX_BATCH);
+  N3D_CHECK_ARG((int64_t)P * P * P < (1ll << 31), "patch_gather: patch too large");
+  GatherDescs gd;
+  for (int i = 0; i < B; ++i) {
+    gd.d[i] = descs[i];
+    N3D_CHECK_ARG(descs[i].vol >= 0 && descs[i].vol < nvol, "patch_gather: descriptor %d names volume %d of a set of %d", i, descs[i].vol, nvol);
+    int seen = 0;
+    for (int a = 0; a < 3; ++a) {
+      N3D_CHECK_ARG(descs[i].d.perm[a] >= 0 && descs[i].d.perm[a] < 3, "patch_gather: perm entries must be 0..2");
+      seen |= 1 << descs[i].d.perm[a];
+    }
+    N3D_CHECK_ARG(seen == 7, "patch_gather: perm must be a permutation of (0,1,2)");
+  }
+  for (int i = B; i < N3D_PATCH_MAX_BATCH; ++i) gd.d[i] = gd.d[0];
+  N3D_CHECK_ARG((flags & ~(N3D_PATCH_INCLUSIVE | N3D_PATCH_T_U8)) == 0, "patch_gather: unknown flag bits %d", flags);
+  const uint32_t P3 = (uint32_t)P * P * P;
+  const int inclusive = flags & N3D_PATCH_INCLUSIVE;
+  const dim3 grid((unsigned)cdiv(P3, 256), B);
+  if (flags & N3D_PATCH_T_U8)
+    hipLaunchKernelGGL(patch_gather_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
+                       (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  else
+    hipLaunchKernelGGL(patch_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
                        (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   N3D_LAUNCH_CHECK();
   return N3D_OK;
