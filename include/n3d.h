@@ -620,6 +620,21 @@ int n3d_stamp(void* out, void* stream);
 int n3d_sync_wait(const void* flag, void* step, void* timeouts, int bump, int64_t max_polls, void* stream);
 /* the same for TWO flags in one launch (both must have reached *step; one time-out is counted if either has not) */
 int n3d_sync_wait2(const void* flag0, const void* flag1, void* step, void* timeouts, int bump, int64_t max_polls, void* stream);
+/* Entry signals: a signal carried by the NEXT kernel of its stream instead of a launch of its own.  n3d_entry_signal_arm attaches
+ * (flag, step, bump) -- the arguments of n3d_sync_signal -- to the next n3d_* launch the calling thread issues; it may be called
+ * twice (two signals, executed in arming order).  If that launch is on `stream` and its kernel is a carrier, one lane of the
+ * kernel's first workgroup does what the signal kernel does before anything else of the kernel runs: the store is ordered behind
+ * everything enqueued on `stream` so far, exactly like n3d_sync_signal, and one dependent kernel boundary goes.  In every other
+ * case (a kernel that carries nothing, a launch on another stream, and the calls that enqueue stream work without a kernel of the
+ * library: n3d_zero, the n3d_comm_* collectives, n3d_stream_capture_end, n3d_graph_launch) the library issues the stand-alone
+ * signal kernel on `stream` IN FRONT OF that work: an armed signal is never lost and never later than "in front of the next
+ * launch".  Calls that enqueue nothing (queries, n3d_host_word_*, n3d_stream_capture_begin, ...) leave it armed.  n3d_entry_signal_flush issues what is armed for `stream` at once (for places with no next launch).
+ * The state is per host thread.  n3d_entry_signal_pending: signals armed and not yet issued (0, 1 or 2);
+ * n3d_entry_signal_counts: signals carried by a kernel / issued stand-alone by the library since the library was loaded. */
+int n3d_entry_signal_arm(void* flag, void* step, int bump, void* stream);
+int n3d_entry_signal_flush(void* stream);
+int n3d_entry_signal_pending(void);
+int n3d_entry_signal_counts(int64_t* carried, int64_t* standalone);
 /* The side streams and their graphs, made through the HIP runtime libn3d is linked against (the one that launches the kernels):
  * a non-blocking stream of the lowest priority the device offers; thread-local capture of a stream into an instantiated
  * executable graph (the side streams are captured NEXT TO torch's capture of the main stream); launch / destroy. */

@@ -232,6 +232,10 @@ PROTOTYPES = {
     "n3d_sync_wait": (_i, [_p, _p, _p, _i, _i64, _p]),
     "n3d_sync_wait2": (_i, [_p, _p, _p, _p, _i, _i64, _p]),
     "n3d_stamp": (_i, [_p, _p]),
+    "n3d_entry_signal_arm": (_i, [_p, _p, _i, _p]),
+    "n3d_entry_signal_flush": (_i, [_p]),
+    "n3d_entry_signal_pending": (_i, []),
+    "n3d_entry_signal_counts": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 # flags (include/n3d.h)

@@ -87,6 +87,7 @@ int n3d_comm_allreduce_sum(void* comm, float* buf, int64_t n, void* stream) {
   N3D_CHECK_ARG(comm && buf && n > 0, "comm_allreduce_sum: bad args");
   Rccl* r = rccl();
   if (!r) N3D_UNSUPPORTED("comm_allreduce_sum: RCCL not loaded");
+  n3d::entry_flush();      // (RCCL enqueues the collective: an armed entry signal goes out in front)
   if (int e = r->AllReduce(buf, buf, (size_t)n, /* ncclFloat32 */ 7, /* ncclSum */ 0, comm, (hipStream_t)stream)) return rccl_fail("ncclAllReduce", e);
   return N3D_OK;
 }
@@ -95,6 +96,7 @@ int n3d_comm_allreduce_sum_f64(void* comm, double* buf, int64_t n, void* stream)
   N3D_CHECK_ARG(comm && buf && n > 0, "comm_allreduce_sum_f64: bad args");
   Rccl* r = rccl();
   if (!r) N3D_UNSUPPORTED("comm_allreduce_sum_f64: RCCL not loaded");
+  n3d::entry_flush();      // (RCCL enqueues the collective: an armed entry signal goes out in front)
   if (int e = r->AllReduce(buf, buf, (size_t)n, /* ncclFloat64 */ 8, /* ncclSum */ 0, comm, (hipStream_t)stream)) return rccl_fail("ncclAllReduce", e);
   return N3D_OK;
 }
@@ -103,6 +105,7 @@ int n3d_comm_broadcast(void* comm, float* buf, int64_t n, int root, void* stream
   N3D_CHECK_ARG(comm && buf && n > 0 && root >= 0, "comm_broadcast: bad args");
   Rccl* r = rccl();
   if (!r) N3D_UNSUPPORTED("comm_broadcast: RCCL not loaded");
+  n3d::entry_flush();      // (RCCL enqueues the collective: an armed entry signal goes out in front)
   if (int e = r->Broadcast(buf, buf, (size_t)n, /* ncclFloat32 */ 7, root, comm, (hipStream_t)stream)) return rccl_fail("ncclBroadcast", e);
   return N3D_OK;
 }

@@ -70,7 +70,8 @@ __device__ __forceinline__ f32x4 mfma_bf16_4x4x4(const uint2 a, const uint2 b, c
 // ACCM: -1 = N3D_ACCUMULATE is read from the flags; 0 / 1 = compiled in (the 8-plane form: the forward launch carries no operand
 // fetch of a previous value and none of its address arithmetic)
 template <int C, int TD, int DIL, int NW, bool P2 = false, int ACCM = -1>
-__global__ __launch_bounds__(64 * NW, 2) void conv_vox64b_kernel(Vx16Args a) {
+__global__ __launch_bounds__(64 * NW, 2) void conv_vox64b_kernel(Vx16Args a, EntrySignal es) {
+  entry_signal(es);      // (n3d_common.h: a stream hand-off signal carried in this kernel's entry)
   N3D_CHAIN_PRIO();
   static_assert(!P2 || C == 4, "the dense two-voxels-per-slot image is the C = 4 form");
   constexpr int HF = C / 4, GH = 4 * NW, GW = 16;
@@ -373,7 +374,8 @@ struct Vs2bArgs {
 };
 
 template <int C, int TD, int DIL>
-__global__ __launch_bounds__(64, 2) void conv_vox_s2b_kernel(Vs2bArgs a) {
+__global__ __launch_bounds__(64, 2) void conv_vox_s2b_kernel(Vs2bArgs a, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   constexpr int HF = C / 4;
   constexpr int LD = 2 * (TD - 1) + 2 * DIL + 1, LH = 7 + 2 * DIL, LW = 31 + 2 * DIL;
@@ -505,7 +507,8 @@ __host__ __device__ constexpr int vupb_p(int dil, int s, int i) { return dil == 
 __host__ __device__ constexpr int vupb_k(int dil, int s, int i) { return dil == 2 ? 1 - s : (s == 0 ? 1 + i : 0); }
 
 template <int C, int DIL>
-__global__ __launch_bounds__(64, 2) void conv_vox_upb_kernel(VupbArgs a) {
+__global__ __launch_bounds__(64, 2) void conv_vox_upb_kernel(VupbArgs a, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   constexpr int HF = C / 4;
   constexpr int LD = 3, LH = 6, LW = 18;
@@ -684,19 +687,20 @@ static Vx16Plan vx16_plan(const n3d_conv_geom* g) {
 // p2: the source is a DENSE 4-channel tensor (pitch 4, 16-byte aligned): the two-voxels-per-slot image
 template <int C, int TD, int DIL>
 static void launch_vox16_t(const Vx16Args& a, const Vx16Plan& p, int B, hipStream_t s, bool p2) {
+  const EntrySignal es = entry_take(s);
   if constexpr (C == 4) {
     if (p2) {
       if constexpr (TD == 4) {
-        if (p.nw == 2) { hipLaunchKernelGGL((conv_vox64b_kernel<C, TD, DIL, 2, true>), dim3(p.tiles * B), dim3(128), p.lds_p2, s, a); return; }
+        if (p.nw == 2) { N3D_LAUNCH((conv_vox64b_kernel<C, TD, DIL, 2, true>), dim3(p.tiles * B), dim3(128), p.lds_p2, s, a, es); return; }
       }
-      hipLaunchKernelGGL((conv_vox64b_kernel<C, TD, DIL, 1, true>), dim3(p.tiles * B), dim3(64), p.lds_p2, s, a);
+      N3D_LAUNCH((conv_vox64b_kernel<C, TD, DIL, 1, true>), dim3(p.tiles * B), dim3(64), p.lds_p2, s, a, es);
       return;
     }
   }
   if constexpr (C == 4 && TD == 4) {
-    if (p.nw == 2) { hipLaunchKernelGGL((conv_vox64b_kernel<C, TD, DIL, 2>), dim3(p.tiles * B), dim3(128), p.lds, s, a); return; }
+    if (p.nw == 2) { N3D_LAUNCH((conv_vox64b_kernel<C, TD, DIL, 2>), dim3(p.tiles * B), dim3(128), p.lds, s, a, es); return; }
   }
-  hipLaunchKernelGGL((conv_vox64b_kernel<C, TD, DIL, 1>), dim3(p.tiles * B), dim3(64), p.lds, s, a);
+  N3D_LAUNCH((conv_vox64b_kernel<C, TD, DIL, 1>), dim3(p.tiles * B), dim3(64), p.lds, s, a, es);
 }
 
 template <int C>
@@ -754,7 +758,7 @@ int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int6
   if (!ws || ws_bytes < need) { set_error("conv(bf16 mfma): workspace too small"); return N3D_ERR_WORKSPACE; }
   // pack modes: vox64b 0 / 1 (data gradient: transposed + flipped), vox_s2b 0 (forward-type gathers only), vox_upb 2 (transposed)
   if (!(flags & N3D_PREPACKED))
-    hipLaunchKernelGGL(pack_vox16_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, w, (bf16_t*)ws, C,
+    N3D_LAUNCH(pack_vox16_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, w, (bf16_t*)ws, C,
                        kind == 3 ? 2 : (kind == 1 && data_grad ? 1 : 0));
   const void* zp = zero_page16_ptr();
   if (!zp) { set_error("conv(bf16 mfma): zero page symbol unavailable"); return N3D_ERR_HIP; }
@@ -775,12 +779,13 @@ int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int6
       a.fT = FastDiv((uint32_t)a.tiles);
       const size_t pstride2 = ((size_t)(4 + 2 * g->dil) * 10 + 63) / 64 * 64, wslots = (((size_t)27 * 16 * 2 + 15) / 16 + 63) / 64 * 64;
       const size_t lds8 = ((size_t)(8 + 2 * g->dil) * pstride2 + wslots) * 16;
+      const EntrySignal es = entry_take(s);
       if (g->dil == 1) {
-        if (acc) hipLaunchKernelGGL((conv_vox64b_kernel<4, 8, 1, 1, true, 1>), dim3(a.tiles * g->B), dim3(64), lds8, s, a);
-        else hipLaunchKernelGGL((conv_vox64b_kernel<4, 8, 1, 1, true, 0>), dim3(a.tiles * g->B), dim3(64), lds8, s, a);
+        if (acc) N3D_LAUNCH((conv_vox64b_kernel<4, 8, 1, 1, true, 1>), dim3(a.tiles * g->B), dim3(64), lds8, s, a, es);
+        else N3D_LAUNCH((conv_vox64b_kernel<4, 8, 1, 1, true, 0>), dim3(a.tiles * g->B), dim3(64), lds8, s, a, es);
       } else {
-        if (acc) hipLaunchKernelGGL((conv_vox64b_kernel<4, 8, 2, 1, true, 1>), dim3(a.tiles * g->B), dim3(64), lds8, s, a);
-        else hipLaunchKernelGGL((conv_vox64b_kernel<4, 8, 2, 1, true, 0>), dim3(a.tiles * g->B), dim3(64), lds8, s, a);
+        if (acc) N3D_LAUNCH((conv_vox64b_kernel<4, 8, 2, 1, true, 1>), dim3(a.tiles * g->B), dim3(64), lds8, s, a, es);
+        else N3D_LAUNCH((conv_vox64b_kernel<4, 8, 2, 1, true, 0>), dim3(a.tiles * g->B), dim3(64), lds8, s, a, es);
       }
       hipError_t e__ = hipGetLastError();
       if (e__ != hipSuccess) { set_error("conv(bf16 mfma): launch error: %s", hipGetErrorString(e__)); return N3D_ERR_HIP; }
@@ -794,11 +799,12 @@ int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int6
     a.wq = (const bf16_t*)ws; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v.tiles; a.tiles = v.tiles; a.zero_page = zp;
     a.fT = FastDiv((uint32_t)v.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
     const dim3 grid(v.tiles * g->B), blk(64);
+    const EntrySignal es = entry_take(s);
     if (v.C == 4) {
-      if (v.td == 2) { if (v.dil == 1) hipLaunchKernelGGL((conv_vox_s2b_kernel<4, 2, 1>), grid, blk, v.lds, s, a); else hipLaunchKernelGGL((conv_vox_s2b_kernel<4, 2, 2>), grid, blk, v.lds, s, a); }
-      else { if (v.dil == 1) hipLaunchKernelGGL((conv_vox_s2b_kernel<4, 1, 1>), grid, blk, v.lds, s, a); else hipLaunchKernelGGL((conv_vox_s2b_kernel<4, 1, 2>), grid, blk, v.lds, s, a); }
+      if (v.td == 2) { if (v.dil == 1) N3D_LAUNCH((conv_vox_s2b_kernel<4, 2, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_s2b_kernel<4, 2, 2>), grid, blk, v.lds, s, a, es); }
+      else { if (v.dil == 1) N3D_LAUNCH((conv_vox_s2b_kernel<4, 1, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_s2b_kernel<4, 1, 2>), grid, blk, v.lds, s, a, es); }
     } else {
-      if (v.dil == 1) hipLaunchKernelGGL((conv_vox_s2b_kernel<8, 1, 1>), grid, blk, v.lds, s, a); else hipLaunchKernelGGL((conv_vox_s2b_kernel<8, 1, 2>), grid, blk, v.lds, s, a);
+      if (v.dil == 1) N3D_LAUNCH((conv_vox_s2b_kernel<8, 1, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_s2b_kernel<8, 1, 2>), grid, blk, v.lds, s, a, es);
     }
   } else {
     const VupbPlan v = vupb_plan(g, data_grad);
@@ -807,8 +813,9 @@ int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int6
     a.wq = (const bf16_t*)ws; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v.tiles; a.tiles = v.tiles; a.zero_page = zp;
     a.fT = FastDiv((uint32_t)v.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
     const dim3 grid(v.tiles * g->B), blk(64);
-    if (v.C == 4) { if (v.dil == 1) hipLaunchKernelGGL((conv_vox_upb_kernel<4, 1>), grid, blk, v.lds, s, a); else hipLaunchKernelGGL((conv_vox_upb_kernel<4, 2>), grid, blk, v.lds, s, a); }
-    else { if (v.dil == 1) hipLaunchKernelGGL((conv_vox_upb_kernel<8, 1>), grid, blk, v.lds, s, a); else hipLaunchKernelGGL((conv_vox_upb_kernel<8, 2>), grid, blk, v.lds, s, a); }
+    const EntrySignal es = entry_take(s);
+    if (v.C == 4) { if (v.dil == 1) N3D_LAUNCH((conv_vox_upb_kernel<4, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_upb_kernel<4, 2>), grid, blk, v.lds, s, a, es); }
+    else { if (v.dil == 1) N3D_LAUNCH((conv_vox_upb_kernel<8, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_upb_kernel<8, 2>), grid, blk, v.lds, s, a, es); }
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(bf16 mfma) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }

@@ -45,7 +45,8 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
 }
 
 template <int CO_T, int SV, int CSQ, typename TS = float, typename TD = float>
-__global__ __launch_bounds__(256) void conv_gather_kernel(GatherArgs a) {
+__global__ __launch_bounds__(256) void conv_gather_kernel(GatherArgs a, EntrySignal es) {
+  entry_signal(es);      // (n3d_common.h: a stream hand-off signal carried in this kernel's entry)
   N3D_CHAIN_PRIO();
   __shared__ double red[4][CO_T * 2];
   const int b = blockIdx.z, cot = blockIdx.y;
@@ -330,11 +331,12 @@ static void launch_gather_t(GatherArgs a, int B, hipStream_t s) {
   a.fWh = FastDiv((uint32_t)(a.Wd / 2 > 0 ? a.Wd / 2 : 1)); a.fHh = FastDiv((uint32_t)(a.Hd / 2 > 0 ? a.Hd / 2 : 1));
   dim3 grid((unsigned)(a.cls ? 8 * cdiv(Nd / 8, 256) : cdiv(Nd, 256)), (unsigned)(a.Cdp / CO_T), (unsigned)B);
   const size_t wbytes = (size_t)a.k * a.k * a.k * a.Cs * CO_T * sizeof(float);
-  if (!vec) hipLaunchKernelGGL((conv_gather_kernel<CO_T, 1, 0, TS, TD>), grid, dim3(256), 0, s, a);
-  else if (a.Cs == 4) hipLaunchKernelGGL((conv_gather_kernel<CO_T, 4, 1, TS, TD>), grid, dim3(256), wbytes, s, a);
-  else if (a.Cs == 8) hipLaunchKernelGGL((conv_gather_kernel<CO_T, 4, 2, TS, TD>), grid, dim3(256), wbytes, s, a);
-  else if (a.Cs == 12) hipLaunchKernelGGL((conv_gather_kernel<CO_T, 4, 3, TS, TD>), grid, dim3(256), wbytes, s, a);
-  else hipLaunchKernelGGL((conv_gather_kernel<CO_T, 4, 0, TS, TD>), grid, dim3(256), 0, s, a);
+  const EntrySignal es = entry_take(s);
+  if (!vec) N3D_LAUNCH((conv_gather_kernel<CO_T, 1, 0, TS, TD>), grid, dim3(256), 0, s, a, es);
+  else if (a.Cs == 4) N3D_LAUNCH((conv_gather_kernel<CO_T, 4, 1, TS, TD>), grid, dim3(256), wbytes, s, a, es);
+  else if (a.Cs == 8) N3D_LAUNCH((conv_gather_kernel<CO_T, 4, 2, TS, TD>), grid, dim3(256), wbytes, s, a, es);
+  else if (a.Cs == 12) N3D_LAUNCH((conv_gather_kernel<CO_T, 4, 3, TS, TD>), grid, dim3(256), wbytes, s, a, es);
+  else N3D_LAUNCH((conv_gather_kernel<CO_T, 4, 0, TS, TD>), grid, dim3(256), 0, s, a, es);
 }
 
 template <typename TS, typename TD>
@@ -408,7 +410,8 @@ __device__ __forceinline__ float4 k1_f4(const uint2 v) {
 // 57 -> 45 us at 2 x 128^3 fp32 (0.59 -> 0.74 of 8 TB/s), bf16 output 45 -> 38; the other forward shapes spill under that cap and keep 2.
 constexpr int k1_min_waves(int csq, int cdq, bool extra) { return (extra && csq * cdq <= 3) ? 4 : ((!extra && csq == 1 && cdq == 3) ? 3 : 2); }
 template <int CSQ, int CDQ, bool EXTRA, typename TS = float, typename TD = float>   // Cs = 4 * CSQ, Cd = 4 * CDQ
-__global__ __launch_bounds__(256, k1_min_waves(CSQ, CDQ, EXTRA)) void conv_k1_kernel(K1Args a) {
+__global__ __launch_bounds__(256, k1_min_waves(CSQ, CDQ, EXTRA)) void conv_k1_kernel(K1Args a, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   constexpr int VPT = EXTRA ? 2 : K1_VPB / 256;   // data-gradient form: no statistics rows to agree on, fewer registers per voxel
   __shared__ __attribute__((aligned(16))) float4 wl[CSQ * 4 * CDQ];
@@ -615,10 +618,11 @@ static bool k1_dims_ok(const n3d_conv_geom* g, bool data_grad, int Cs, int Cd) {
 
 template <int CSQ, bool EXTRA, typename TS, typename TD>
 static void launch_k1_e(const K1Args& a, int Cd, dim3 grid, hipStream_t s) {
+  const EntrySignal es = entry_take(s);
   switch (Cd / 4) {
-    case 1: hipLaunchKernelGGL((conv_k1_kernel<CSQ, 1, EXTRA, TS, TD>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((conv_k1_kernel<CSQ, 2, EXTRA, TS, TD>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((conv_k1_kernel<CSQ, 3, EXTRA, TS, TD>), grid, dim3(256), 0, s, a); break;
+    case 1: N3D_LAUNCH((conv_k1_kernel<CSQ, 1, EXTRA, TS, TD>), grid, dim3(256), 0, s, a, es); break;
+    case 2: N3D_LAUNCH((conv_k1_kernel<CSQ, 2, EXTRA, TS, TD>), grid, dim3(256), 0, s, a, es); break;
+    default: N3D_LAUNCH((conv_k1_kernel<CSQ, 3, EXTRA, TS, TD>), grid, dim3(256), 0, s, a, es); break;
   }
 }
 template <int CSQ, typename TS, typename TD>
@@ -746,9 +750,9 @@ static bool k1_wgrad_shape_ok(const n3d_conv_geom* g) {
 template <int CIQ, typename TS, typename TD>
 static void launch_k1_wgrad_d(const K1WgArgs& a, int Co, int nchunks, hipStream_t s) {
   switch (Co / 4) {
-    case 1: hipLaunchKernelGGL((conv_k1_wgrad_kernel<CIQ, 1, TS, TD>), dim3(nchunks), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((conv_k1_wgrad_kernel<CIQ, 2, TS, TD>), dim3(nchunks), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((conv_k1_wgrad_kernel<CIQ, 3, TS, TD>), dim3(nchunks), dim3(256), 0, s, a); break;
+    case 1: N3D_LAUNCH((conv_k1_wgrad_kernel<CIQ, 1, TS, TD>), dim3(nchunks), dim3(256), 0, s, a); break;
+    case 2: N3D_LAUNCH((conv_k1_wgrad_kernel<CIQ, 2, TS, TD>), dim3(nchunks), dim3(256), 0, s, a); break;
+    default: N3D_LAUNCH((conv_k1_wgrad_kernel<CIQ, 3, TS, TD>), dim3(nchunks), dim3(256), 0, s, a); break;
   }
 }
 template <int CIQ>
@@ -780,7 +784,8 @@ struct K1nArgs {
 };
 
 template <int CIQ, int COQ, bool APPLY, typename TS, typename TD>
-__global__ __launch_bounds__(256) void k1n_bwd_kernel(K1nArgs q) {
+__global__ __launch_bounds__(256) void k1n_bwd_kernel(K1nArgs q, EntrySignal es) {
+  entry_signal(es);
   constexpr int CI = CIQ * 4, CO = COQ * 4, NV = APPLY ? CI * CO : CO * 3;
   __shared__ float wsm[CO][CI + 1];
   __shared__ float red[4][NV];
@@ -874,11 +879,12 @@ static int k1n_chunk(int64_t N) {      // voxels per workgroup: 2048, fewer on t
 
 template <bool APPLY, typename TS, typename TD>
 static bool launch_k1n_t(const K1nArgs& q, int Ci, int Co, dim3 grid, hipStream_t s) {
-  if (Ci == 4 && Co == 4) hipLaunchKernelGGL((k1n_bwd_kernel<1, 1, APPLY, TS, TD>), grid, dim3(256), 0, s, q);
-  else if (Ci == 4 && Co == 8) hipLaunchKernelGGL((k1n_bwd_kernel<1, 2, APPLY, TS, TD>), grid, dim3(256), 0, s, q);
-  else if (Ci == 4 && Co == 12) hipLaunchKernelGGL((k1n_bwd_kernel<1, 3, APPLY, TS, TD>), grid, dim3(256), 0, s, q);
-  else if (Ci == 8 && Co == 4) hipLaunchKernelGGL((k1n_bwd_kernel<2, 1, APPLY, TS, TD>), grid, dim3(256), 0, s, q);
-  else return false;
+  if (!((Ci == 4 && (Co == 4 || Co == 8 || Co == 12)) || (Ci == 8 && Co == 4))) return false;
+  const EntrySignal es = entry_take(s);      // (behind the test: a taken signal must be launched)
+  if (Ci == 4 && Co == 4) N3D_LAUNCH((k1n_bwd_kernel<1, 1, APPLY, TS, TD>), grid, dim3(256), 0, s, q, es);
+  else if (Ci == 4 && Co == 8) N3D_LAUNCH((k1n_bwd_kernel<1, 2, APPLY, TS, TD>), grid, dim3(256), 0, s, q, es);
+  else if (Ci == 4 && Co == 12) N3D_LAUNCH((k1n_bwd_kernel<1, 3, APPLY, TS, TD>), grid, dim3(256), 0, s, q, es);
+  else N3D_LAUNCH((k1n_bwd_kernel<2, 1, APPLY, TS, TD>), grid, dim3(256), 0, s, q, es);
   return true;
 }
 template <bool APPLY>
@@ -1729,10 +1735,10 @@ template <int CI_T, int CO_T>
 static void launch_wgrad_t(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
   const bool sb = a.flags & N3D_SRC_BF16, db = a.flags & N3D_DST_BF16;
   const dim3 grid(p.nchunks, p.ntiles);
-  if (sb && db) hipLaunchKernelGGL((conv_wgrad_kernel<CI_T, CO_T, bf16_t, bf16_t>), grid, dim3(256), 0, s, a);
-  else if (sb) hipLaunchKernelGGL((conv_wgrad_kernel<CI_T, CO_T, bf16_t, float>), grid, dim3(256), 0, s, a);
-  else if (db) hipLaunchKernelGGL((conv_wgrad_kernel<CI_T, CO_T, float, bf16_t>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((conv_wgrad_kernel<CI_T, CO_T, float, float>), grid, dim3(256), 0, s, a);
+  if (sb && db) N3D_LAUNCH((conv_wgrad_kernel<CI_T, CO_T, bf16_t, bf16_t>), grid, dim3(256), 0, s, a);
+  else if (sb) N3D_LAUNCH((conv_wgrad_kernel<CI_T, CO_T, bf16_t, float>), grid, dim3(256), 0, s, a);
+  else if (db) N3D_LAUNCH((conv_wgrad_kernel<CI_T, CO_T, float, bf16_t>), grid, dim3(256), 0, s, a);
+  else N3D_LAUNCH((conv_wgrad_kernel<CI_T, CO_T, float, float>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace n3d
@@ -1916,10 +1922,10 @@ static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, 
     const dim3 grid((unsigned)cdiv(Nd * (a.C / 4), 256), g->B);
     const size_t shm = (size_t)(a.C / 4) * 27 * sizeof(float4);
     // storage types of source / destination (round 5: bf16 storage of the C <= 8 cells also with depthwise primitives)
-    if (sb16 && db16) hipLaunchKernelGGL((dw_gather_kernel<bf16_t, bf16_t>), grid, dim3(256), shm, s, a);
-    else if (sb16) hipLaunchKernelGGL((dw_gather_kernel<bf16_t, float>), grid, dim3(256), shm, s, a);
-    else if (db16) hipLaunchKernelGGL((dw_gather_kernel<float, bf16_t>), grid, dim3(256), shm, s, a);
-    else hipLaunchKernelGGL((dw_gather_kernel<float, float>), grid, dim3(256), shm, s, a);
+    if (sb16 && db16) N3D_LAUNCH((dw_gather_kernel<bf16_t, bf16_t>), grid, dim3(256), shm, s, a);
+    else if (sb16) N3D_LAUNCH((dw_gather_kernel<bf16_t, float>), grid, dim3(256), shm, s, a);
+    else if (db16) N3D_LAUNCH((dw_gather_kernel<float, bf16_t>), grid, dim3(256), shm, s, a);
+    else N3D_LAUNCH((dw_gather_kernel<float, float>), grid, dim3(256), shm, s, a);
     N3D_LAUNCH_CHECK();
     return N3D_OK;
   }
@@ -1958,7 +1964,7 @@ static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, 
   a.wp = wp;
   const int total = taps * a.Cs * a.Cdp;
   if (!(flags & N3D_PREPACKED))
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, g->Co, g->Ci, taps, a.Cdp, data_grad ? 1 : 0);
+    N3D_LAUNCH(pack_weights_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, g->Co, g->Ci, taps, a.Cdp, data_grad ? 1 : 0);
   if (stats && gather_class_mode(a.den, a.k, a.Dd, a.Hd, a.Wd, a.Cs, true) && !((a.Cs % 4 == 0) && (a.sld % 4 == 0) && aligned_quad(a.src, sb16))) {
     set_error("conv: statistics on this shape need a 16-byte aligned source (n3d_conv_stats_rows assumed the parity-class kernel)");
     return N3D_ERR_UNSUPPORTED;
@@ -2150,7 +2156,7 @@ static int run_wgrad(const n3d_conv_geom* g, const float* x, int64_t xld, const 
             q.x = x; q.xld = xld; q.dy = dy; q.dyld = dyld; q.D = g->Di; q.H = g->Hi; q.W = g->Wi; q.B = g->B; q.C = g->Ci;
             q.partial = wsf; q.pbias = wsf + (size_t)chunks * 27 * g->Ci;
             q.tiles_per_sample = tiles_per_sample; q.tiles_total = (int)tiles_total; q.tiles_per_wg = tpw; q.zero_page = zp;
-            hipLaunchKernelGGL(dw_wgrad_tile_kernel, dim3((unsigned)chunks, (unsigned)quads), dim3(256), 0, s, q);
+            N3D_LAUNCH(dw_wgrad_tile_kernel, dim3((unsigned)chunks, (unsigned)quads), dim3(256), 0, s, q);
             n3d_final_job job;
             fill_job(&job, q.partial, q.pbias, dw, dbias, chunks, 27, 1, 1, 1, g->Ci, g->Ci, 1, 27);
             if (deferred) *deferred = job;
@@ -2176,16 +2182,16 @@ static int run_wgrad(const n3d_conv_geom* g, const float* x, int64_t xld, const 
     if (flags & N3D_ANY_BF16) {
       // bf16 storage (round 5: the C <= 8 cells of the bf16 configuration): both tensors bf16, 4 or 8 channels
       if (!(sb16 && db16) || (cpb != 1 && cpb != 2)) N3D_UNSUPPORTED("depthwise weight gradient: bf16 storage is built for x and dy both bf16, C = 4 / 8");
-      if (cpb == 1) hipLaunchKernelGGL((dw_wgrad_kernel<1, bf16_t, bf16_t>), dim3(nchunks), dim3(256), shm, s, a);
-      else hipLaunchKernelGGL((dw_wgrad_kernel<2, bf16_t, bf16_t>), dim3(nchunks), dim3(256), shm, s, a);
+      if (cpb == 1) N3D_LAUNCH((dw_wgrad_kernel<1, bf16_t, bf16_t>), dim3(nchunks), dim3(256), shm, s, a);
+      else N3D_LAUNCH((dw_wgrad_kernel<2, bf16_t, bf16_t>), dim3(nchunks), dim3(256), shm, s, a);
     } else
     switch (cpb) {
-      case 1: hipLaunchKernelGGL(dw_wgrad_kernel<1>, dim3(nchunks), dim3(256), shm, s, a); break;
-      case 2: hipLaunchKernelGGL(dw_wgrad_kernel<2>, dim3(nchunks), dim3(256), shm, s, a); break;
-      case 4: hipLaunchKernelGGL(dw_wgrad_kernel<4>, dim3(nchunks), dim3(256), shm, s, a); break;
-      case 8: hipLaunchKernelGGL(dw_wgrad_kernel<8>, dim3(nchunks), dim3(256), shm, s, a); break;
-      case 16: hipLaunchKernelGGL(dw_wgrad_kernel<16>, dim3(nchunks), dim3(256), shm, s, a); break;
-      default: hipLaunchKernelGGL(dw_wgrad_kernel<0>, dim3(nchunks), dim3(256), shm, s, a); break;
+      case 1: N3D_LAUNCH(dw_wgrad_kernel<1>, dim3(nchunks), dim3(256), shm, s, a); break;
+      case 2: N3D_LAUNCH(dw_wgrad_kernel<2>, dim3(nchunks), dim3(256), shm, s, a); break;
+      case 4: N3D_LAUNCH(dw_wgrad_kernel<4>, dim3(nchunks), dim3(256), shm, s, a); break;
+      case 8: N3D_LAUNCH(dw_wgrad_kernel<8>, dim3(nchunks), dim3(256), shm, s, a); break;
+      case 16: N3D_LAUNCH(dw_wgrad_kernel<16>, dim3(nchunks), dim3(256), shm, s, a); break;
+      default: N3D_LAUNCH(dw_wgrad_kernel<0>, dim3(nchunks), dim3(256), shm, s, a); break;
     }
     // fixed-order slab reduction through the common finalize: one "tile" per tap, ci_t = 1, co_t = C, Ci = 1
     n3d_final_job job;
@@ -2364,7 +2370,7 @@ int n3d_dwconv_batch(const n3d_dw_job* jobs, int n, void* stream) {
     if (i == 0) { Nd0 = Nd; C0 = js.j[i].C; B0 = q->g->B; }
     N3D_CHECK_ARG(Nd == Nd0 && js.j[i].C == C0 && q->g->B == B0, "dwconv_batch: the jobs must share output shape, channel count and batch");
   }
-  hipLaunchKernelGGL(dw_gatherN_kernel, dim3((unsigned)cdiv(Nd0 * (C0 / 4), 256), B0, n), dim3(256), (size_t)(C0 / 4) * 27 * sizeof(float4),
+  N3D_LAUNCH(dw_gatherN_kernel, dim3((unsigned)cdiv(Nd0 * (C0 / 4), 256), B0, n), dim3(256), (size_t)(C0 / 4) * 27 * sizeof(float4),
                      (hipStream_t)stream, js);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2590,7 +2596,7 @@ int n3d_pack_batch(const n3d_pack_job* jobs, int njobs, void* stream) {
       d.mode = (uint8_t)(q.layout | (q.data_grad ? 16 : 0));
     }
     for (int i = n; i < N3D_PACK_JOBS; ++i) pj.j[i] = pj.j[0];
-    if (nblk > 0) hipLaunchKernelGGL(pack_batch_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, pj);
+    if (nblk > 0) N3D_LAUNCH(pack_batch_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, pj);
     base += n;
   }
   N3D_LAUNCH_CHECK();
@@ -2628,7 +2634,7 @@ int n3d_wgrad_finalize_batch(const n3d_final_job* jobs, int njobs, void* stream)
       d.tci = (uint8_t)q.tci; d.tco = (uint8_t)q.tco; d.ci_t = (uint16_t)q.ci_t; d.co_t = (uint16_t)q.co_t; d.taps = (uint8_t)q.taps; d.pad_ = 0;
     }
     for (int i = n; i < N3D_FINAL_JOBS; ++i) fj.j[i] = fj.j[0];
-    if (nblk > 0) hipLaunchKernelGGL(wgrad_final_batch_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, fj);
+    if (nblk > 0) N3D_LAUNCH(wgrad_final_batch_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, fj);
     base += n;
   }
   N3D_LAUNCH_CHECK();
@@ -2718,12 +2724,12 @@ int n3d_convT_bwd_weight(const n3d_conv_geom* g, const float* x, int64_t xld, co
     // dy is the SECOND activation tensor of a transposed weight-gradient call... but the kernel roles are swapped (see above):
     // the caller's dy (Ci channels, i side) carries the N3D_DST_BF16 flag
     if (flags & N3D_DST_BF16)
-      hipLaunchKernelGGL(channel_sum_kernel<bf16_t>, dim3((unsigned)nblk), dim3(256), (size_t)4 * (g->Ci / 4) * 4 * sizeof(float), s,
+      N3D_LAUNCH(channel_sum_kernel<bf16_t>, dim3((unsigned)nblk), dim3(256), (size_t)4 * (g->Ci / 4) * 4 * sizeof(float), s,
                          reinterpret_cast<const bf16_t*>(dy), dyld, total, g->Ci, chunk, wsf);
     else
-      hipLaunchKernelGGL(channel_sum_kernel<float>, dim3((unsigned)nblk), dim3(256), (size_t)4 * (g->Ci / 4) * 4 * sizeof(float), s, dy, dyld, total, g->Ci,
+      N3D_LAUNCH(channel_sum_kernel<float>, dim3((unsigned)nblk), dim3(256), (size_t)4 * (g->Ci / 4) * 4 * sizeof(float), s, dy, dyld, total, g->Ci,
                          chunk, wsf);
-    hipLaunchKernelGGL(channel_sum_final_kernel, dim3((unsigned)cdiv(g->Ci, 256)), dim3(256), 0, s, wsf, (int)nblk, g->Ci, dbias);
+    N3D_LAUNCH(channel_sum_final_kernel, dim3((unsigned)cdiv(g->Ci, 256)), dim3(256), 0, s, wsf, (int)nblk, g->Ci, dbias);
     N3D_LAUNCH_CHECK();
   }
   return N3D_OK;

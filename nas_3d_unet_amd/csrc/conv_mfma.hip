@@ -562,7 +562,8 @@ __global__ __launch_bounds__(KS == 16 ? 1024 : 256, KS == 16 ? 4 : 2) void conv_
 struct PairArgs { MfArgs a0, a1; int n0, gx0, gx1; };
 
 template <int KS>
-__global__ __launch_bounds__(KS == 16 ? 1024 : 256, KS == 16 ? 4 : 2) void conv_gemm16_pair_kernel(PairArgs q) {
+__global__ __launch_bounds__(KS == 16 ? 1024 : 256, KS == 16 ? 4 : 2) void conv_gemm16_pair_kernel(PairArgs q, EntrySignal es) {
+  entry_signal(es);      // (n3d_common.h: a stream hand-off signal carried in this kernel's entry)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int L = blockIdx.x;
   if (L < q.n0) gemm16_body<1, 1, KS>(q.a0, L % q.gx0, L / q.gx0, lds);
@@ -925,7 +926,8 @@ __device__ __forceinline__ void vox64_body(const VxArgs& a, const int wg_raw, co
 }
 
 template <int C, int TD, int DIL, int NW>
-__global__ __launch_bounds__(64 * NW, VOX_LB) void conv_vox64_kernel(VxArgs a) {
+__global__ __launch_bounds__(64 * NW, VOX_LB) void conv_vox64_kernel(VxArgs a, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   extern __shared__ __attribute__((aligned(16))) float4 vlds[];
   vox64_body<C, TD, DIL, NW>(a, blockIdx.x, gridDim.x, vlds);
@@ -1112,7 +1114,8 @@ __device__ __forceinline__ void vox_s2_body(const Vs2Args& a, const int wg_raw, 
 }
 
 template <int C, int TD, int DIL>
-__global__ __launch_bounds__(64, 2) void conv_vox_s2_kernel(Vs2Args a) {
+__global__ __launch_bounds__(64, 2) void conv_vox_s2_kernel(Vs2Args a, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   extern __shared__ __attribute__((aligned(16))) float4 vlds[];
   vox_s2_body<C, TD, DIL>(a, blockIdx.x, gridDim.x, vlds);
@@ -1139,7 +1142,8 @@ static Vs2Plan vs2_plan(const n3d_conv_geom* g, bool data_grad) {
 
 template <int C, int TD, int DIL>
 static void launch_vs2_t(Vs2Args& a, const Vs2Plan& p, int B, hipStream_t s) {
-  hipLaunchKernelGGL((conv_vox_s2_kernel<C, TD, DIL>), dim3(p.tiles * B), dim3(64), p.lds, s, a);
+  const EntrySignal es = entry_take(s);
+  N3D_LAUNCH((conv_vox_s2_kernel<C, TD, DIL>), dim3(p.tiles * B), dim3(64), p.lds, s, a, es);
 }
 
 static void launch_vs2(Vs2Args& a, const Vs2Plan& p, int B, hipStream_t s) {
@@ -1174,7 +1178,8 @@ __host__ __device__ constexpr int vup_p(int dil, int s, int i) { return dil == 2
 __host__ __device__ constexpr int vup_k(int dil, int s, int i) { return dil == 2 ? 1 - s : (s == 0 ? 1 + i : 0); }
 
 template <int C, int DIL>
-__global__ __launch_bounds__(64, 2) void conv_vox_up_kernel(VupArgs a) {
+__global__ __launch_bounds__(64, 2) void conv_vox_up_kernel(VupArgs a, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   constexpr int Q = C / 4;
   constexpr int LD = 3, LH = 6, LW = 18;
@@ -1389,10 +1394,11 @@ static int launch_vox_t(VxArgs& a, const VxPlan& p, int B, hipStream_t s) {
   a.fT = FastDiv((uint32_t)p.tiles); a.fTw = FastDiv((uint32_t)(a.W / 16)); a.fTh = FastDiv((uint32_t)(a.H / (4 * p.nw)));
   a.zero_page = zero_page_ptr();
   if (!a.zero_page) return 0;
+  const EntrySignal es = entry_take(s);
   if constexpr (C == 4 && TD == 4) {
-    if (p.nw == 2) { hipLaunchKernelGGL((conv_vox64_kernel<C, TD, DIL, 2>), dim3(p.tiles * B), dim3(128), p.lds, s, a); return 1; }
+    if (p.nw == 2) { N3D_LAUNCH((conv_vox64_kernel<C, TD, DIL, 2>), dim3(p.tiles * B), dim3(128), p.lds, s, a, es); return 1; }
   }
-  hipLaunchKernelGGL((conv_vox64_kernel<C, TD, DIL, 1>), dim3(p.tiles * B), dim3(64), p.lds, s, a);
+  N3D_LAUNCH((conv_vox64_kernel<C, TD, DIL, 1>), dim3(p.tiles * B), dim3(64), p.lds, s, a, es);
   return 1;
 }
 
@@ -1501,7 +1507,7 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
     float* wq = (float*)cc.ws;
     const bool s2 = kind[k] >= VOXK_S2_D1;
     if (i < n && !(cc.flags & N3D_PREPACKED))
-      hipLaunchKernelGGL(pack_vox_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, cc.w, wq, C, (!s2 && cc.data_grad) ? 1 : 0);
+      N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, cc.w, wq, C, (!s2 && cc.data_grad) ? 1 : 0);
     VxArgs& x = q.x[i];
     x.src = cc.src; x.sld = cc.sld; x.dst = cc.dst; x.dld = cc.dld; x.wq = wq; x.bias = cc.bias; x.D = g->Di; x.H = g->Hi; x.W = g->Wi;
     x.flags = cc.flags; x.stats = cc.stats; x.rows_per_sample = tiles[k]; x.tiles = tiles[k]; x.zero_page = zp;
@@ -1515,8 +1521,8 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
     if (i < n) at += tiles[k] * g->B;
   }
   q.start[4] = at;
-  if (C == 4) hipLaunchKernelGGL(conv_vox_multi_kernel<4>, dim3((unsigned)at), dim3(64), lds, s, q);
-  else hipLaunchKernelGGL(conv_vox_multi_kernel<8>, dim3((unsigned)at), dim3(64), lds, s, q);
+  if (C == 4) N3D_LAUNCH(conv_vox_multi_kernel<4>, dim3((unsigned)at), dim3(64), lds, s, q);
+  else N3D_LAUNCH(conv_vox_multi_kernel<8>, dim3((unsigned)at), dim3(64), lds, s, q);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(vox multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -2109,22 +2115,22 @@ int vox_wgrad_s2_try(const n3d_conv_geom* g, const float* x, int64_t xld, const 
   if (!a.zero_page) return 0;
   dim3 grid(tiles, g->B, tco);
   if (mixed) {
-    if (g->dil == 1) hipLaunchKernelGGL((vox_wgrad_s2_kernel<4, 1, float, bf16_t>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((vox_wgrad_s2_kernel<4, 2, float, bf16_t>), grid, dim3(256), lds, s, a);
+    if (g->dil == 1) N3D_LAUNCH((vox_wgrad_s2_kernel<4, 1, float, bf16_t>), grid, dim3(256), lds, s, a);
+    else N3D_LAUNCH((vox_wgrad_s2_kernel<4, 2, float, bf16_t>), grid, dim3(256), lds, s, a);
   } else if (b16) {
     if (g->Ci == 4) {
-      if (g->dil == 1) hipLaunchKernelGGL((vox_wgrad_s2_kernel<4, 1, bf16_t>), grid, dim3(256), lds, s, a);
-      else hipLaunchKernelGGL((vox_wgrad_s2_kernel<4, 2, bf16_t>), grid, dim3(256), lds, s, a);
+      if (g->dil == 1) N3D_LAUNCH((vox_wgrad_s2_kernel<4, 1, bf16_t>), grid, dim3(256), lds, s, a);
+      else N3D_LAUNCH((vox_wgrad_s2_kernel<4, 2, bf16_t>), grid, dim3(256), lds, s, a);
     } else {
-      if (g->dil == 1) hipLaunchKernelGGL((vox_wgrad_s2_kernel<8, 1, bf16_t>), grid, dim3(256), lds, s, a);
-      else hipLaunchKernelGGL((vox_wgrad_s2_kernel<8, 2, bf16_t>), grid, dim3(256), lds, s, a);
+      if (g->dil == 1) N3D_LAUNCH((vox_wgrad_s2_kernel<8, 1, bf16_t>), grid, dim3(256), lds, s, a);
+      else N3D_LAUNCH((vox_wgrad_s2_kernel<8, 2, bf16_t>), grid, dim3(256), lds, s, a);
     }
   } else if (g->Ci == 4) {
-    if (g->dil == 1) hipLaunchKernelGGL((vox_wgrad_s2_kernel<4, 1>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((vox_wgrad_s2_kernel<4, 2>), grid, dim3(256), lds, s, a);
+    if (g->dil == 1) N3D_LAUNCH((vox_wgrad_s2_kernel<4, 1>), grid, dim3(256), lds, s, a);
+    else N3D_LAUNCH((vox_wgrad_s2_kernel<4, 2>), grid, dim3(256), lds, s, a);
   } else {
-    if (g->dil == 1) hipLaunchKernelGGL((vox_wgrad_s2_kernel<8, 1>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((vox_wgrad_s2_kernel<8, 2>), grid, dim3(256), lds, s, a);
+    if (g->dil == 1) N3D_LAUNCH((vox_wgrad_s2_kernel<8, 1>), grid, dim3(256), lds, s, a);
+    else N3D_LAUNCH((vox_wgrad_s2_kernel<8, 2>), grid, dim3(256), lds, s, a);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(vox_wgrad_s2) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
@@ -2191,10 +2197,10 @@ int vox_wgrad_try(const n3d_conv_geom* g, const float* x, int64_t xld, const flo
   const int ns = vw_stages(p.dchunk / 4, vw_stage_lds(slots, p.dil));
   const size_t lds = vw_plan_lds(slots, p.dil, ns);
 #define N3D_VW_T(C_, D_, T_) do { \
-    if (ns == 4) hipLaunchKernelGGL((vox_wgrad_kernel<C_, D_, T_, 4>), grid, dim3(256), lds, s, a); \
-    else if (ns == 2) hipLaunchKernelGGL((vox_wgrad_kernel<C_, D_, T_, 2>), grid, dim3(256), lds, s, a); \
-    else if (ns == 1) hipLaunchKernelGGL((vox_wgrad_kernel<C_, D_, T_, 1>), grid, dim3(256), lds, s, a); \
-    else hipLaunchKernelGGL((vox_wgrad_kernel<C_, D_, T_, 0>), grid, dim3(256), lds, s, a); } while (0)
+    if (ns == 4) N3D_LAUNCH((vox_wgrad_kernel<C_, D_, T_, 4>), grid, dim3(256), lds, s, a); \
+    else if (ns == 2) N3D_LAUNCH((vox_wgrad_kernel<C_, D_, T_, 2>), grid, dim3(256), lds, s, a); \
+    else if (ns == 1) N3D_LAUNCH((vox_wgrad_kernel<C_, D_, T_, 1>), grid, dim3(256), lds, s, a); \
+    else N3D_LAUNCH((vox_wgrad_kernel<C_, D_, T_, 0>), grid, dim3(256), lds, s, a); } while (0)
 #define N3D_VW(T_) do { \
     if (p.C == 4) { if (p.dil == 1) N3D_VW_T(4, 1, T_); else N3D_VW_T(4, 2, T_); } \
     else { if (p.dil == 1) N3D_VW_T(8, 1, T_); else N3D_VW_T(8, 2, T_); } } while (0)
@@ -2531,8 +2537,8 @@ static bool launch_tile32(const MfArgs& a, int tiles, hipStream_t s) {
 #undef N3D_T32_ATTR
     attr_set = true;
   }
-#define N3D_T32_LAUNCH(DIL_, DG_) do { if (bf) hipLaunchKernelGGL((conv_tile32_kernel<DIL_, DG_, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); \
-    else hipLaunchKernelGGL((conv_tile32_kernel<DIL_, DG_, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); } while (0)
+#define N3D_T32_LAUNCH(DIL_, DG_) do { if (bf) N3D_LAUNCH((conv_tile32_kernel<DIL_, DG_, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); \
+    else N3D_LAUNCH((conv_tile32_kernel<DIL_, DG_, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); } while (0)
   if (d == 1) { if (a.dt > 0) N3D_T32_LAUNCH(1, false); else N3D_T32_LAUNCH(1, true); }
   else { if (a.dt > 0) N3D_T32_LAUNCH(2, false); else N3D_T32_LAUNCH(2, true); }
 #undef N3D_T32_LAUNCH
@@ -2704,8 +2710,8 @@ static bool launch_tile16(const MfArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(tiles * a.B));
   const FastDiv fT((uint32_t)tiles), fTw((uint32_t)(a.Wd / 16)), fTh((uint32_t)(a.Hd / 4));
   const bool bf = a.flags & N3D_MM_BF16;
-#define N3D_T16_LAUNCH(DIL_, DG_) do { if (bf) hipLaunchKernelGGL((conv_tile16_kernel<DIL_, DG_, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); \
-    else hipLaunchKernelGGL((conv_tile16_kernel<DIL_, DG_, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); } while (0)
+#define N3D_T16_LAUNCH(DIL_, DG_) do { if (bf) N3D_LAUNCH((conv_tile16_kernel<DIL_, DG_, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); \
+    else N3D_LAUNCH((conv_tile16_kernel<DIL_, DG_, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); } while (0)
   if (d == 1) {
     if (a.dt > 0) N3D_T16_LAUNCH(1, false); else N3D_T16_LAUNCH(1, true);
   } else {
@@ -2772,11 +2778,11 @@ static void launch_g16(const MfArgs& a, int64_t M, hipStream_t s) {
   constexpr int RPB = 16 * MT * (KS == 1 ? 4 : 1);
   dim3 grid((unsigned)cdiv(M, RPB), (unsigned)(a.Cd / (16 * NT)));
   size_t shm = (KS > 1 ? (size_t)(KS - 1) * MT * NT * 256 * sizeof(float) : 0) + (size_t)16 * NT * 16 * 2 * sizeof(double);
-  hipLaunchKernelGGL((conv_gemm16_kernel<MT, NT, KS>), grid, dim3(KS == 16 ? 1024 : 256), shm, s, a);
+  N3D_LAUNCH((conv_gemm16_kernel<MT, NT, KS>), grid, dim3(KS == 16 ? 1024 : 256), shm, s, a);
 }
 
 void mfma_pack16(const float* w, float* wp, int Co, int Ci, int taps, int data_grad, hipStream_t s) {
-  hipLaunchKernelGGL(pack16_kernel, dim3((unsigned)cdiv((int64_t)taps * Co * Ci, 256)), dim3(256), 0, s, w, wp, Co, Ci, taps, data_grad);
+  N3D_LAUNCH(pack16_kernel, dim3((unsigned)cdiv((int64_t)taps * Co * Ci, 256)), dim3(256), 0, s, w, wp, Co, Ci, taps, data_grad);
 }
 
 int g16_prepare(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
@@ -2798,7 +2804,7 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
       if (!ws || ws_bytes < need) { set_error("conv(vox_s2): workspace too small"); return N3D_ERR_WORKSPACE; }
       float* wq = (float*)ws;
       if (!(flags & N3D_PREPACKED))
-        hipLaunchKernelGGL(pack_vox_kernel, dim3((unsigned)cdiv(27 * v2.C * v2.C, 256)), dim3(256), 0, s, w, wq, v2.C, 0);
+        N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * v2.C * v2.C, 256)), dim3(256), 0, s, w, wq, v2.C, 0);
       Vs2Args a;
       a.src = src; a.sld = sld; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.dst = dst; a.dld = dld; a.oD = g->Do; a.oH = g->Ho; a.oW = g->Wo;
       a.wq = wq; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v2.tiles; a.tiles = v2.tiles; a.zero_page = zero_page_ptr();
@@ -2819,16 +2825,17 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
       if (!ws || ws_bytes < need) { set_error("conv(vox_up): workspace too small"); return N3D_ERR_WORKSPACE; }
       float* wq = (float*)ws;
       if (!(flags & N3D_PREPACKED))
-        hipLaunchKernelGGL(pack_vox_kernel, dim3((unsigned)cdiv(27 * v3.C * v3.C, 256)), dim3(256), 0, s, w, wq, v3.C, 2);
+        N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * v3.C * v3.C, 256)), dim3(256), 0, s, w, wq, v3.C, 2);
       VupArgs a;
       a.src = src; a.sld = sld; a.D = g->Do; a.H = g->Ho; a.W = g->Wo; a.dst = dst; a.dld = dld;
       a.wq = wq; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v3.tiles; a.tiles = v3.tiles; a.zero_page = zero_page_ptr();
       a.fT = FastDiv((uint32_t)v3.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
       if (!a.zero_page) { set_error("conv(vox_up): zero page symbol unavailable"); return N3D_ERR_HIP; }
-      if (v3.C == 4) { if (v3.dil == 1) hipLaunchKernelGGL((conv_vox_up_kernel<4, 1>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a);
-                       else hipLaunchKernelGGL((conv_vox_up_kernel<4, 2>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a); }
-      else { if (v3.dil == 1) hipLaunchKernelGGL((conv_vox_up_kernel<8, 1>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a);
-             else hipLaunchKernelGGL((conv_vox_up_kernel<8, 2>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a); }
+      const EntrySignal es = entry_take(s);
+      if (v3.C == 4) { if (v3.dil == 1) N3D_LAUNCH((conv_vox_up_kernel<4, 1>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es);
+                       else N3D_LAUNCH((conv_vox_up_kernel<4, 2>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es); }
+      else { if (v3.dil == 1) N3D_LAUNCH((conv_vox_up_kernel<8, 1>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es);
+             else N3D_LAUNCH((conv_vox_up_kernel<8, 2>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es); }
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) { set_error("conv(vox_up) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
       return 1;
@@ -2843,7 +2850,7 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
       if (!ws || ws_bytes < need) { set_error("conv(vox64): workspace too small"); return N3D_ERR_WORKSPACE; }
       float* wq = (float*)ws;
       if (!(flags & N3D_PREPACKED))
-        hipLaunchKernelGGL(pack_vox_kernel, dim3((unsigned)cdiv(27 * v.C * v.C, 256)), dim3(256), 0, s, w, wq, v.C, data_grad ? 1 : 0);
+        N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * v.C * v.C, 256)), dim3(256), 0, s, w, wq, v.C, data_grad ? 1 : 0);
       VxArgs a;
       a.src = src; a.sld = sld; a.dst = dst; a.dld = dld; a.wq = wq; a.bias = bias; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.flags = flags;
       a.stats = stats; a.rows_per_sample = v.tiles * v.nw;
@@ -2875,10 +2882,10 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
         const dim3 grid((unsigned)(tiles * g->B));
         const FastDiv fT((uint32_t)tiles), fTw((uint32_t)(g->Wo / 16)), fTh((uint32_t)(g->Ho / 4));      // (source grid = the o side)
         const bool bf = a.flags & N3D_MM_BF16;
-        if (d == 1) { if (bf) hipLaunchKernelGGL((conv_tile16_up_kernel<1, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh);
-                      else hipLaunchKernelGGL((conv_tile16_up_kernel<1, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); }
-        else { if (bf) hipLaunchKernelGGL((conv_tile16_up_kernel<2, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh);
-               else hipLaunchKernelGGL((conv_tile16_up_kernel<2, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); }
+        if (d == 1) { if (bf) N3D_LAUNCH((conv_tile16_up_kernel<1, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh);
+                      else N3D_LAUNCH((conv_tile16_up_kernel<1, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); }
+        else { if (bf) N3D_LAUNCH((conv_tile16_up_kernel<2, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh);
+               else N3D_LAUNCH((conv_tile16_up_kernel<2, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { set_error("conv(tile16_up) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
         return 1;
@@ -2951,7 +2958,7 @@ int g16_prepare(const n3d_conv_geom* g, bool data_grad, const float* src, int64_
   a.wp = wp;
   const int total = taps * a.Cs * a.Cd;
   if (!(flags & N3D_PREPACKED))
-    hipLaunchKernelGGL(pack16_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, g->Co, g->Ci, taps, data_grad ? 1 : 0);
+    N3D_LAUNCH(pack16_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, g->Co, g->Ci, taps, data_grad ? 1 : 0);
   *out = a; *plan = p;
   return 1;
 }
@@ -2984,8 +2991,9 @@ int mfma_conv_pair_try(const n3d_conv_geom* g0, bool dg0, const float* src0, int
   q.n0 = q.gx0 * (q.a0.Cd / 16);
   const int n1 = q.gx1 * (q.a1.Cd / 16);
   const size_t shm = (size_t)(p0.ksplit - 1) * 256 * sizeof(float) + (size_t)16 * 16 * 2 * sizeof(double);
-  if (p0.ksplit == 16) hipLaunchKernelGGL(conv_gemm16_pair_kernel<16>, dim3((unsigned)(q.n0 + n1)), dim3(1024), shm, s, q);
-  else hipLaunchKernelGGL(conv_gemm16_pair_kernel<4>, dim3((unsigned)(q.n0 + n1)), dim3(256), shm, s, q);
+  const EntrySignal es = entry_take(s);
+  if (p0.ksplit == 16) N3D_LAUNCH(conv_gemm16_pair_kernel<16>, dim3((unsigned)(q.n0 + n1)), dim3(1024), shm, s, q, es);
+  else N3D_LAUNCH(conv_gemm16_pair_kernel<4>, dim3((unsigned)(q.n0 + n1)), dim3(256), shm, s, q, es);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(pair) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -3023,8 +3031,8 @@ int mfma_conv_multi_try(int n, const n3d_conv_geom* const* g, const bool* dg, co
   }
   q.start[4] = total;
   const size_t shm = (size_t)(ksplit - 1) * 256 * sizeof(float) + (size_t)16 * 16 * 2 * sizeof(double);
-  if (ksplit == 16) hipLaunchKernelGGL(conv_gemm16_multi_kernel<16>, dim3((unsigned)total), dim3(1024), shm, s, q);
-  else hipLaunchKernelGGL(conv_gemm16_multi_kernel<4>, dim3((unsigned)total), dim3(256), shm, s, q);
+  if (ksplit == 16) N3D_LAUNCH(conv_gemm16_multi_kernel<16>, dim3((unsigned)total), dim3(1024), shm, s, q);
+  else N3D_LAUNCH(conv_gemm16_multi_kernel<4>, dim3((unsigned)total), dim3(256), shm, s, q);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -3060,7 +3068,7 @@ int mfma_wgrad_try(const n3d_conv_geom* g, const float* x, int64_t xld, const fl
   a.fTco = FastDiv((uint32_t)a.tco); a.fTci = FastDiv((uint32_t)a.tci);
   *nchunks_out = (int)nch; *ntiles_out = ntiles;
   if (prepared) { *prepared = a; return 1; }
-  hipLaunchKernelGGL(conv_wgrad16_kernel, dim3(ntiles, (unsigned)nch), dim3(256), 0, s, a);
+  N3D_LAUNCH(conv_wgrad16_kernel, dim3(ntiles, (unsigned)nch), dim3(256), 0, s, a);
   return 1;
 }
 
@@ -3248,8 +3256,8 @@ int wgrad_tile16_try(const n3d_conv_geom* g, const float* x, int64_t xld, const 
   const size_t shm = (size_t)((nv * 4 + 255) / 256) * 256 * 16;
   const dim3 grid((unsigned)chunks, (unsigned)(tci * tco));
   const bool bf = flags & N3D_MM_BF16;
-#define N3D_WT16_LAUNCH(DIL_, TW_) do { if (bf) hipLaunchKernelGGL((wgrad_tile16_kernel<DIL_, TW_, true>), grid, dim3(256), shm, s, a); \
-    else hipLaunchKernelGGL((wgrad_tile16_kernel<DIL_, TW_, false>), grid, dim3(256), shm, s, a); } while (0)
+#define N3D_WT16_LAUNCH(DIL_, TW_) do { if (bf) N3D_LAUNCH((wgrad_tile16_kernel<DIL_, TW_, true>), grid, dim3(256), shm, s, a); \
+    else N3D_LAUNCH((wgrad_tile16_kernel<DIL_, TW_, false>), grid, dim3(256), shm, s, a); } while (0)
   if (tw == 16) {
     if (d == 1) N3D_WT16_LAUNCH(1, 16); else N3D_WT16_LAUNCH(2, 16);
   } else {
@@ -3300,8 +3308,8 @@ int mfma_bwd_dual_try(const n3d_conv_geom* g, bool transposed, const float* dy, 
   const size_t shm_b = (size_t)units * (3 * 64 * 16 + 4 * 16 * 4);
   const size_t shm = shm_a > shm_b ? shm_a : shm_b;
   const dim3 grid((unsigned)(q.nA + cdiv(q.nB, units)));
-  if (p.ksplit == 16) hipLaunchKernelGGL(conv_bwd16_dual_kernel<16>, grid, dim3(1024), shm, s, q);
-  else hipLaunchKernelGGL(conv_bwd16_dual_kernel<4>, grid, dim3(256), shm, s, q);
+  if (p.ksplit == 16) N3D_LAUNCH(conv_bwd16_dual_kernel<16>, grid, dim3(1024), shm, s, q);
+  else N3D_LAUNCH(conv_bwd16_dual_kernel<4>, grid, dim3(256), shm, s, q);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(bwd dual) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -3344,8 +3352,8 @@ int mfma_bwd_quad_try(BwdOne* c0, BwdOne* c1, hipStream_t s) {
   const size_t shm_a = (size_t)(k0 - 1) * 256 * sizeof(float) + (size_t)16 * 16 * 2 * sizeof(double);
   const size_t shm_b = (size_t)units * (3 * 64 * 16 + 4 * 16 * 4);
   const size_t shm = shm_a > shm_b ? shm_a : shm_b;
-  if (k0 == 16) hipLaunchKernelGGL(conv_bwd16_quad_kernel<16>, dim3((unsigned)(z.n0 + n1)), dim3(1024), shm, s, z);
-  else hipLaunchKernelGGL(conv_bwd16_quad_kernel<4>, dim3((unsigned)(z.n0 + n1)), dim3(256), shm, s, z);
+  if (k0 == 16) N3D_LAUNCH(conv_bwd16_quad_kernel<16>, dim3((unsigned)(z.n0 + n1)), dim3(1024), shm, s, z);
+  else N3D_LAUNCH(conv_bwd16_quad_kernel<4>, dim3((unsigned)(z.n0 + n1)), dim3(256), shm, s, z);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(bwd quad) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;

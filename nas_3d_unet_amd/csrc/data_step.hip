@@ -104,10 +104,10 @@ extern "C" int n3d_patch_batch(const float* vol, int Cv, const uint8_t* truth, i
   const int inclusive = flags & N3D_PATCH_INCLUSIVE;
   const dim3 grid((unsigned)cdiv(P3, 256), B);
   if (flags & N3D_PATCH_T_U8)
-    hipLaunchKernelGGL(patch_batch_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cv, truth, X, Y, Z, pd, P, inclusive, x_out, xld,
+    N3D_LAUNCH(patch_batch_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cv, truth, X, Y, Z, pd, P, inclusive, x_out, xld,
                        (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   else
-    hipLaunchKernelGGL(patch_batch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cv, truth, X, Y, Z, pd, P, inclusive, x_out, xld,
+    N3D_LAUNCH(patch_batch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cv, truth, X, Y, Z, pd, P, inclusive, x_out, xld,
                        (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -135,10 +135,10 @@ extern "C" int n3d_patch_gather(const n3d_patch_volume* vols, int nvol, int Cv, 
   const int inclusive = flags & N3D_PATCH_INCLUSIVE;
   const dim3 grid((unsigned)cdiv(P3, 256), B);
   if (flags & N3D_PATCH_T_U8)
-    hipLaunchKernelGGL(patch_gather_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
+    N3D_LAUNCH(patch_gather_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
                        (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   else
-    hipLaunchKernelGGL(patch_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
+    N3D_LAUNCH(patch_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
                        (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   N3D_LAUNCH_CHECK();
   return N3D_OK;

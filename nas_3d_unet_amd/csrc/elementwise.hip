@@ -251,7 +251,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const T* __restrict__ r
 template <bool RELU, typename T = float>
 __global__ __launch_bounds__(256) void affine_bwd_reduce_kernel(const T* __restrict__ dout, int64_t dld, const T* __restrict__ raw,
                                                                 int64_t rld, const float* __restrict__ a, const float* __restrict__ bb,
-                                                                int64_t N, int C, EwMap m, double* __restrict__ sums) {
+                                                                int64_t N, int C, EwMap m, double* __restrict__ sums, EntrySignal es) {
+  entry_signal(es);      // (n3d_common.h: a stream hand-off signal carried in this kernel's entry)
   N3D_CHAIN_PRIO();
   __shared__ double lds[4 * 64 * 12];
   const int b = blockIdx.y;
@@ -1161,7 +1162,8 @@ struct BwdRedTerm { const float* raw; int64_t rld; const float* a; const float* 
 // TWO: the second op has its own output gradient (independent outputs); otherwise both share dout (a node)
 template <bool TWO, typename T = float>
 __global__ __launch_bounds__(256) void affine_bwd_reduce2_kernel(const T* __restrict__ dout, int64_t dld, const T* __restrict__ dout1,
-                                                                 int64_t dld1, BwdRedTerm t0, BwdRedTerm t1, int64_t N, int C, EwMap m) {
+                                                                 int64_t dld1, BwdRedTerm t0, BwdRedTerm t1, int64_t N, int C, EwMap m, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   __shared__ double lds[4 * 64 * 12];
   const int b = blockIdx.y;
@@ -1368,7 +1370,8 @@ __global__ __launch_bounds__(256) void affine_bwd_apply_gn2_kernel(const T* __re
 template <int QPT, bool TWO, bool SPLIT, int NT, typename T = float>
 __global__ __launch_bounds__(1024) void gn_bwd_small2_kernel(const T* __restrict__ dout, int64_t dld, const T* __restrict__ dout1,
                                                             int64_t dld1, GnBwdTerm t0, GnBwdTerm t1, int B, int N, int C, int G, double count,
-                                                            double* __restrict__ scratch, unsigned* __restrict__ tickets) {
+                                                            double* __restrict__ scratch, unsigned* __restrict__ tickets, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   constexpr int MB = SPLIT ? 1 : 4;
   __shared__ float red[QPT * 16][2][32];   // [slot = i*16 + wave][term][(S1 | S2) x 16 channels]
@@ -2365,7 +2368,7 @@ int n3d_channel_stats_t(const void* x, int64_t ld, int dtype, int B, int64_t N, 
   EwMap m = ew_map(N, C);
   with_act_type(dtype == N3D_BF16, [&](auto* tag) {
     using T = N3D_T(tag);
-    hipLaunchKernelGGL(channel_stats_kernel<T>, dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)x, ld, N, C, m, stats);
+    N3D_LAUNCH(channel_stats_kernel<T>, dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)x, ld, N, C, m, stats);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2384,7 +2387,7 @@ int n3d_channel_statsN(const float* const* xs, const int64_t* lds, double* const
     js.x[i] = xs[k]; js.ld[i] = lds[k]; js.stats[i] = stats[k];
   }
   EwMap m = ew_map(N, C);
-  hipLaunchKernelGGL(channel_statsN_kernel, dim3(m.rows, B, n), dim3(256), 0, (hipStream_t)stream, js, N, C, m);
+  N3D_LAUNCH(channel_statsN_kernel, dim3(m.rows, B, n), dim3(256), 0, (hipStream_t)stream, js, N, C, m);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2395,7 +2398,7 @@ int n3d_gn_coeffs(const double* stats, int rows, const float* gamma, const float
   G = gn_groups(G);
   N3D_CHECK_ARG(stats && gamma && beta && a && b && C <= 64 && G >= 1 && C % G == 0 && rows >= 1, "gn_coeffs: bad args");
   const GnCoefArgs q{stats, rows, gamma, beta, a, b, mean_rstd, sumraw};
-  hipLaunchKernelGGL(gn_coeffs_kernel, dim3(B, 1), dim3(256), 0, (hipStream_t)stream, q, q, C, G, gn_cnt_, eps);
+  N3D_LAUNCH(gn_coeffs_kernel, dim3(B, 1), dim3(256), 0, (hipStream_t)stream, q, q, C, G, gn_cnt_, eps);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2413,10 +2416,10 @@ int n3d_affine_act(const float* raw, int64_t rld, const float* a, const float* b
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
     const T* r = (const T*)raw; T* o = (T*)out;
-    if (relu && acc) hipLaunchKernelGGL((affine_act_kernel<true, true, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
-    else if (relu) hipLaunchKernelGGL((affine_act_kernel<true, false, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
-    else if (acc) hipLaunchKernelGGL((affine_act_kernel<false, true, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
-    else hipLaunchKernelGGL((affine_act_kernel<false, false, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
+    if (relu && acc) N3D_LAUNCH((affine_act_kernel<true, true, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
+    else if (relu) N3D_LAUNCH((affine_act_kernel<true, false, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
+    else if (acc) N3D_LAUNCH((affine_act_kernel<false, true, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
+    else N3D_LAUNCH((affine_act_kernel<false, false, T>), grid, blk, 0, s, r, rld, a, b, wptr, o, old_, N, C, m);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2430,10 +2433,11 @@ int n3d_affine_act_bwd_reduce(const float* dout, int64_t dld, const float* raw, 
   if (int e = check_vec(raw, rld, C, "bwd_reduce(raw)", bf)) return e;
   EwMap m = ew_map(N, C);
   dim3 grid(m.rows, B), blk(256);
+  const EntrySignal es = entry_take((hipStream_t)stream);
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-    if (flags & N3D_RELU) hipLaunchKernelGGL((affine_bwd_reduce_kernel<true, T>), grid, blk, 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)raw, rld, a, b, N, C, m, sums);
-    else hipLaunchKernelGGL((affine_bwd_reduce_kernel<false, T>), grid, blk, 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)raw, rld, a, b, N, C, m, sums);
+    if (flags & N3D_RELU) N3D_LAUNCH((affine_bwd_reduce_kernel<true, T>), grid, blk, 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)raw, rld, a, b, N, C, m, sums, es);
+    else N3D_LAUNCH((affine_bwd_reduce_kernel<false, T>), grid, blk, 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)raw, rld, a, b, N, C, m, sums, es);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2447,8 +2451,8 @@ int n3d_gn_bwd_coeffs(const double* sums, int rows, const float* gamma, const fl
   N3D_CHECK_ARG(sums && gamma && mean_rstd && A && Bc && Cc && C <= 64 && C % G == 0, "gn_bwd_coeffs: bad args");
   N3D_CHECK_ARG(!dbias_conv || sumraw, "gn_bwd_coeffs: dbias_conv needs the forward per-channel sums");
   const GnBwdCoefArgs q{sums, rows, gamma, mean_rstd, wptr, dgamma, dbeta, dalpha, A, Bc, Cc, sumraw, dbias_conv};
-  if (B <= 2) hipLaunchKernelGGL(gn_bwd_coeffs_kernel<2>, dim3(1), dim3(512), 0, (hipStream_t)stream, q, q, B, C, G, gn_cnt_);
-  else hipLaunchKernelGGL(gn_bwd_coeffs_kernel<GNB_BP>, dim3(1), dim3(256 * GNB_BP), 0, (hipStream_t)stream, q, q, B, C, G, gn_cnt_);
+  if (B <= 2) N3D_LAUNCH(gn_bwd_coeffs_kernel<2>, dim3(1), dim3(512), 0, (hipStream_t)stream, q, q, B, C, G, gn_cnt_);
+  else N3D_LAUNCH(gn_bwd_coeffs_kernel<GNB_BP>, dim3(1), dim3(256 * GNB_BP), 0, (hipStream_t)stream, q, q, B, C, G, gn_cnt_);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2478,8 +2482,8 @@ int n3d_affine_act_gn2(const n3d_gn_fwd_term* t0, const n3d_gn_fwd_term* t1, int
   hipStream_t s = (hipStream_t)stream;
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-    if (flags & N3D_ACCUMULATE) hipLaunchKernelGGL((affine_act_gn2_kernel<true, false, T>), grid, blk, 0, s, k[0], k[1], G, gn_cnt_, eps, (T*)out, old_, (T*)out1, old1, N, C, m);
-    else hipLaunchKernelGGL((affine_act_gn2_kernel<false, false, T>), grid, blk, 0, s, k[0], k[1], G, gn_cnt_, eps, (T*)out, old_, (T*)out1, old1, N, C, m);
+    if (flags & N3D_ACCUMULATE) N3D_LAUNCH((affine_act_gn2_kernel<true, false, T>), grid, blk, 0, s, k[0], k[1], G, gn_cnt_, eps, (T*)out, old_, (T*)out1, old1, N, C, m);
+    else N3D_LAUNCH((affine_act_gn2_kernel<false, false, T>), grid, blk, 0, s, k[0], k[1], G, gn_cnt_, eps, (T*)out, old_, (T*)out1, old1, N, C, m);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2501,10 +2505,11 @@ int n3d_affine_act_bwd_reduce2(const float* dout, int64_t dld, const float* dout
     k[i] = BwdRedTerm{t->raw, t->rld, t->a, t->b, t->sums, t->relu};
   }
   if (dout1) { if (int e = check_vec(dout1, dld1, C, "bwd_reduce2(dout1)", bf)) return e; }
+  const EntrySignal es = entry_take((hipStream_t)stream);
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-    if (dout1) hipLaunchKernelGGL((affine_bwd_reduce2_kernel<true, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], N, C, m);
-    else hipLaunchKernelGGL((affine_bwd_reduce2_kernel<false, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], N, C, m);
+    if (dout1) N3D_LAUNCH((affine_bwd_reduce2_kernel<true, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], N, C, m, es);
+    else N3D_LAUNCH((affine_bwd_reduce2_kernel<false, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], N, C, m, es);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2536,8 +2541,8 @@ int n3d_affine_act_bwd_apply_gn2(const float* dout, int64_t dld, const float* do
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
     // (grid.x = rows + 1: the last workgroup column forms the parameter gradients)
-    if (dout1) hipLaunchKernelGGL((affine_bwd_apply_gn2_kernel<false, true, T>), dim3(m.rows + 1, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, G, gn_cnt_, N, C, m);
-    else hipLaunchKernelGGL((affine_bwd_apply_gn2_kernel<false, false, T>), dim3(m.rows + 1, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, G, gn_cnt_, N, C, m);
+    if (dout1) N3D_LAUNCH((affine_bwd_apply_gn2_kernel<false, true, T>), dim3(m.rows + 1, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, G, gn_cnt_, N, C, m);
+    else N3D_LAUNCH((affine_bwd_apply_gn2_kernel<false, false, T>), dim3(m.rows + 1, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, G, gn_cnt_, N, C, m);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2596,10 +2601,11 @@ static int bwd_small_launch(const float* dout, int64_t dld, const float* dout1, 
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(G, mode == 2 ? B : 1);
   double* sc = (double*)scratch;
+  const EntrySignal es = entry_take(s);
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
     const T* d0 = (const T*)dout; const T* d1 = (const T*)dout1;
-#define N3D_BS(Q, TW, SP, NT_) hipLaunchKernelGGL((gn_bwd_small2_kernel<Q, TW, SP, NT_, T>), grid, dim3(1024), 0, s, d0, dld, d1, dld1, k[0], k[1], B, (int)N, C, G, (double)N, sc, tickets)
+#define N3D_BS(Q, TW, SP, NT_) N3D_LAUNCH((gn_bwd_small2_kernel<Q, TW, SP, NT_, T>), grid, dim3(1024), 0, s, d0, dld, d1, dld1, k[0], k[1], B, (int)N, C, G, (double)N, sc, tickets, es)
 #define N3D_BS_Q(TW, SP, NT_) do { if (quads <= 1024) N3D_BS(1, TW, SP, NT_); else N3D_BS(2, TW, SP, NT_); } while (0)
     if (!t1) { if (mode == 2) N3D_BS_Q(false, true, 1); else N3D_BS_Q(false, false, 1); }
     else if (dout1) { if (mode == 2) N3D_BS_Q(true, true, 2); else N3D_BS_Q(true, false, 2); }
@@ -2637,7 +2643,7 @@ int n3d_gn_coeffs2(const n3d_gn_fwd_term* t0, const n3d_gn_fwd_term* t1, int B, 
     N3D_CHECK_ARG(t->stats && t->gamma && t->beta && t->a_out && t->b_out && t->rows >= 1, "gn_coeffs2: null term pointer");
     q[i] = GnCoefArgs{t->stats, t->rows, t->gamma, t->beta, t->a_out, t->b_out, t->mean_rstd_out, t->sumraw};
   }
-  hipLaunchKernelGGL(gn_coeffs_kernel, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, q[0], q[1], C, G, gn_cnt_, eps);
+  N3D_LAUNCH(gn_coeffs_kernel, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, q[0], q[1], C, G, gn_cnt_, eps);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2661,8 +2667,8 @@ int n3d_affine_act2(const n3d_gn_fwd_term* t0, const n3d_gn_fwd_term* t1, float*
   hipStream_t s = (hipStream_t)stream;
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-    if (flags & N3D_ACCUMULATE) hipLaunchKernelGGL((affine_act_gn2_kernel<true, true, T>), grid, blk, 0, s, k[0], k[1], 1, (double)N, 0.f, (T*)out, old_, (T*)out1, old1, N, C, m);
-    else hipLaunchKernelGGL((affine_act_gn2_kernel<false, true, T>), grid, blk, 0, s, k[0], k[1], 1, (double)N, 0.f, (T*)out, old_, (T*)out1, old1, N, C, m);
+    if (flags & N3D_ACCUMULATE) N3D_LAUNCH((affine_act_gn2_kernel<true, true, T>), grid, blk, 0, s, k[0], k[1], 1, (double)N, 0.f, (T*)out, old_, (T*)out1, old1, N, C, m);
+    else N3D_LAUNCH((affine_act_gn2_kernel<false, true, T>), grid, blk, 0, s, k[0], k[1], 1, (double)N, 0.f, (T*)out, old_, (T*)out1, old1, N, C, m);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2681,8 +2687,8 @@ int n3d_gn_bwd_coeffs2(const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int
     q[i] = GnBwdCoefArgs{t->sums, t->rows, t->gamma, t->mean_rstd, t->wptr, t->dgamma, t->dbeta, t->dalpha, t->cA, t->cB, t->cC, t->sumraw,
                          t->dbias_conv};
   }
-  if (B <= 2) hipLaunchKernelGGL(gn_bwd_coeffs_kernel<2>, dim3(2), dim3(512), 0, (hipStream_t)stream, q[0], q[1], B, C, G, gn_cnt_);
-  else hipLaunchKernelGGL(gn_bwd_coeffs_kernel<GNB_BP>, dim3(2), dim3(256 * GNB_BP), 0, (hipStream_t)stream, q[0], q[1], B, C, G, gn_cnt_);
+  if (B <= 2) N3D_LAUNCH(gn_bwd_coeffs_kernel<2>, dim3(2), dim3(512), 0, (hipStream_t)stream, q[0], q[1], B, C, G, gn_cnt_);
+  else N3D_LAUNCH(gn_bwd_coeffs_kernel<GNB_BP>, dim3(2), dim3(256 * GNB_BP), 0, (hipStream_t)stream, q[0], q[1], B, C, G, gn_cnt_);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2706,8 +2712,8 @@ int n3d_affine_act_bwd_apply2(const float* dout, int64_t dld, const float* dout1
   if (dout1) { if (int e = check_vec(dout1, dld1, C, "bwd_apply2(dout1)", bf)) return e; }
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-    if (dout1) hipLaunchKernelGGL((affine_bwd_apply_gn2_kernel<true, true, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, 1, (double)N, N, C, m);
-    else hipLaunchKernelGGL((affine_bwd_apply_gn2_kernel<true, false, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, 1, (double)N, N, C, m);
+    if (dout1) N3D_LAUNCH((affine_bwd_apply_gn2_kernel<true, true, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, 1, (double)N, N, C, m);
+    else N3D_LAUNCH((affine_bwd_apply_gn2_kernel<true, false, T>), dim3(m.rows, B), dim3(256), 0, (hipStream_t)stream, (const T*)dout, dld, (const T*)dout1, dld1, k[0], k[1], B, 1, (double)N, N, C, m);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2731,7 +2737,7 @@ int n3d_gn_coeffsN(const n3d_gn_fwd_term* terms, int n, int B, int C, int G, int
     N3D_CHECK_ARG(t->stats && t->gamma && t->beta && t->a_out && t->b_out && t->rows >= 1, "gn_coeffsN: null term pointer");
     qs.q[i] = GnCoefArgs{t->stats, t->rows, t->gamma, t->beta, t->a_out, t->b_out, t->mean_rstd_out, t->sumraw};
   }
-  hipLaunchKernelGGL(gn_coeffsN_kernel, dim3(B, n), dim3(256), 0, (hipStream_t)stream, qs, C, G, gn_cnt_, eps);
+  N3D_LAUNCH(gn_coeffsN_kernel, dim3(B, n), dim3(256), 0, (hipStream_t)stream, qs, C, G, gn_cnt_, eps);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2750,8 +2756,8 @@ int n3d_affine_actN(const n3d_gn_fwd_term* terms, int n, float* out, int64_t old
   if (int e = check_vec(out, old_, C, "affine_actN(out)")) return e;
   EwMap m = ew_map(N, C);
   dim3 grid(m.rows, B), blk(256);
-  if (flags & N3D_ACCUMULATE) hipLaunchKernelGGL(affine_actN_kernel<true>, grid, blk, 0, (hipStream_t)stream, ts, out, old_, N, C, m);
-  else hipLaunchKernelGGL(affine_actN_kernel<false>, grid, blk, 0, (hipStream_t)stream, ts, out, old_, N, C, m);
+  if (flags & N3D_ACCUMULATE) N3D_LAUNCH(affine_actN_kernel<true>, grid, blk, 0, (hipStream_t)stream, ts, out, old_, N, C, m);
+  else N3D_LAUNCH(affine_actN_kernel<false>, grid, blk, 0, (hipStream_t)stream, ts, out, old_, N, C, m);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2769,7 +2775,7 @@ int n3d_affine_act_bwd_reduceN(const float* dout, int64_t dld, const n3d_gn_bwd_
     ts.t[i] = BwdRedTerm{t->raw, t->rld, t->a, t->b, t->sums, t->relu};
   }
   EwMap m = ew_map(N, C);
-  hipLaunchKernelGGL(affine_bwd_reduceN_kernel, dim3(m.rows, B, n), dim3(256), 0, (hipStream_t)stream, dout, dld, ts, N, C, m);
+  N3D_LAUNCH(affine_bwd_reduceN_kernel, dim3(m.rows, B, n), dim3(256), 0, (hipStream_t)stream, dout, dld, ts, N, C, m);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2787,8 +2793,8 @@ int n3d_gn_bwd_coeffsN(const n3d_gn_bwd_term* terms, int n, int B, int C, int G,
     qs.q[i] = GnBwdCoefArgs{t->sums, t->rows, t->gamma, t->mean_rstd, t->wptr, t->dgamma, t->dbeta, t->dalpha, t->cA, t->cB, t->cC, t->sumraw,
                             t->dbias_conv};
   }
-  if (B <= 2) hipLaunchKernelGGL(gn_bwd_coeffsN_kernel<2>, dim3(n), dim3(512), 0, (hipStream_t)stream, qs, B, C, G, gn_cnt_);
-  else hipLaunchKernelGGL(gn_bwd_coeffsN_kernel<GNB_BP>, dim3(n), dim3(256 * GNB_BP), 0, (hipStream_t)stream, qs, B, C, G, gn_cnt_);
+  if (B <= 2) N3D_LAUNCH(gn_bwd_coeffsN_kernel<2>, dim3(n), dim3(512), 0, (hipStream_t)stream, qs, B, C, G, gn_cnt_);
+  else N3D_LAUNCH(gn_bwd_coeffsN_kernel<GNB_BP>, dim3(n), dim3(256 * GNB_BP), 0, (hipStream_t)stream, qs, B, C, G, gn_cnt_);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2806,7 +2812,7 @@ int n3d_affine_act_bwd_applyN(const float* dout, int64_t dld, const n3d_gn_bwd_t
     ts.t[i] = BwdApplyTerm{t->raw, t->rld, t->a, t->b, t->cA, t->cB, t->cC, t->draw, t->drld, t->relu};
   }
   EwMap m = ew_map(N, C);
-  hipLaunchKernelGGL(affine_bwd_applyN_kernel, dim3(m.rows, B, n), dim3(256), 0, (hipStream_t)stream, dout, dld, ts, N, C, m);
+  N3D_LAUNCH(affine_bwd_applyN_kernel, dim3(m.rows, B, n), dim3(256), 0, (hipStream_t)stream, dout, dld, ts, N, C, m);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2839,7 +2845,7 @@ int n3d_affine_act_bwd_apply_sum(const float* dout, int64_t dld, const n3d_gn_bw
     for (int j = 0; j < i; ++j)
       N3D_CHECK_ARG(terms[ts.start[i]].draw != terms[ts.start[j]].draw, "affine_act_bwd_apply_sum: the terms of a target must be consecutive");
   EwMap m = ew_map(N, C);
-  hipLaunchKernelGGL(affine_bwd_apply_sum_kernel, dim3(m.rows, B, nt), dim3(256), 0, (hipStream_t)stream, dout, dld, ts, N, C, m);
+  N3D_LAUNCH(affine_bwd_apply_sum_kernel, dim3(m.rows, B, nt), dim3(256), 0, (hipStream_t)stream, dout, dld, ts, N, C, m);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2847,7 +2853,7 @@ int n3d_affine_act_bwd_apply_sum(const float* dout, int64_t dld, const n3d_gn_bw
 int n3d_plain_bwd_coeffs(const double* sums, int rows, const float* wptr, int B, int C, float* dalpha, float* A, void* stream) {
   N3D_CHECK_ARG(C <= 64 && (A || dalpha), "plain_bwd_coeffs: bad args");
   N3D_CHECK_ARG(!dalpha || sums, "plain_bwd_coeffs: dalpha needs sums");
-  hipLaunchKernelGGL(plain_bwd_coeffs_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, rows, wptr, B, C, dalpha, A);
+  N3D_LAUNCH(plain_bwd_coeffs_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, rows, wptr, B, C, dalpha, A);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2860,7 +2866,7 @@ int n3d_plain_bwd_coeffsN(const n3d_plain_coef_term* terms, int n, int B, int C,
     N3D_CHECK_ARG((!t->dalpha || (t->sums && t->rows >= 1)) && (t->dalpha || t->A), "plain_bwd_coeffsN: null term pointer");
     qs.q[i] = PlainCoefArgs{t->sums, t->rows, t->wptr, t->dalpha, t->A};
   }
-  hipLaunchKernelGGL(plain_bwd_coeffsN_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, qs, B, C);
+  N3D_LAUNCH(plain_bwd_coeffsN_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, qs, B, C);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2880,10 +2886,10 @@ int n3d_affine_act_bwd_apply(const float* dout, int64_t dld, const float* raw, i
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
     const T* d = (const T*)dout; const T* r = (const T*)raw; T* o = (T*)draw;
-    if (relu && acc) hipLaunchKernelGGL((affine_bwd_apply_kernel<true, true, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
-    else if (relu) hipLaunchKernelGGL((affine_bwd_apply_kernel<true, false, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
-    else if (acc) hipLaunchKernelGGL((affine_bwd_apply_kernel<false, true, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
-    else hipLaunchKernelGGL((affine_bwd_apply_kernel<false, false, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
+    if (relu && acc) N3D_LAUNCH((affine_bwd_apply_kernel<true, true, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
+    else if (relu) N3D_LAUNCH((affine_bwd_apply_kernel<true, false, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
+    else if (acc) N3D_LAUNCH((affine_bwd_apply_kernel<false, true, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
+    else N3D_LAUNCH((affine_bwd_apply_kernel<false, false, T>), grid, blk, 0, s, d, dld, r, rld, a, b, A, Bc, Cc, o, drld, N, C, m);
   });
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -2892,7 +2898,7 @@ int n3d_affine_act_bwd_apply(const float* dout, int64_t dld, const float* raw, i
 int n3d_se_gate_fwd(const double* stats, int rows, int64_t N, const float* w1, const float* b1, const float* w2, const float* b2, int B,
                     int C, float* mean, float* hidden, float* gate, void* stream) {
   N3D_CHECK_ARG(stats && w1 && b1 && w2 && b2 && mean && hidden && gate && C <= 64, "se_gate_fwd: bad args");
-  hipLaunchKernelGGL(se_gate_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, stats, rows, (double)N, w1, b1, w2, b2, C, mean, hidden, gate);
+  N3D_LAUNCH(se_gate_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, stats, rows, (double)N, w1, b1, w2, b2, C, mean, hidden, gate);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2904,9 +2910,9 @@ int n3d_se_gate_bwd(const double* sums, int rows, const float* wptr, const float
   if (B == 2) {
     const SeTerm q{sums, rows, w1, nullptr, w2, nullptr, const_cast<float*>(mean), const_cast<float*>(hidden), const_cast<float*>(gate), wptr, dw1, db1, dw2,
                    db2, dalpha, A, Bc};
-    hipLaunchKernelGGL(se_gate_bwd2_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, q, C, (double)N);
+    N3D_LAUNCH(se_gate_bwd2_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, q, C, (double)N);
   } else {
-    hipLaunchKernelGGL(se_gate_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, rows, wptr, mean, hidden, gate, w1, w2, B, C,
+    N3D_LAUNCH(se_gate_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, rows, wptr, mean, hidden, gate, w1, w2, B, C,
                        (double)N, dw1, db1, dw2, db2, dalpha, A, Bc);
   }
   N3D_LAUNCH_CHECK();
@@ -2932,7 +2938,7 @@ int n3d_se_gate_fwdN(const n3d_se_term* terms, int n, int64_t N, int B, int C, v
   N3D_CHECK_ARG(terms && B > 0 && N > 0 && C >= 1 && C <= 64, "se_gate_fwdN: bad args");
   SeTermN ts;
   if (int e = se_terms(terms, n, false, &ts, "se_gate_fwdN")) return e;
-  hipLaunchKernelGGL(se_gate_fwdN_kernel, dim3(B, n), dim3(256), 0, (hipStream_t)stream, ts, (double)N, C);
+  N3D_LAUNCH(se_gate_fwdN_kernel, dim3(B, n), dim3(256), 0, (hipStream_t)stream, ts, (double)N, C);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2941,8 +2947,8 @@ int n3d_se_gate_bwdN(const n3d_se_term* terms, int n, int64_t N, int B, int C, v
   N3D_CHECK_ARG(terms && B > 0 && N > 0 && C >= 1 && C <= 64, "se_gate_bwdN: bad args");
   SeTermN ts;
   if (int e = se_terms(terms, n, true, &ts, "se_gate_bwdN")) return e;
-  if (B == 2) hipLaunchKernelGGL(se_gate_bwdN2_kernel, dim3(n), dim3(512), 0, (hipStream_t)stream, ts, C, (double)N);
-  else hipLaunchKernelGGL(se_gate_bwdN_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ts, B, C, (double)N);
+  if (B == 2) N3D_LAUNCH(se_gate_bwdN2_kernel, dim3(n), dim3(512), 0, (hipStream_t)stream, ts, C, (double)N);
+  else N3D_LAUNCH(se_gate_bwdN_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ts, B, C, (double)N);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2962,7 +2968,7 @@ int n3d_node_fwd_coeffs(const n3d_gn_fwd_term* gn, int n_gn, const n3d_se_term* 
   SeTermN ts;
   if (int e = se_terms(se, n_se, false, &ts, "node_fwd_coeffs")) return e;
   for (int i = 0; i < 8; ++i) qs.s[i] = ts.t[i];
-  hipLaunchKernelGGL(node_fwd_coeffs_kernel, dim3(B, n_gn + n_se), dim3(256), 0, (hipStream_t)stream, qs, C, G, (double)N, eps);
+  N3D_LAUNCH(node_fwd_coeffs_kernel, dim3(B, n_gn + n_se), dim3(256), 0, (hipStream_t)stream, qs, C, G, (double)N, eps);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2986,7 +2992,7 @@ int n3d_node_bwd_coeffs(const n3d_gn_bwd_term* gn, int n_gn, const n3d_se_term* 
     SeTermN ts;
     if (int e = se_terms(se, n_se, true, &ts, "node_bwd_coeffs")) return e;
     for (int i = 0; i < 8; ++i) qs.s[i] = ts.t[i];
-    hipLaunchKernelGGL(node_bwd_coeffs_kernel, dim3(n_gn + n_se), dim3(512), 0, (hipStream_t)stream, qs, C, G, (double)N);
+    N3D_LAUNCH(node_bwd_coeffs_kernel, dim3(n_gn + n_se), dim3(512), 0, (hipStream_t)stream, qs, C, G, (double)N);
     N3D_LAUNCH_CHECK();
     return N3D_OK;
   }
@@ -3007,10 +3013,10 @@ int n3d_pool2_fwd(const float* x, int64_t xld, float* y, int64_t yld, int B, int
   dim3 grid((unsigned)cdiv(total, 256), B), blk(256);
   if (bf) {
     const bf16_t* xb = (const bf16_t*)x; bf16_t* yb = (bf16_t*)y;
-    if (flags & N3D_POOL_MAX) hipLaunchKernelGGL((pool2_fwd_kernel<true, bf16_t>), grid, blk, 0, (hipStream_t)stream, xb, xld, yb, yld, Di, Hi, Wi, C);
-    else hipLaunchKernelGGL((pool2_fwd_kernel<false, bf16_t>), grid, blk, 0, (hipStream_t)stream, xb, xld, yb, yld, Di, Hi, Wi, C);
-  } else if (flags & N3D_POOL_MAX) hipLaunchKernelGGL((pool2_fwd_kernel<true>), grid, blk, 0, (hipStream_t)stream, x, xld, y, yld, Di, Hi, Wi, C);
-  else hipLaunchKernelGGL((pool2_fwd_kernel<false>), grid, blk, 0, (hipStream_t)stream, x, xld, y, yld, Di, Hi, Wi, C);
+    if (flags & N3D_POOL_MAX) N3D_LAUNCH((pool2_fwd_kernel<true, bf16_t>), grid, blk, 0, (hipStream_t)stream, xb, xld, yb, yld, Di, Hi, Wi, C);
+    else N3D_LAUNCH((pool2_fwd_kernel<false, bf16_t>), grid, blk, 0, (hipStream_t)stream, xb, xld, yb, yld, Di, Hi, Wi, C);
+  } else if (flags & N3D_POOL_MAX) N3D_LAUNCH((pool2_fwd_kernel<true>), grid, blk, 0, (hipStream_t)stream, x, xld, y, yld, Di, Hi, Wi, C);
+  else N3D_LAUNCH((pool2_fwd_kernel<false>), grid, blk, 0, (hipStream_t)stream, x, xld, y, yld, Di, Hi, Wi, C);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3022,7 +3028,7 @@ int n3d_pool2_fwd_both(const float* x, int64_t xld, float* y_avg, int64_t yald, 
   if (int e = check_vec(y_avg, yald, C, "pool2_fwd_both(y_avg)")) return e;
   if (int e = check_vec(y_max, ymld, C, "pool2_fwd_both(y_max)")) return e;
   const int64_t total = (int64_t)(Di / 2) * (Hi / 2) * (Wi / 2) * (C / 4);
-  hipLaunchKernelGGL(pool2_fwd_both_kernel, dim3((unsigned)cdiv(total, 256), B), dim3(256), 0, (hipStream_t)stream, x, xld, y_avg, yald, y_max, ymld,
+  N3D_LAUNCH(pool2_fwd_both_kernel, dim3((unsigned)cdiv(total, 256), B), dim3(256), 0, (hipStream_t)stream, x, xld, y_avg, yald, y_max, ymld,
                      Di, Hi, Wi, C);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -3036,8 +3042,8 @@ int n3d_pool2_bwd_both(const float* dy, int64_t dyld, const float* x, int64_t xl
   if (int e = check_vec(x, xld, C, "pool2_bwd_both(x)")) return e;
   const int64_t total = (int64_t)(Di / 2) * (Hi / 2) * (Wi / 2) * (C / 4);
   dim3 grid((unsigned)cdiv(total, 256), B), blk(256);
-  if (flags & N3D_ACCUMULATE) hipLaunchKernelGGL(pool2_bwd_both_kernel<true>, grid, blk, 0, (hipStream_t)stream, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, w_avg, w_max);
-  else hipLaunchKernelGGL(pool2_bwd_both_kernel<false>, grid, blk, 0, (hipStream_t)stream, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, w_avg, w_max);
+  if (flags & N3D_ACCUMULATE) N3D_LAUNCH(pool2_bwd_both_kernel<true>, grid, blk, 0, (hipStream_t)stream, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, w_avg, w_max);
+  else N3D_LAUNCH(pool2_bwd_both_kernel<false>, grid, blk, 0, (hipStream_t)stream, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, w_avg, w_max);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3059,17 +3065,17 @@ int n3d_pool2_bwd_scaled(const float* dy, int64_t dyld, const float* x, int64_t 
   hipStream_t s = (hipStream_t)stream;
   if (bf) {       // all three tensors in bf16 storage (round 5)
     const bf16_t* dyb = (const bf16_t*)dy; const bf16_t* xb = (const bf16_t*)x; bf16_t* dxb = (bf16_t*)dx;
-    if (mx && acc) hipLaunchKernelGGL((pool2_bwd_kernel<true, true, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
-    else if (mx) hipLaunchKernelGGL((pool2_bwd_kernel<true, false, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
-    else if (acc) hipLaunchKernelGGL((pool2_bwd_kernel<false, true, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
-    else hipLaunchKernelGGL((pool2_bwd_kernel<false, false, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
+    if (mx && acc) N3D_LAUNCH((pool2_bwd_kernel<true, true, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
+    else if (mx) N3D_LAUNCH((pool2_bwd_kernel<true, false, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
+    else if (acc) N3D_LAUNCH((pool2_bwd_kernel<false, true, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
+    else N3D_LAUNCH((pool2_bwd_kernel<false, false, bf16_t>), grid, blk, 0, s, dyb, dyld, xb, xld, dxb, dxld, Di, Hi, Wi, C, wptr);
     N3D_LAUNCH_CHECK();
     return N3D_OK;
   }
-  if (mx && acc) hipLaunchKernelGGL((pool2_bwd_kernel<true, true>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
-  else if (mx) hipLaunchKernelGGL((pool2_bwd_kernel<true, false>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
-  else if (acc) hipLaunchKernelGGL((pool2_bwd_kernel<false, true>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
-  else hipLaunchKernelGGL((pool2_bwd_kernel<false, false>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
+  if (mx && acc) N3D_LAUNCH((pool2_bwd_kernel<true, true>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
+  else if (mx) N3D_LAUNCH((pool2_bwd_kernel<true, false>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
+  else if (acc) N3D_LAUNCH((pool2_bwd_kernel<false, true>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
+  else N3D_LAUNCH((pool2_bwd_kernel<false, false>), grid, blk, 0, s, dy, dyld, x, xld, dx, dxld, Di, Hi, Wi, C, wptr);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3078,8 +3084,8 @@ int n3d_dice_fwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const fl
                  int64_t N, float smooth, double* partial, double* sums, float* loss, void* stream) {
   N3D_CHECK_ARG(p && t && partial && sums && loss && B > 0 && C > 0 && N > 0, "dice_fwd: bad args");
   const int rows = (int)cdiv(N, DICE_CHUNK);
-  hipLaunchKernelGGL(dice_reduce_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, p, psb, psc, psv, t, tsb, tsc, tsv, N, partial);
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, rows, B * C, (double)smooth, sums, loss);
+  N3D_LAUNCH(dice_reduce_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, p, psb, psc, psv, t, tsb, tsc, tsv, N, partial);
+  N3D_LAUNCH(dice_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, rows, B * C, (double)smooth, sums, loss);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3089,7 +3095,7 @@ int n3d_dice_bwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const fl
                  void* stream) {
   N3D_CHECK_ARG(t && sums && dp, "dice_bwd: bad args");
   const int rows = (int)cdiv(N, DICE_CHUNK);
-  hipLaunchKernelGGL(dice_bwd_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, p, psb, psc, psv, t, tsb, tsc, tsv, N, B * C,
+  N3D_LAUNCH(dice_bwd_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, p, psb, psc, psv, t, tsb, tsc, tsv, N, B * C,
                      (double)smooth, sums, dloss, dp, dsb, dsc, dsv);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -3097,13 +3103,13 @@ int n3d_dice_bwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const fl
 
 int n3d_ncdhw_to_ndhwc(const float* src, float* dst, int64_t dld, int B, int C, int64_t N, void* stream) {
   N3D_CHECK_ARG(src && dst && dld >= C, "ncdhw_to_ndhwc: bad args");
-  hipLaunchKernelGGL(ncdhw_to_ndhwc_kernel, dim3((unsigned)cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, src, dst, dld, C, N);
+  N3D_LAUNCH(ncdhw_to_ndhwc_kernel, dim3((unsigned)cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, src, dst, dld, C, N);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
 int n3d_ndhwc_to_ncdhw(const float* src, int64_t sld, float* dst, int B, int C, int64_t N, void* stream) {
   N3D_CHECK_ARG(src && dst && sld >= C, "ndhwc_to_ncdhw: bad args");
-  hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel, dim3((unsigned)cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, src, sld, dst, C, N);
+  N3D_LAUNCH(ndhwc_to_ncdhw_kernel, dim3((unsigned)cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, src, sld, dst, C, N);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3115,7 +3121,7 @@ int n3d_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 }
 int n3d_guard_flag(const void* timeouts, const void* acked, float* flag, void* stream) {
   N3D_CHECK_ARG(timeouts && acked && flag, "guard_flag: null pointer");
-  hipLaunchKernelGGL(guard_flag_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned*)timeouts, (const unsigned*)acked, flag);
+  N3D_LAUNCH(guard_flag_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned*)timeouts, (const unsigned*)acked, flag);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3132,9 +3138,9 @@ int n3d_adam_step_guarded(float* param, const float* grad, float* exp_avg, float
   int64_t blocks = cdiv(n, adam_epb);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, lr_ptr,
+  N3D_LAUNCH(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, lr_ptr,
                      beta1, beta2, eps, weight_decay, grad_scale, step_ptr, inc_step == 2 ? 1 : 0, gd);
-  if (inc_step == 1) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
+  if (inc_step == 1) N3D_LAUNCH(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -3161,7 +3167,7 @@ int n3d_affine_act_gn(const float* raw, int64_t rld, const double* stats, int ro
   const bool relu = flags & N3D_RELU, acc = flags & N3D_ACCUMULATE;
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-#define N3D_AAG(R, A_) hipLaunchKernelGGL((affine_act_gn_kernel<R, A_, T>), grid, blk, 0, s, (const T*)raw, rld, stats, rows, gamma, beta, G, gn_cnt_, eps, wptr, (T*)out, old_, N, C, m, a_out, b_out, mean_rstd_out, sumraw)
+#define N3D_AAG(R, A_) N3D_LAUNCH((affine_act_gn_kernel<R, A_, T>), grid, blk, 0, s, (const T*)raw, rld, stats, rows, gamma, beta, G, gn_cnt_, eps, wptr, (T*)out, old_, N, C, m, a_out, b_out, mean_rstd_out, sumraw)
     if (relu && acc) N3D_AAG(true, true); else if (relu) N3D_AAG(true, false); else if (acc) N3D_AAG(false, true); else N3D_AAG(false, false);
 #undef N3D_AAG
   });
@@ -3190,7 +3196,7 @@ int n3d_affine_act_bwd_apply_gn(const float* dout, int64_t dld, const float* raw
   const bool relu = flags & N3D_RELU, acc = flags & N3D_ACCUMULATE;
   with_act_type(bf, [&](auto* tag) {
     using T = N3D_T(tag);
-#define N3D_ABG(R, A_) hipLaunchKernelGGL((affine_bwd_apply_gn_kernel<R, A_, T>), grid, blk, 0, s, (const T*)dout, dld, (const T*)raw, rld, a, b, sums, rows, gamma, mean_rstd, wptr, sumraw, B, G, gn_cnt_, (T*)draw, drld, N, C, m, dgamma, dbeta, dalpha, dbias_conv)
+#define N3D_ABG(R, A_) N3D_LAUNCH((affine_bwd_apply_gn_kernel<R, A_, T>), grid, blk, 0, s, (const T*)dout, dld, (const T*)raw, rld, a, b, sums, rows, gamma, mean_rstd, wptr, sumraw, B, G, gn_cnt_, (T*)draw, drld, N, C, m, dgamma, dbeta, dalpha, dbias_conv)
     if (relu && acc) N3D_ABG(true, true); else if (relu) N3D_ABG(true, false); else if (acc) N3D_ABG(false, true); else N3D_ABG(false, false);
 #undef N3D_ABG
   });
@@ -3201,6 +3207,7 @@ int n3d_affine_act_bwd_apply_gn(const float* dout, int64_t dld, const float* raw
 int n3d_zero(void* p, size_t bytes, void* stream) {
   N3D_CHECK_ARG(p || bytes == 0, "zero: null");
   if (bytes == 0) return N3D_OK;
+  n3d::entry_flush();      // (no kernel of ours: an armed entry signal goes out in front)
   hipError_t e = hipMemsetAsync(p, 0, bytes, (hipStream_t)stream);
   if (e != hipSuccess) { set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return N3D_OK;

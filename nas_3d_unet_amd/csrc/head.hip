@@ -492,9 +492,9 @@ static bool launch_head_fwd(const HeadFwdArgs& a, int B, bool t_u8, hipStream_t 
   const bool three = a.Co == 3;
   if (t_u8 && !three) return false;
 #define N3D_HEAD_FWD(Q_)                                                                                                     \
-  case Q_: if (t_u8) hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, 3, uint8_t, EVAL>), grid, blk, 0, s, a);                     \
-           else if (three) hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, 3, float, EVAL>), grid, blk, 0, s, a);                 \
-           else hipLaunchKernelGGL((head_fwd_kernel<TX, Q_, HEAD_COMAX, float, EVAL>), grid, blk, 0, s, a);                   \
+  case Q_: if (t_u8) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, uint8_t, EVAL>), grid, blk, 0, s, a);                     \
+           else if (three) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, float, EVAL>), grid, blk, 0, s, a);                 \
+           else N3D_LAUNCH((head_fwd_kernel<TX, Q_, HEAD_COMAX, float, EVAL>), grid, blk, 0, s, a);                   \
            break;
   switch (a.Ci / 4) {
     N3D_HEAD_FWD(1) N3D_HEAD_FWD(2) N3D_HEAD_FWD(3) N3D_HEAD_FWD(4) N3D_HEAD_FWD(6) N3D_HEAD_FWD(8)
@@ -510,9 +510,9 @@ static bool launch_head_bwd(const HeadBwdArgs& a, int B, bool t_u8, hipStream_t 
   const bool three = a.Co == 3;
   if (t_u8 && !three) return false;
 #define N3D_HEAD_BWD(Q_)                                                                                                     \
-  case Q_: if (t_u8) hipLaunchKernelGGL((head_bwd_kernel<TX, TD, Q_, 3, uint8_t>), grid, blk, 0, s, a);                       \
-           else if (three) hipLaunchKernelGGL((head_bwd_kernel<TX, TD, Q_, 3>), grid, blk, 0, s, a);                          \
-           else hipLaunchKernelGGL((head_bwd_kernel<TX, TD, Q_, HEAD_COMAX>), grid, blk, 0, s, a);                            \
+  case Q_: if (t_u8) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3, uint8_t>), grid, blk, 0, s, a);                       \
+           else if (three) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3>), grid, blk, 0, s, a);                          \
+           else N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, HEAD_COMAX>), grid, blk, 0, s, a);                            \
            break;
   switch (a.Ci / 4) {
     N3D_HEAD_BWD(1) N3D_HEAD_BWD(2) N3D_HEAD_BWD(3) N3D_HEAD_BWD(4) N3D_HEAD_BWD(6) N3D_HEAD_BWD(8)
@@ -551,7 +551,7 @@ float n3d_dropout3d_uniform(uint64_t seed, uint32_t counter, uint32_t index) { r
 
 int n3d_dropout3d_gate(uint32_t* state, float p, int B, int C, float* gate, void* stream) {
   N3D_CHECK_ARG(state && gate && B > 0 && C > 0 && p >= 0.f && p < 1.f, "dropout3d_gate: bad args");
-  hipLaunchKernelGGL(dropout3d_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, p, B * C, gate);
+  N3D_LAUNCH(dropout3d_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, p, B * C, gate);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -579,7 +579,7 @@ int n3d_head_fwd(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t 
   a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
   const bool ok = h->x_dtype == N3D_BF16 ? launch_head_fwd<bf16_t>(a, h->B, u8, s) : launch_head_fwd<float>(a, h->B, u8, s);
   if (!ok) N3D_UNSUPPORTED("head_fwd: Ci=%d", h->Ci);
-  if (t) hipLaunchKernelGGL(head_dice_finalize_kernel<>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
+  if (t) N3D_LAUNCH(head_dice_finalize_kernel<>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
                            HeadEvalAcc{});
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -602,7 +602,7 @@ int n3d_head_eval(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t
   a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
   const bool ok = h->x_dtype == N3D_BF16 ? launch_head_fwd<bf16_t, true>(a, h->B, u8, s) : launch_head_fwd<float, true>(a, h->B, u8, s);
   if (!ok) N3D_UNSUPPORTED("head_eval: Ci=%d", h->Ci);
-  hipLaunchKernelGGL(head_dice_finalize_kernel<true>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
+  N3D_LAUNCH(head_dice_finalize_kernel<true>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
                      HeadEvalAcc{hpartial, h->Co, acc});
   N3D_LAUNCH_CHECK();
   return N3D_OK;

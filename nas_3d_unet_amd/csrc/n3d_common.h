@@ -39,6 +39,22 @@ void set_error(const char* fmt, ...);
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- entry signals (include/n3d.h, "Entry signals"): a stream hand-off signal carried in the entry of the next kernel of its stream.
+// Up to two (flag, step, bump) records, by value, as the LAST parameter of a carrier kernel (the argument structs of the kernel
+// families stay as they are: several of them are also elements of the multi-launch tables); flag0 == nullptr means "none".
+struct EntrySignal {
+  unsigned* flag0; unsigned* step0;
+  unsigned* flag1; unsigned* step1;
+  int bump;      // bit 0: bump *step0 behind the first store, bit 1: *step1 behind the second
+};
+// Host side (n3d_core.hip), per thread.  entry_flush(): stand-alone signal kernels for whatever is armed -- runs in front of EVERY
+// launch of the library (N3D_LAUNCH below) and in the entry points that enqueue stream work without a kernel of ours (n3d_zero,
+// the n3d_comm_* collectives, n3d_stream_capture_end, n3d_graph_launch), so a kernel that carries nothing cannot lose a signal.
+// entry_take(s): what a carrier passes as its last kernel argument, taken right before its launch -- the signals armed for stream s (they count
+// as issued from here on); signals armed for another stream are flushed to their own stream and an empty record comes back.
+void entry_flush();
+EntrySignal entry_take(hipStream_t s);
+
 // Division by a launch-time constant without the ~40-200 instruction integer-division sequences hipcc emits
 // for runtime divisors (index decoding used to dominate the small kernels).  Exact for 0 <= n < 2^31.
 struct FastDiv {
@@ -105,6 +121,30 @@ static inline EwMap ew_map(int64_t N, int C) {
 }
 
 #ifdef __HIPCC__
+// Carrier kernels call this first, in front of every early return: thread (0,0,0) of workgroup (0,0,0) does what sync_signal_kernel
+// does (n3d_core.hip), the other lanes and waves go on -- no barrier behind it.  The stores of the stream's earlier kernels were
+// released by the kernel boundary in front of this kernel.  An empty record costs one uniform compare.
+__device__ __forceinline__ void entry_signal(const EntrySignal& e) {
+  if (__builtin_expect(e.flag0 != nullptr, 0)) {
+    if ((blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x | threadIdx.y | threadIdx.z) == 0) {
+      unsigned s = __hip_atomic_load(e.step0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(e.flag0, s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      if (e.bump & 1) __hip_atomic_store(e.step0, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (e.flag1 != nullptr) {
+        s = __hip_atomic_load(e.step1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(e.flag1, s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (e.bump & 2) __hip_atomic_store(e.step1, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+// THE way to launch a kernel in libn3d (no bare <<<>>> and no hipLaunchKernelGGL in csrc/: tests/test_host_cpu_launch_rule.py):
+// whatever is still armed when a launch is issued was not taken by a carrier and becomes a stand-alone signal launch in front of it.
+#define N3D_LAUNCH(kernel_, grid_, block_, shmem_, stream_, ...)                                   \
+  do {                                                                                            \
+    n3d::entry_flush();                                                                           \
+    kernel_<<<(grid_), (block_), (shmem_), (stream_)>>>(__VA_ARGS__);                             \
+  } while (0)
 // Kernels of the dependent chain raise their waves' issue priority (s_setprio 0..3, 0 = the reset value): the weight-gradient
 // kernels, which only ever run beside the chain on the side streams, stay at 0, so where both have waves on a SIMD the chain's
 // instructions go first.  No effect when a kernel has the chip to itself.

@@ -1,6 +1,8 @@
 // Error reporting, version and device probe for libn3d.
 #include <stdarg.h>
 
+#include <atomic>
+
 #include "n3d_common.h"
 
 namespace n3d {
@@ -25,7 +27,10 @@ __global__ void sync_signal_kernel(unsigned* flag, unsigned* step, int bump) {
   __hip_atomic_store(flag, s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   if (bump) *step = s + 1;
 }
-__global__ void sync_wait_kernel(const unsigned* flag, unsigned* step, unsigned* timeouts, int bump, long max_polls) {
+// The wait kernels carry entry signals (n3d_common.h): they store first and poll afterwards, so a stream's signal in front of its
+// wait ("S W") is one launch, and the other stream sees the store no later than it would have.
+__global__ void sync_wait_kernel(const unsigned* flag, unsigned* step, unsigned* timeouts, int bump, long max_polls, n3d::EntrySignal es) {
+  n3d::entry_signal(es);
   unsigned want = *step;
   bool ok = false;
   for (long it = 0; it < max_polls; ++it) {
@@ -39,7 +44,9 @@ __global__ void sync_wait_kernel(const unsigned* flag, unsigned* step, unsigned*
 }
 // two flags, one launch: where a stream has two joins in a row (a cell's own side work and the late writer of one of its gradient
 // buffers) the second wait kernel and its boundary (~3.3 us on the chain) go
-__global__ void sync_wait2_kernel(const unsigned* flag0, const unsigned* flag1, unsigned* step, unsigned* timeouts, int bump, long max_polls) {
+__global__ void sync_wait2_kernel(const unsigned* flag0, const unsigned* flag1, unsigned* step, unsigned* timeouts, int bump, long max_polls,
+                                  n3d::EntrySignal es) {
+  n3d::entry_signal(es);
   unsigned want = *step;
   bool ok0 = false, ok1 = false;
   for (long it = 0; it < max_polls; ++it) {
@@ -53,34 +60,97 @@ __global__ void sync_wait2_kernel(const unsigned* flag0, const unsigned* flag1, 
   if (bump) *step = want + 1;
 }
 __global__ void stamp_kernel(unsigned long long* out) { *out = __builtin_amdgcn_s_memrealtime(); }
+
+// ---- entry signals, host side (include/n3d.h, "Entry signals") ---------------------------------------------------------------
+struct EntryArmed {
+  int n = 0;
+  hipStream_t stream = nullptr;
+  n3d::EntrySignal sig = {nullptr, nullptr, nullptr, nullptr, 0};
+};
+thread_local EntryArmed g_armed;
+std::atomic<int64_t> g_carried{0}, g_standalone{0};
 }  // namespace
+
+namespace n3d {
+void entry_flush() {
+  EntryArmed& a = g_armed;
+  if (a.n == 0) return;
+  const EntrySignal e = a.sig;
+  const hipStream_t s = a.stream;
+  g_standalone += a.n;
+  a = EntryArmed();
+  sync_signal_kernel<<<dim3(1), dim3(1), 0, s>>>(e.flag0, e.step0, e.bump & 1);
+  if (e.flag1) sync_signal_kernel<<<dim3(1), dim3(1), 0, s>>>(e.flag1, e.step1, (e.bump >> 1) & 1);
+}
+EntrySignal entry_take(hipStream_t s) {
+  EntryArmed& a = g_armed;
+  const EntrySignal none = {nullptr, nullptr, nullptr, nullptr, 0};
+  if (a.n == 0) return none;
+  if (a.stream != s) { entry_flush(); return none; }
+  const EntrySignal e = a.sig;
+  g_carried += a.n;
+  a = EntryArmed();
+  return e;
+}
+}  // namespace n3d
 
 extern "C" {
 int n3d_stamp(void* out, void* stream) {
   N3D_CHECK_ARG(out && (reinterpret_cast<uintptr_t>(out) & 7) == 0, "n3d_stamp: needs an 8-byte aligned device word");
-  hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long*)out);
+  N3D_LAUNCH(stamp_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long*)out);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
 int n3d_sync_signal(void* flag, void* step, int bump, void* stream) {
   N3D_CHECK_ARG(flag && step, "n3d_sync_signal: null pointer");
-  hipLaunchKernelGGL(sync_signal_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned*)flag, (unsigned*)step, bump);
+  N3D_LAUNCH(sync_signal_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned*)flag, (unsigned*)step, bump);
   N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+int n3d_entry_signal_arm(void* flag, void* step, int bump, void* stream) {
+  N3D_CHECK_ARG(flag && step, "n3d_entry_signal_arm: null pointer");
+  EntryArmed& a = g_armed;
+  if (a.n && (a.n == 2 || a.stream != (hipStream_t)stream)) {   // no room, or armed for another stream: those go out first
+    n3d::entry_flush();
+    N3D_LAUNCH_CHECK();
+  }
+  a.stream = (hipStream_t)stream;
+  if (a.n == 0) {
+    a.sig.flag0 = (unsigned*)flag; a.sig.step0 = (unsigned*)step; a.sig.bump = bump ? 1 : 0;
+  } else {
+    a.sig.flag1 = (unsigned*)flag; a.sig.step1 = (unsigned*)step; a.sig.bump |= bump ? 2 : 0;
+  }
+  ++a.n;
+  return N3D_OK;
+}
+int n3d_entry_signal_flush(void* stream) {
+  if (g_armed.n && g_armed.stream == (hipStream_t)stream) {
+    n3d::entry_flush();
+    N3D_LAUNCH_CHECK();
+  }
+  return N3D_OK;
+}
+int n3d_entry_signal_pending(void) { return g_armed.n; }
+int n3d_entry_signal_counts(int64_t* carried, int64_t* standalone) {
+  if (carried) *carried = g_carried.load();
+  if (standalone) *standalone = g_standalone.load();
   return N3D_OK;
 }
 int n3d_sync_wait(const void* flag, void* step, void* timeouts, int bump, int64_t max_polls, void* stream) {
   N3D_CHECK_ARG(flag && step && timeouts, "n3d_sync_wait: null pointer");
   N3D_CHECK_ARG(max_polls > 0, "n3d_sync_wait: max_polls must be positive (the poll is bounded by construction)");
-  hipLaunchKernelGGL(sync_wait_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned*)flag, (unsigned*)step,
-                     (unsigned*)timeouts, bump, (long)max_polls);
+  const n3d::EntrySignal es = n3d::entry_take((hipStream_t)stream);
+  N3D_LAUNCH(sync_wait_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned*)flag, (unsigned*)step,
+                     (unsigned*)timeouts, bump, (long)max_polls, es);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
 int n3d_sync_wait2(const void* flag0, const void* flag1, void* step, void* timeouts, int bump, int64_t max_polls, void* stream) {
   N3D_CHECK_ARG(flag0 && flag1 && step && timeouts, "n3d_sync_wait2: null pointer");
   N3D_CHECK_ARG(max_polls > 0, "n3d_sync_wait2: max_polls must be positive (the poll is bounded by construction)");
-  hipLaunchKernelGGL(sync_wait2_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned*)flag0, (const unsigned*)flag1, (unsigned*)step,
-                     (unsigned*)timeouts, bump, (long)max_polls);
+  const n3d::EntrySignal es = n3d::entry_take((hipStream_t)stream);
+  N3D_LAUNCH(sync_wait2_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned*)flag0, (const unsigned*)flag1, (unsigned*)step,
+                     (unsigned*)timeouts, bump, (long)max_polls, es);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -128,6 +198,7 @@ int n3d_stream_capture_end(void* stream, void** graph_exec_out) {
   N3D_CHECK_ARG(graph_exec_out, "n3d_stream_capture_end: null pointer");
   hipGraph_t g = nullptr;
   hipGraphExec_t ex = nullptr;
+  n3d::entry_flush();      // an armed signal belongs in the graph that is being closed
   if (hipStreamEndCapture((hipStream_t)stream, &g) != hipSuccess || !g) {
     n3d::set_error("n3d_stream_capture_end: hipStreamEndCapture failed");
     (void)hipGetLastError();
@@ -145,6 +216,7 @@ int n3d_stream_capture_end(void* stream, void** graph_exec_out) {
 }
 int n3d_graph_launch(void* graph_exec, void* stream) {
   N3D_CHECK_ARG(graph_exec, "n3d_graph_launch: null graph");
+  n3d::entry_flush();
   if (hipGraphLaunch((hipGraphExec_t)graph_exec, (hipStream_t)stream) != hipSuccess) {
     n3d::set_error("n3d_graph_launch: hipGraphLaunch failed");
     (void)hipGetLastError();

@@ -122,15 +122,15 @@ extern "C" int n3d_volume_sat(const float* vol, int Cv, const uint8_t* truth, in
   hipStream_t s = (hipStream_t)stream;
   int2* T = reinterpret_cast<int2*>(sat);
   const int64_t lines = (int64_t)(X + 1) * (Y + 1);
-  hipLaunchKernelGGL(sat_z_kernel, dim3((unsigned)cdiv(lines, 4)), dim3(256), 0, s, vol, Cv, truth, X, Y, Z, T);
+  N3D_LAUNCH(sat_z_kernel, dim3((unsigned)cdiv(lines, 4)), dim3(256), 0, s, vol, Cv, truth, X, Y, Z, T);
   N3D_LAUNCH_CHECK();
   const int64_t Zp = Z + 1, Yp = Y + 1;
   // y pass: lines (x' >= 1, z'), running along y' (stride Z+1); x pass: lines (y', z'), running along x' (stride (Y+1)(Z+1))
   const int64_t ny = (int64_t)X * Zp;
-  hipLaunchKernelGGL(sat_scan_kernel, dim3((unsigned)cdiv(ny, 256)), dim3(256), 0, s, T, ny, (int)Zp, Yp * Zp, Zp, Y + 1, 1);
+  N3D_LAUNCH(sat_scan_kernel, dim3((unsigned)cdiv(ny, 256)), dim3(256), 0, s, T, ny, (int)Zp, Yp * Zp, Zp, Y + 1, 1);
   N3D_LAUNCH_CHECK();
   const int64_t nx = Yp * Zp;
-  hipLaunchKernelGGL(sat_scan_kernel, dim3((unsigned)cdiv(nx, 256)), dim3(256), 0, s, T, nx, (int)Zp, Zp, Yp * Zp, X + 1, 0);
+  N3D_LAUNCH(sat_scan_kernel, dim3((unsigned)cdiv(nx, 256)), dim3(256), 0, s, T, nx, (int)Zp, Zp, Yp * Zp, X + 1, 0);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -141,7 +141,7 @@ extern "C" int n3d_patch_qualify(const n3d_patch_volume* vols, int nvol, const i
   N3D_CHECK_ARG(cand && flags && (vols || nvol == 0), "patch_qualify: bad args");
   N3D_CHECK_ARG((reinterpret_cast<uintptr_t>(cand) & 15) == 0, "patch_qualify: the candidate table must be 16-byte aligned");
   const int64_t blocks = cdiv(N, 256) < 8192 ? cdiv(N, 256) : 8192;
-  hipLaunchKernelGGL(patch_qualify_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, vols, nvol,
+  N3D_LAUNCH(patch_qualify_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, vols, nvol,
                      reinterpret_cast<const int4*>(cand), N, P, flags);
   N3D_LAUNCH_CHECK();
   return N3D_OK;

@@ -60,7 +60,7 @@ extern "C" int n3d_stitch(const float* patches, int64_t sb, int64_t sc, int64_t 
   N3D_CHECK_ARG(ox >= 0 && oy >= 0 && oz >= 0 && ox + X <= FX && oy + Y <= FY && oz + Z <= FZ, "stitch: brain-wide box outside the full image");
   N3D_CHECK_ARG((int64_t)X * Y * Z < (1ll << 31), "stitch: volume too large");
   const uint32_t N = (uint32_t)X * Y * Z;
-  hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, patches, sb, sc, sv, C, P, corners, B, X, Y, Z, out,
+  N3D_LAUNCH(stitch_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, patches, sb, sc, sv, C, P, corners, B, X, Y, Z, out,
                      FX, FY, FZ, ox, oy, oz, FastDiv((uint32_t)Z), FastDiv((uint32_t)Y * Z));
   N3D_LAUNCH_CHECK();
   return N3D_OK;
@@ -68,7 +68,7 @@ extern "C" int n3d_stitch(const float* patches, int64_t sb, int64_t sc, int64_t 
 
 extern "C" int n3d_tumor_labels(const double* pred, int64_t N, double threshold, int inclusive, uint8_t* out, void* stream) {
   N3D_CHECK_ARG(pred && out && N > 0, "tumor_labels: bad args");
-  hipLaunchKernelGGL(tumor_labels_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, pred, N, threshold, inclusive, out);
+  N3D_LAUNCH(tumor_labels_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, pred, N, threshold, inclusive, out);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }

@@ -24,10 +24,76 @@ __all__ = ["View", "as_view", "empty_ndhwc", "stream_ptr", "conv_geom", "ptr"]
 _redirect = None
 
 
+# Entry signals (include/n3d.h, "Entry signals"): while a stream is being CAPTURED (entry_capture_begin .. entry_capture_end: torch's
+# capture of the main stream in Trainer._capture_side, n3d_stream_capture_begin .. _end on the side streams) a hand-off signal of the
+# side schedule is not launched but kept here, per stream handle, until the next launch wrapper asks for that stream's pointer
+# (stream_ptr(), right in front of its library call): there it is armed, and libn3d stores it in the entry of that launch's kernel --
+# or, where the kernel carries nothing, launches the signal kernel in front of it.  A signal waiting for its own stream's next launch
+# stays where it is while OTHER streams launch: in a captured graph the store's place in its own stream's order is all that counts.
+# Outside capture (eager passes, warm-up, autograd's thread) signals are launched as before: a held-back signal would also wait for
+# the HOST to issue the stream's next launch while the other stream polls.
+ENTRY_SIGNALS = os.environ.get("N3D_ENTRY_SIGNALS", "1") != "0"    # False: every signal a stand-alone launch (A/B runs, tests)
+_entry_streams = set()     # handles of the streams being captured
+_entry_pending = {}        # stream handle -> [(flag, step, bump)] (at most two: what one kernel entry holds)
+
+
+def _launch_handle():
+    return _redirect if _redirect is not None else torch.cuda.current_stream().cuda_stream
+
+
 def stream_ptr():
-    if _redirect is not None:
-        return C.c_void_p(_redirect)
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    h = _launch_handle()
+    if _entry_pending:
+        q = _entry_pending.pop(h, None)
+        if q:
+            lib = _lib.load()
+            for f, st, b in q:
+                check(lib.n3d_entry_signal_arm(C.c_void_p(f), C.c_void_p(st), b, C.c_void_p(h)), "n3d_entry_signal_arm")
+    return C.c_void_p(h)
+
+
+def flush_entry_signals(handle=None):
+    """stand-alone signal launches, each on its own stream, for whatever is armed or pending (handle: for that stream only)"""
+    lib = _lib.load()
+    for h in ([handle] if handle is not None else list(_entry_pending)):
+        check(lib.n3d_entry_signal_flush(C.c_void_p(h)), "n3d_entry_signal_flush")     # (armed earlier than anything still pending)
+        for f, st, b in _entry_pending.pop(h, ()):
+            check(lib.n3d_sync_signal(C.c_void_p(f), C.c_void_p(st), b, C.c_void_p(h)), "n3d_sync_signal")
+
+
+def entry_capture_begin(handle):
+    """the stream `handle` is being captured from here on: its hand-off signals ride in the entry of its next launch"""
+    if ENTRY_SIGNALS:
+        _entry_streams.add(handle)
+
+
+def entry_capture_end(handle):
+    """call BEFORE the capture of `handle` is closed: whatever has found no launch to ride in goes out now"""
+    _entry_streams.discard(handle)
+    flush_entry_signals(handle)
+
+
+def entry_capture_abort(handle):
+    """the capture of `handle` has failed (an exception inside it): its held-back signals are dropped, not launched -- a launch into an
+    invalidated capture would fail too and hide the first error.  What is armed in the library goes with them."""
+    _entry_streams.discard(handle)
+    _entry_pending.pop(handle, None)
+    try:
+        _lib.load().n3d_entry_signal_flush(C.c_void_p(handle))      # (status ignored: the graph is lost anyway)
+    except Exception:
+        pass
+
+
+def entry_signal_pending():
+    """signals held back here or armed in the library and not yet issued (0 whenever no capture is open)"""
+    return sum(len(q) for q in _entry_pending.values()) + int(_lib.load().n3d_entry_signal_pending())
+
+
+def entry_signal_counts():
+    """(signals carried by a kernel entry, signals the library launched stand-alone) since the library was loaded"""
+    a, b = C.c_int64(0), C.c_int64(0)
+    check(_lib.load().n3d_entry_signal_counts(C.byref(a), C.byref(b)), "n3d_entry_signal_counts")
+    return a.value, b.value
 
 
 class on_side:
@@ -1474,11 +1540,13 @@ def stream_create_low_priority():
 
 def stream_capture_begin(stream):
     check(_lib.load().n3d_stream_capture_begin(C.c_void_p(stream)), "n3d_stream_capture_begin")
+    entry_capture_begin(stream)
 
 
 def stream_capture_end(stream):
     """-> executable graph handle (int)"""
     ex = C.c_void_p()
+    entry_capture_end(stream)      # signals that found no launch to ride in belong in the graph being closed
     check(_lib.load().n3d_stream_capture_end(C.c_void_p(stream), C.byref(ex)), "n3d_stream_capture_end")
     return ex.value
 
@@ -1500,8 +1568,18 @@ def step_counter(device):
 
 
 # ------------------------------------------------------------------------------------------ stream hand-off
-def sync_signal(flag_ptr, step_ptr, bump=False):
-    """publish *step to *flag behind everything on the current stream (include/n3d.h, "stream hand-off"); pointers are ints"""
+def sync_signal(flag_ptr, step_ptr, bump=False, entry=False):
+    """publish *step to *flag behind everything on the current stream (include/n3d.h, "stream hand-off"); pointers are ints.
+    entry: while the stream is being captured the signal may ride in the entry of the stream's next launch (see ENTRY_SIGNALS)"""
+    if entry and _entry_streams:
+        h = _launch_handle()
+        if h in _entry_streams:
+            q = _entry_pending.setdefault(h, [])
+            if len(q) >= 2:          # a kernel entry holds two
+                flush_entry_signals(h)
+                q = _entry_pending.setdefault(h, [])
+            q.append((flag_ptr, step_ptr, 1 if bump else 0))
+            return
     check(_lib.load().n3d_sync_signal(C.c_void_p(flag_ptr), C.c_void_p(step_ptr), 1 if bump else 0, stream_ptr()), "n3d_sync_signal")
 
 
@@ -1526,6 +1604,7 @@ def sync_wait2(flag0_ptr, flag1_ptr, step_ptr, timeouts_ptr, bump=False, max_pol
 
 def stamp(ptr_):
     """diagnostic: the current stream stores the 100 MHz wall clock to the device uint64 at `ptr_` when it gets there"""
+    flush_entry_signals(_launch_handle())      # a stamp next to a hand-off is taken behind the signal itself, as the timeline tools expect
     check(_lib.load().n3d_stamp(C.c_void_p(ptr_), stream_ptr()), "n3d_stamp")
 
 

@@ -481,7 +481,7 @@ class SideSchedule:
     def fork(self):
         """main stream: store a flag behind everything launched so far; returns its id"""
         i = self._flag()
-        K.sync_signal(self.ptr(8 + i), self.ptr(0), False)
+        K.sync_signal(self.ptr(8 + i), self.ptr(0), False, entry=True)     # (under capture: stored by the chain's next kernel as it starts)
         return i
 
     class _Side:
@@ -504,7 +504,7 @@ class SideSchedule:
     def side_signal(self):
         """inside side(): store a flag behind the side stream's launches so far; returns its id"""
         i = self._flag()
-        K.sync_signal(self.ptr(8 + i), self.ptr(2), False)
+        K.sync_signal(self.ptr(8 + i), self.ptr(2), False, entry=True)     # (usually rides in the wait kernel of the next side segment)
         if self.trace is not None:
             K.stamp(self.trace.data_ptr() + 8 * (2 * i + 2))      # (a join flag: the side stream stored it ...)
         self._side_tok = i
@@ -698,7 +698,7 @@ class SideSchedule:
         n = ctx.queued()
         if n > 0 and (final or (n >= self.min_queue and self._cuts < self.JOIN - 1)):
             i = self._flag()
-            K.sync_signal(self.ptr(8 + i), self.ptr(0), False)
+            K.sync_signal(self.ptr(8 + i), self.ptr(0), False, entry=True)
             self._main_jobs[i] = len(ctx.final)     # slab-reduction jobs the main chain has issued in front of this flag
             if self.trace is not None:
                 K.stamp(self.trace.data_ptr() + 8 * (2 * i + 2))
@@ -1217,7 +1217,13 @@ class _GraphTrainer:
             try:
                 with torch.cuda.stream(s):
                     g_main.capture_begin(pool=pool, capture_error_mode="thread_local")
-                    losses.append(run())
+                    K.entry_capture_begin(s.cuda_stream)      # hand-off signals ride in the entry of the chain's next kernel
+                    try:
+                        losses.append(run())
+                    except BaseException:
+                        K.entry_capture_abort(s.cuda_stream)  # (nothing is launched into a capture that has failed)
+                        raise
+                    K.entry_capture_end(s.cuda_stream)        # ... and what found none goes out before the graph is closed
                     g_main.capture_end()
                 sd.launch_side(redirect=True)
             finally:

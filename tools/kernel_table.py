@@ -26,12 +26,14 @@ PEAK_HBM_GBS = 8000.0
 # entry points that launch nothing (queries)
 HOST_ONLY = {"n3d_conv_workspace_bytes", "n3d_conv_stats_rows", "n3d_conv_pack_info", "n3d_stats_rows", "n3d_fused_max_rows", "n3d_bwd_small2_ok",
              "n3d_head_rows", "n3d_head_workspace_bytes", "n3d_dice_rows", "n3d_last_error", "n3d_version", "n3d_device_ok", "n3d_comm_available",
-             "n3d_dropout3d_uniform", "n3d_comm_unique_id", "n3d_comm_init", "n3d_comm_destroy"}
+             "n3d_dropout3d_uniform", "n3d_comm_unique_id", "n3d_comm_init", "n3d_comm_destroy", "n3d_entry_signal_pending",
+             "n3d_entry_signal_counts"}
 
 
 # entry points that are never replayed for timing: they change state the step depends on (weights and moments, the dropout
 # generator) or hold a stream until another stream acts (the device-side hand-off); their coarse per-call event time is reported
-NO_REPLAY = {"n3d_adam_step", "n3d_dropout3d_gate", "n3d_sync_wait", "n3d_sync_wait2", "n3d_sync_signal"}
+NO_REPLAY = {"n3d_adam_step", "n3d_dropout3d_gate", "n3d_sync_wait", "n3d_sync_wait2", "n3d_sync_signal", "n3d_entry_signal_arm",
+             "n3d_entry_signal_flush"}
 
 
 # coefficient / gate kernels: a few workgroups over statistics rows (kilobytes) -- no roofline applies, their time is launch latency
