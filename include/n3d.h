@@ -556,6 +556,27 @@ int n3d_stitch(const float* patches, int64_t sb, int64_t sc, int64_t sv, int C, 
                double* out, int FX, int FY, int FZ, int ox, int oy, int oz, void* stream);
 int n3d_tumor_labels(const double* pred, int64_t N, double threshold, int inclusive, uint8_t* out, void* stream);
 
+/* ---- the same stitch for a whole subject, chunk by chunk (prediction.py:64-170): no patch prediction outlives its chunk.
+ * Running buffers of the brain-wide box, zeroed by the caller per subject: sum float64 (C, X, Y, Z), cnt int32 (X, Y, Z).
+ * n3d_stitch_add adds one chunk: patches as n3d_stitch (nslots patches; NULL with nslots == 0); entries: DEVICE table of n records
+ * in list order.  A record is the descriptor its patch was GATHERED with (n3d_patch_desc: q[i] = x[s(i)]) and the patch's index in
+ * the tensor: the prediction of q is brought back onto x's grid here (the kernel solves s(i) = l for i; the host does not
+ * invert).  slot < 0 (or >= nslots): a patch the net never ran (all-zero input): it counts as covering and adds zeros, the reference's
+ * rule (prediction.py:133-135).  lo / hi: HOST int32[3] each, the bounding box [lo, hi) of the chunk's patches on the brain-wide
+ * grid (may hang over; clipped here): the launch covers that box only, so the cost follows the chunk; a record outside it is
+ * not added.  Every voxel adds its covering records one by one in table order in fp64, no atomics: chunk after chunk this is bit
+ * for bit the list-order sum of n3d_stitch.  1 <= C <= 4.
+ * n3d_stitch_finish: ONE pass over the full image (FX, FY, FZ) with the box at (ox, oy, oz).  mean = sum / max(cnt, 1).  probs
+ * (float64 (C, FX, FY, FZ)) and labels (uint8 (FX, FY, FZ); C == 3) may each be NULL (not both): probs takes the mean, labels
+ * the fusion of n3d_tumor_labels on that mean; with mask_vol -- the subject's (Cv, X, Y, Z) fp32 box -- the label is 0 where
+ * every channel is zero ("zero" as n3d_volume_sat: prediction.py:83-96, tumor_pred *= skull_mask).  Outside the box both are 0:
+ * every voxel of an output is written exactly once, so the outputs need no clearing. */
+typedef struct n3d_stitch_entry { n3d_patch_desc d; int32_t slot; } n3d_stitch_entry;
+int n3d_stitch_add(const float* patches, int64_t sb, int64_t sc, int64_t sv, int C, int P, int nslots, const n3d_stitch_entry* entries, int n,
+                   const int32_t* lo, const int32_t* hi, int X, int Y, int Z, double* sum, int32_t* cnt, void* stream);
+int n3d_stitch_finish(const double* sum, const int32_t* cnt, int C, int X, int Y, int Z, double* probs, uint8_t* labels, double threshold,
+                      int inclusive, const float* mask_vol, int Cv, int FX, int FY, int FZ, int ox, int oy, int oz, void* stream);
+
 /* ---- RCCL exchange step of data-parallel training (no reference counterpart: config.yml:54 `multi_gpus` is never read;
  * SURVEY 8(e)).  One process per GPU; the hot path's only exchange is a SUM all-reduce of the flat fp32 gradient buffer, in
  * place, stream-ordered on `stream` (a side HIP stream lets it run under the backward kernels of the next bucket).

@@ -105,6 +105,11 @@ class GatherDesc(C.Structure):
     _fields_ = [("d", PatchDesc), ("vol", C.c_int32)]
 
 
+class StitchEntry(C.Structure):
+    """n3d_stitch_entry (include/n3d.h)"""
+    _fields_ = [("d", PatchDesc), ("slot", C.c_int32)]
+
+
 class PatchVolume(C.Structure):
     """n3d_patch_volume (include/n3d.h)"""
     _fields_ = [("data", C.c_void_p), ("truth", C.c_void_p), ("sat", C.c_void_p), ("dims", C.c_int32 * 3), ("pad_", C.c_int32)]
@@ -211,6 +216,8 @@ PROTOTYPES = {
     "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_stitch": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "n3d_tumor_labels": (_i, [_p, _i64, C.c_double, _i, _p, _p]),
+    "n3d_stitch_add": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, _p, _p, _p]),
+    "n3d_stitch_finish": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, C.c_double, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "n3d_comm_available": (_i, []),
     "n3d_comm_unique_id": (_i, [_p]),
     "n3d_comm_init": (_i, [_p, _i, _i, C.POINTER(C.c_void_p)]),

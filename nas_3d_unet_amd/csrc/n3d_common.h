@@ -145,6 +145,9 @@ __device__ __forceinline__ void entry_signal(const EntrySignal& e) {
     n3d::entry_flush();                                                                           \
     kernel_<<<(grid_), (block_), (shmem_), (stream_)>>>(__VA_ARGS__);                             \
   } while (0)
+// "zero" of the data step and the step after it (n3d_volume_sat, the skull mask of n3d_stitch_finish): numpy's `== 0` on fp32 -- +-0 is
+// zero, NaN / inf / denormals are not (on the bit pattern: a denormal flush cannot change it)
+__device__ __forceinline__ int nonzero_f32(float f) { return (__float_as_uint(f) & 0x7fffffffu) != 0; }
 // Kernels of the dependent chain raise their waves' issue priority (s_setprio 0..3, 0 = the reset value): the weight-gradient
 // kernels, which only ever run beside the chain on the side streams, stay at 0, so where both have waves on a SIMD the chain's
 // instructions go first.  No effect when a kernel has the chip to itself.

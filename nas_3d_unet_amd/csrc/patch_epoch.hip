@@ -7,9 +7,6 @@
 
 namespace n3d {
 
-// numpy's `== 0` on fp32: +-0 is zero, NaN / inf / denormals are not (on the bit pattern: a denormal flush cannot change it)
-__device__ __forceinline__ int nonzero_f32(float f) { return (__float_as_uint(f) & 0x7fffffffu) != 0; }
-
 // z pass, fused with the indicator test: one wave per (x', y') line of the padded table (X+1, Y+1, Z+1); the plane x' = 0 and
 // the row y' = 0 are zeros, entry z' = 0 of every line too.  Lanes along z (coalesced loads of the planar volume); a 64-voxel
 // chunk is scanned in the wave with both counts packed in one word (a chunk adds at most 64 per count), then carried on.

@@ -56,6 +56,14 @@ def isometry_of_key(key):
     return [s[0] for s in src], [bool(s[1]) for s in src]
 
 
+def inverse_isometry(perm, flip):
+    """(perm, flip) of the isometry that undoes isometry_of_key's: with q[i] = x[s(i)], s_a = i[perm[a]] or P-1-i[perm[a]], the
+    array x is q read at i_b = s[inv_perm[b]] or P-1-s[inv_perm[b]] (inv_flip[b]).  This is what n3d_stitch_add solves per
+    voxel; on the host it is the tests' and tools' way to build an expectation."""
+    inv_perm = [list(perm).index(b) for b in range(3)]
+    return inv_perm, [bool(flip[a]) for a in inv_perm]
+
+
 def patch_batch(vol, truth, corners, keys, patch, inclusive_label=True, target_dtype=torch.float32, out=None):
     """vol: (Cv, X, Y, Z) fp32 device tensor; truth: (X, Y, Z) or (1, X, Y, Z) uint8 device tensor or None;
     corners: B patch corners (may lie outside the volume: zero padding); keys: B isometry keys (None = identity).

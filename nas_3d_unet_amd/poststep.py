@@ -4,11 +4,13 @@ sigmoid channels into a label volume -- on the device, from the layout the net p
 as in prediction.py:132-138).  Host logic here: argument plumbing only."""
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _lib
 from . import kernels as K
-from ._lib import N3DError, check
+from ._lib import N3DError, PatchDesc, StitchEntry, check
 
 
 def stitch(patches, corners, box_shape, full_shape=None, origin=(0, 0, 0)):
@@ -45,3 +47,81 @@ def tumor_labels(pred, threshold=0.5, inclusive_label=False):
     check(_lib.load().n3d_tumor_labels(K.ptr(pred), out.numel(), float(threshold), 1 if inclusive_label else 0, K.ptr(out), K.stream_ptr()),
           "n3d_tumor_labels")
     return out
+
+
+# ---- the same stitch for a whole subject, chunk by chunk (predict.SubjectPredictor): running buffers instead of a patch list
+IDENTITY = ([0, 1, 2], [False, False, False])
+
+
+def entry_table(entries, device):
+    """entries: [(corner, (perm, flip) the patch was gathered with, slot)] in list order -> the device table n3d_stitch_add reads
+    (n3d_stitch_entry records as bytes; one host -> device copy).  slot: the patch's index in the tensor; < 0: a dead patch."""
+    recs = (StitchEntry * max(len(entries), 1))()
+    for i, (corner, (perm, flip), slot) in enumerate(entries):
+        if sorted(int(a) for a in perm) != [0, 1, 2]:
+            raise N3DError("stitch entries: perm must be a permutation of (0, 1, 2), got %s" % (list(perm),))
+        recs[i] = StitchEntry(PatchDesc((C.c_int32 * 3)(*[int(c) for c in corner]), (C.c_int32 * 3)(*[int(a) for a in perm]),
+                                        (C.c_int32 * 3)(*[int(bool(f)) for f in flip])), int(slot))
+    return torch.frombuffer(bytearray(recs), dtype=torch.uint8).to(device)
+
+
+def stitch_buffers(channels, box_shape, device):
+    """the zeroed running buffers of one subject: (sum float64 (C, X, Y, Z), cnt int32 (X, Y, Z))"""
+    X, Y, Z = (int(v) for v in box_shape)
+    return (torch.zeros((int(channels), X, Y, Z), dtype=torch.float64, device=device),
+            torch.zeros((X, Y, Z), dtype=torch.int32, device=device))
+
+
+def _running(sum_, cnt):
+    if not (isinstance(sum_, torch.Tensor) and sum_.is_cuda and sum_.dtype == torch.float64 and sum_.dim() == 4 and sum_.is_contiguous()
+            and isinstance(cnt, torch.Tensor) and cnt.device == sum_.device and cnt.dtype == torch.int32 and cnt.is_contiguous()
+            and tuple(cnt.shape) == tuple(sum_.shape[1:])):
+        raise N3DError("stitch: running buffers are a contiguous float64 (C, X, Y, Z) sum and int32 (X, Y, Z) count on one HIP device")
+    return tuple(int(v) for v in sum_.shape)
+
+
+def stitch_add(patches, table, first, count, lo, hi, sum_, cnt):
+    """add the records [first, first + count) of an entry_table to the running buffers (n3d_stitch_add).  patches: the chunk's
+    (B, C, P, P, P) fp32 predictions in any layout the ops produce, or (None, P) when every record of the range is dead; lo / hi:
+    the bounding box [lo, hi) of those records' patches on the brain-wide grid (the launch covers it, clipped to the box)."""
+    Cc, X, Y, Z = _running(sum_, cnt)
+    es = C.sizeof(StitchEntry)
+    if not (isinstance(table, torch.Tensor) and table.dtype == torch.uint8 and table.device == sum_.device and table.is_contiguous()
+            and first >= 0 and count >= 1 and (first + count) * es <= table.numel()):
+        raise N3DError("stitch_add: records [%d, %d) are not in the entry table" % (first, first + count))
+    if isinstance(patches, tuple):
+        pp, (sb, sc, sv), B, P = None, (0, 0, 0), 0, int(patches[1])
+    else:
+        if not (isinstance(patches, torch.Tensor) and patches.device == sum_.device and patches.dtype == torch.float32 and patches.dim() == 5
+                and patches.shape[1] == Cc and patches.shape[2] == patches.shape[3] == patches.shape[4]):
+            raise N3DError("stitch_add: patches must be a (B, %d, P, P, P) fp32 tensor on the buffers' device" % Cc)
+        st = K._bcv_strides(patches)
+        if st is None:
+            patches = patches.contiguous()
+            st = K._bcv_strides(patches)
+        pp, (sb, sc, sv), B, P = K.ptr(patches), st, int(patches.shape[0]), int(patches.shape[2])
+    check(_lib.load().n3d_stitch_add(pp, sb, sc, sv, Cc, P, B, table.data_ptr() + first * es, int(count), (C.c_int32 * 3)(*[int(v) for v in lo]),
+                                     (C.c_int32 * 3)(*[int(v) for v in hi]), X, Y, Z, K.ptr(sum_), K.ptr(cnt), K.stream_ptr()), "n3d_stitch_add")
+
+
+def stitch_finish(sum_, cnt, full_shape=None, origin=(0, 0, 0), want_probs=True, want_labels=True, threshold=0.5, inclusive_label=False,
+                  mask_vol=None):
+    """one pass over the full image (n3d_stitch_finish) -> (labels uint8 (FX, FY, FZ) or None, probs float64 (C, FX, FY, FZ) or
+    None): the mean sum / max(cnt, 1) of the box placed at `origin`, and / or tumor_labels of that mean; mask_vol: the subject's
+    (Cv, X, Y, Z) fp32 box -- labels are 0 where all of its channels are (the skull mask, prediction.py:83-96)."""
+    Cc, X, Y, Z = _running(sum_, cnt)
+    if not (want_probs or want_labels):
+        raise N3DError("stitch_finish: neither probabilities nor labels asked for")
+    FX, FY, FZ = (int(v) for v in (full_shape if full_shape is not None else (X, Y, Z)))
+    Cv = 0
+    if mask_vol is not None:
+        if not (isinstance(mask_vol, torch.Tensor) and mask_vol.device == sum_.device and mask_vol.dtype == torch.float32 and mask_vol.dim() == 4
+                and mask_vol.is_contiguous() and tuple(mask_vol.shape[1:]) == (X, Y, Z)):
+            raise N3DError("stitch_finish: mask_vol must be the subject's contiguous (Cv, %d, %d, %d) fp32 box on the buffers' device" % (X, Y, Z))
+        Cv = int(mask_vol.shape[0])
+    probs = torch.empty((Cc, FX, FY, FZ), dtype=torch.float64, device=sum_.device) if want_probs else None
+    labels = torch.empty((FX, FY, FZ), dtype=torch.uint8, device=sum_.device) if want_labels else None
+    check(_lib.load().n3d_stitch_finish(K.ptr(sum_), K.ptr(cnt), Cc, X, Y, Z, K.ptr(probs), K.ptr(labels), float(threshold),
+                                        1 if inclusive_label else 0, K.ptr(mask_vol), Cv, FX, FY, FZ, int(origin[0]), int(origin[1]),
+                                        int(origin[2]), K.stream_ptr()), "n3d_stitch_finish")
+    return labels, probs

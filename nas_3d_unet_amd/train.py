@@ -1317,6 +1317,15 @@ class Trainer(_GraphTrainer):
             self.sync.ranges = [r for _, r in self._buckets]
         self.sync.broadcast(self.fp.flat)
 
+    # -- subject-level inference -------------------------------------------------------------------
+    def predictor(self, patch=64, batch=8):
+        """a predict.SubjectPredictor (prediction.py:64-170 on the device) on the module this trainer's step trains -- its padded
+        twin, its storage configuration -- behind a host-visible point (check_sync()).  Its captured forward packs the weights
+        inside the graph, so a predictor made once goes on predicting with the weights as later steps leave them."""
+        from .predict import SubjectPredictor
+        self.check_sync()
+        return SubjectPredictor(self.model, patch, batch, graph=self.use_graph, _net=self.net, _padded=self._twin is not None)
+
     # -- bucket plan ------------------------------------------------------------------------------
     def _bucket_plan(self):
         """[(cell index whose backward completes the bucket (-1 = the stems, i.e. the end), (begin, end) flat range)] in issue
