@@ -414,7 +414,9 @@ int n3d_node_fwd_coeffs(const n3d_gn_fwd_term* gn, int n_gn, const n3d_se_term* 
 int n3d_node_bwd_coeffs(const n3d_gn_bwd_term* gn, int n_gn, const n3d_se_term* se, int n_se, int B, int C, int G, int64_t N, void* stream);
 
 
-/* ---- 2x2x2 pooling, stride 2 (prim_ops.py:160-163) ------------------------------------------------ */
+/* ---- 2x2x2 pooling, stride 2 (prim_ops.py:160-163) ------------------------------------------------
+ * Every entry returns N3D_ERR_INVALID for an odd spatial dimension.  Max pooling is torch's bit for bit: the FIRST maximum of a
+ * window in (d, h, w) order is the output (so -0.0 in front of +0.0 stays -0.0), it takes the whole gradient, and a NaN wins. */
 int n3d_pool2_fwd(const float* x, int64_t xld, float* y, int64_t yld, int B, int Di, int Hi, int Wi, int C,
                   int flags, void* stream);
 int n3d_pool2_bwd(const float* dy, int64_t dyld, const float* x, int64_t xld, float* dx, int64_t dxld, int B,

@@ -1984,6 +1984,10 @@ __global__ __launch_bounds__(512) void node_bwd_coeffs_kernel(NodeCoefArgs qs, i
 // ------------------------------------------------------------------------------------------------
 // pooling 2x2x2 / 2
 // ------------------------------------------------------------------------------------------------
+// running maximum of a 2x2x2 window: the FIRST maximum in (d, h, w) scan order stays and a NaN takes over -- the element the backward
+// kernels below route the gradient to, and torch's max_pool3d bit for bit (fmaxf turns a window of -0.0, +0.0 into +0.0 and drops NaNs)
+__device__ __forceinline__ float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
+
 template <bool MAX, typename T = float>
 __global__ __launch_bounds__(256) void pool2_fwd_kernel(const T* __restrict__ x, int64_t xld, T* __restrict__ y, int64_t yld, int Di,
                                                         int Hi, int Wi, int C) { N3D_CHAIN_PRIO();
@@ -2008,7 +2012,7 @@ __global__ __launch_bounds__(256) void pool2_fwd_kernel(const T* __restrict__ x,
       for (int kw = 0; kw < 2; ++kw) {
         const int64_t vi = ((int64_t)(2 * d_o + kd) * Hi + (2 * ho + kh)) * Wi + (2 * wo + kw);
         const float4 q = ld4(xb + vi * xld);
-        if (MAX) { acc.x = fmaxf(acc.x, q.x); acc.y = fmaxf(acc.y, q.y); acc.z = fmaxf(acc.z, q.z); acc.w = fmaxf(acc.w, q.w); }
+        if (MAX) { acc.x = pool_max(acc.x, q.x); acc.y = pool_max(acc.y, q.y); acc.z = pool_max(acc.z, q.z); acc.w = pool_max(acc.w, q.w); }
         else { acc.x += q.x; acc.y += q.y; acc.z += q.z; acc.w += q.w; }
       }
   if (!MAX) { acc.x *= 0.125f; acc.y *= 0.125f; acc.z *= 0.125f; acc.w *= 0.125f; }
@@ -2041,7 +2045,7 @@ __global__ __launch_bounds__(256) void pool2_fwd_both_kernel(const float* __rest
 #pragma unroll
   for (int k = 0; k < 8; ++k) {   // same summation / comparison order as the two single kernels
     sa.x += q[k].x; sa.y += q[k].y; sa.z += q[k].z; sa.w += q[k].w;
-    sm.x = fmaxf(sm.x, q[k].x); sm.y = fmaxf(sm.y, q[k].y); sm.z = fmaxf(sm.z, q[k].z); sm.w = fmaxf(sm.w, q[k].w);
+    sm.x = pool_max(sm.x, q[k].x); sm.y = pool_max(sm.y, q[k].y); sm.z = pool_max(sm.z, q[k].z); sm.w = pool_max(sm.w, q[k].w);
   }
   sa.x *= 0.125f; sa.y *= 0.125f; sa.z *= 0.125f; sa.w *= 0.125f;
   const int64_t vo = (int64_t)b * Do * Ho * Wo + ((int64_t)d_o * Ho + ho) * Wo + wo;
@@ -3056,7 +3060,7 @@ int n3d_pool2_bwd(const float* dy, int64_t dyld, const float* x, int64_t xld, fl
 int n3d_pool2_bwd_scaled(const float* dy, int64_t dyld, const float* x, int64_t xld, float* dx, int64_t dxld, int B, int Di, int Hi, int Wi,
                          int C, int flags, const float* wptr, void* stream) {
   const bool mx = flags & N3D_POOL_MAX, acc = flags & N3D_ACCUMULATE, bf = flags & N3D_ACT_BF16;
-  N3D_CHECK_ARG(dy && dx && (!mx || x), "pool2_bwd: bad args");
+  N3D_CHECK_ARG(dy && dx && (!mx || x) && Di % 2 == 0 && Hi % 2 == 0 && Wi % 2 == 0, "pool2_bwd: bad args / odd spatial dims");
   if (int e = check_vec(dy, dyld, C, "pool2_bwd(dy)", bf)) return e;
   if (int e = check_vec(dx, dxld, C, "pool2_bwd(dx)", bf)) return e;
   if (mx) if (int e = check_vec(x, xld, C, "pool2_bwd(x)", bf)) return e;
