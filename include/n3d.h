@@ -62,6 +62,12 @@ extern "C" {
  * fp32 (v_mfma_f32_16x16x16_bf16 instead of four v_mfma_f32_16x16x4_f32).  Ignored by every other kernel.  Never set by the fp32
  * configuration, whose arithmetic is exact fp32. */
 #define N3D_MM_BF16 256
+/* Small pointwise convs (1x1x1, fp32, channel counts and pitches multiples of 4, 16-byte aligned rows, no node-planar operand:
+ * forward at stride 1 or 2, data gradient at stride 1, data gradient at stride 2 without bias and statistics) that neither the MFMA
+ * family nor the 1x1x1 streaming kernel takes run on an LDS-weight kernel (conv_point_kernel) that performs the generic gather
+ * kernel's fp32 operations in its order: results and statistics rows are the same bit for bit.  This flag sends such a call down
+ * the gather path it used to take (A/B timing, bit comparison), like N3D_NO_MFMA for the MFMA family. */
+#define N3D_NO_POINTWISE 512
 
 /* storage type of an activation tensor (entry points that take a dtype argument; all others are fp32) */
 #define N3D_F32 0
@@ -200,6 +206,8 @@ typedef struct n3d_conv_fwd_call {     /* arguments of n3d_conv_fwd / n3d_convT_
   const float* x; int64_t xld; const float* w; const float* bias; float* y; int64_t yld;
   const float* in_gate; double* stats; void* ws; size_t ws_bytes;
 } n3d_conv_fwd_call;
+/* Two small pointwise convs (N3D_NO_POINTWISE above; plain convs, distinct outputs) that do not fold as an MFMA pair also share ONE
+ * launch: the pointwise kernel takes two jobs.  With one such call of the two, that one runs on the pointwise kernel alone. */
 int n3d_conv_fwd2(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1, void* stream);
 /* the same for up to four calls (`calls` = array): the plain-conv primitives of a supernet node (cell.py:76-81).  One launch when
  * all are small MFMA problems of one K-split plan, or all one-plane-tile 3x3x3 convs of one channel count in {4, 8} (stride 1 or 2,
@@ -230,6 +238,10 @@ int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
  * the reference runs loss.backward() through every conv's input there): fields x, dw, dbias, in_gate, ws_weight, deferred and
  * flags_weight of the calls are ignored.  One launch where both fit the small-tensor MFMA kernel and dx of c0 != dx of c1. */
 int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream);
+/* (two small pointwise data gradients with dx of c0 != dx of c1 fold the same way as in n3d_conv_fwd2: one two-job launch)
+ * n3d_conv_pointwise_counts: launches of the pointwise kernel / jobs they carried since the library was loaded (a two-job launch
+ * counts 1 / 2): lets a test see which path a call took. */
+int n3d_conv_pointwise_counts(int64_t* launches, int64_t* jobs);
 /* transposed convolution y[i side] = convT(x[o side]) + bias; same kernels with the roles swapped */
 int n3d_convT_fwd(const n3d_conv_geom* g, const float* x, int64_t xld, const float* w, const float* bias,
                   float* y, int64_t yld, int flags, const float* in_gate, double* stats,

@@ -143,6 +143,7 @@ PROTOTYPES = {
     "n3d_conv_fwdN": (_i, [C.POINTER(ConvFwdCall), _i, _p]),
     "n3d_conv_bwd_both2": (_i, [C.POINTER(ConvBwdCall), C.POINTER(ConvBwdCall), _p]),
     "n3d_conv_bwd_data2": (_i, [C.POINTER(ConvBwdCall), C.POINTER(ConvBwdCall), _p]),
+    "n3d_conv_pointwise_counts": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "n3d_convT_bwd_both": (_i, [_gp, _p, _i64, _p, _i64, _p, _p, _i64, _i, _p, _sz, _p, _i, _p, _sz, C.POINTER(FinalJob), _p]),
     "n3d_conv_bwd_both": (_i, [_gp, _p, _i64, _p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _p, _sz, _p, _p, _i, _p, _p, _sz,
                                 C.POINTER(FinalJob), _p]),
@@ -250,6 +251,7 @@ RELU_IN, RELU, ACCUMULATE, POOL_MAX, NO_MFMA, PREPACKED = 1, 2, 4, 8, 16, 32
 F32, BF16, U8 = 0, 1, 2   # N3D_F32 / N3D_BF16 / N3D_U8 (byte targets of the head passes and of the data step)
 PATCH_INCLUSIVE, PATCH_T_U8 = 1, 2   # n3d_patch_batch flags
 SRC_BF16, DST_BF16, ACT_BF16 = 64, 128, 64   # storage flags of the conv / epilogue families
+NO_POINTWISE = 512   # conv family: small pointwise convs take the generic gather kernel instead of conv_point_kernel (A/B, bit comparison)
 MM_BF16 = 256   # conv family, bf16 configuration: the C >= 16 MFMA kernels round their operands to bf16 (fp32 storage, fp32 accumulate)
 
 _lib = None

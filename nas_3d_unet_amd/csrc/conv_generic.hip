@@ -8,6 +8,7 @@
 #include "n3d_common.h"
 #define N3D_WG16_SLABS 1024   // 256-float partial slabs reserved for the gemm16 weight-gradient kernels (+ one per tile)
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 namespace n3d {
@@ -356,6 +357,257 @@ static void launch_gather(const GatherArgs& a, int B, hipStream_t s) {
   else if (sb) launch_gather_d<bf16_t, float>(a, B, s);
   else if (db) launch_gather_d<float, bf16_t>(a, B, s);
   else launch_gather_d<float, float>(a, B, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pointwise (1x1x1) fp32 convs neither the gemm16 family (it needs channel counts that are multiples of 16) nor the streaming
+// kernel below (>= 32768 voxels, narrow tiles) takes, at any voxel count (point_job has the full list of conditions): in the
+// benchmarked nets the cells' 12/24/48-channel preprocess convs and their data gradients.  The work mapping is the gather kernel's (256 consecutive destination voxels x CO_T channels x one sample, one
+// statistics row per voxel block) and so is every fp32 operation and its order, so results and statistics rows are the gather
+// kernel's bit for bit; what differs is where the time of these launches goes, which is latency, not work:
+//   * the [Cs][CO_T] weight tile is staged in LDS once and read back with broadcast ds_read_b128 (the gather kernel's Cs > 12
+//     path reads its weights as uniform global loads inside the channel loop);
+//   * everything a voxel needs -- source quads, ReLU-mask quads, the destination's previous value -- is requested before the
+//     first use, behind the weight loads, so a thread pays about one memory latency instead of three or four;
+//   * CO_T is chosen for workgroups, not for reuse (point_cot);
+//   * a launch takes up to two jobs (blockIdx.z = (job, sample)): a cell's two preprocess convs share one launch.
+// ------------------------------------------------------------------------------------------------
+struct PointJob {
+  const float* src; int64_t sld; float* dst; int64_t dld; const float* wp; const float* bias; const float* in_gate;
+  const float* relu_src; int64_t rld; const float* out_gate; double* stats;
+  int64_t Nd, Ns;
+  int Cs, Cd, Cdp, flags, sn, den, Hs, Ws, nblk, ncot;
+  FastDiv fWd, fHd;
+};
+struct PointArgs { PointJob j[2]; int B0; };   // blockIdx.z < B0: job 0, sample blockIdx.z; else job 1, sample blockIdx.z - B0
+
+// BQ: source quads requested per batch (one batch when Cs <= 4 * BQ); XIN: the source carries N3D_RELU_IN and / or an input gate
+template <int CO_T, int BQ, bool XIN>
+__global__ __launch_bounds__(256) void conv_point_kernel(PointArgs a, EntrySignal es) {
+  entry_signal(es);      // in front of the early return below
+  N3D_CHAIN_PRIO();
+  static_assert(CO_T % 4 == 0, "conv_point_kernel: CO_T must be a multiple of 4");
+  constexpr int CQ = CO_T / 4;
+  __shared__ double red[4][CO_T * 2];
+  extern __shared__ __attribute__((aligned(16))) float wlds[];     // [Cs][CO_T] weights, then [Cs] input gate (XIN)
+  PointJob j;
+  int b = blockIdx.z;
+  if (b < a.B0) j = a.j[0]; else { j = a.j[1]; b -= a.B0; }
+  if ((int)blockIdx.x >= j.nblk || (int)blockIdx.y >= j.ncot) return;   // the grid is the larger job's
+  const int c0 = blockIdx.y * CO_T, nq = j.Cs >> 2;
+  // ---- requests: weights first (the LDS stores wait for them alone), then the voxel's operands
+  const int ntile4 = j.Cs * CQ;
+  float4 wv[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = min((int)threadIdx.x + u * 256, ntile4 - 1);
+    wv[u] = ld4(j.wp + (int64_t)(i / CQ) * j.Cdp + c0 + (i % CQ) * 4);
+  }
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = v < j.Nd;
+  const uint32_t vv = valid ? (uint32_t)v : 0u;
+  bool ok = valid;         // a source voxel reaches this destination voxel
+  int64_t si = vv;
+  if (j.sn != 1 || j.den != 1) {
+    uint32_t qw, w_, d_, h_;
+    j.fWd.divmod(vv, qw, w_);
+    j.fHd.divmod(qw, d_, h_);
+    if (j.den == 2) {      // data gradient of a stride-2 conv: even destination coordinates take source (d/2, h/2, w/2), the others nothing
+      ok = ok && !((d_ | h_ | w_) & 1);
+      d_ >>= 1; h_ >>= 1; w_ >>= 1;
+    } else { d_ *= j.sn; h_ *= j.sn; w_ *= j.sn; }
+    si = ((int64_t)d_ * j.Hs + h_) * j.Ws + w_;
+  }
+  const float* xs = j.src + ((int64_t)b * j.Ns + si) * j.sld;
+  float4 xq[BQ];
+#pragma unroll
+  for (int u = 0; u < BQ; ++u) xq[u] = ld4(xs + 4 * min(u, nq - 1));
+  const bool accum = j.flags & N3D_ACCUMULATE;
+  float4 rs[CQ], prev[CQ];
+  float* o = j.dst + ((int64_t)b * j.Nd + vv) * j.dld + c0;
+  if (j.relu_src) {
+    const float* r = j.relu_src + ((int64_t)b * j.Nd + vv) * j.rld + c0;
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) rs[q] = ld4(r + 4 * q);
+  }
+  if (accum) {
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) prev[q] = ld4(o + 4 * q);
+  }
+  float acc[CO_T];
+#pragma unroll
+  for (int e = 0; e < CO_T; ++e) acc[e] = j.bias ? j.bias[c0 + e] : 0.f;
+  // ---- weight tile (and input gate) into LDS
+  float4* wl4 = reinterpret_cast<float4*>(wlds);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = (int)threadIdx.x + u * 256;
+    if (i < ntile4) wl4[i] = wv[u];
+  }
+  for (int i0 = (int)threadIdx.x + 1024; i0 < ntile4; i0 += 256)      // wide sources (Cs * CO_T > 4096)
+    wl4[i0] = ld4(j.wp + (int64_t)(i0 / CQ) * j.Cdp + c0 + (i0 % CQ) * 4);
+  const bool relu_in = j.flags & N3D_RELU_IN;
+  if (XIN) {
+    float* gl = wlds + j.Cs * CO_T;
+    for (int c = threadIdx.x; c < j.Cs; c += 256) gl[c] = j.in_gate ? j.in_gate[(int64_t)b * j.Cs + c] : 1.f;
+  }
+  __syncthreads();
+  // ---- acc = fmaf(x', w[c][co], acc), c ascending
+  const float4* gl4 = reinterpret_cast<const float4*>(wlds + j.Cs * CO_T);
+  for (int q0 = 0;;) {
+#pragma unroll
+    for (int u = 0; u < BQ; ++u) {
+      const int q = q0 + u;
+      if (q < nq) {
+        float xv[4] = {xq[u].x, xq[u].y, xq[u].z, xq[u].w};
+        if (XIN) {
+          const float4 g4 = gl4[q];       // 1.0f without a gate: x * 1.0f == x
+          const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) xv[e] = (relu_in ? fmaxf(xv[e], 0.f) : xv[e]) * gv[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float4* wrow = wl4 + (q * 4 + e) * CQ;
+#pragma unroll
+          for (int c4 = 0; c4 < CQ; ++c4) {
+            const float4 w4 = wrow[c4];
+            acc[c4 * 4 + 0] = fmaf(xv[e], w4.x, acc[c4 * 4 + 0]);
+            acc[c4 * 4 + 1] = fmaf(xv[e], w4.y, acc[c4 * 4 + 1]);
+            acc[c4 * 4 + 2] = fmaf(xv[e], w4.z, acc[c4 * 4 + 2]);
+            acc[c4 * 4 + 3] = fmaf(xv[e], w4.w, acc[c4 * 4 + 3]);
+          }
+        }
+      }
+    }
+    q0 += BQ;
+    if (q0 >= nq) break;
+#pragma unroll
+    for (int u = 0; u < BQ; ++u) xq[u] = ld4(xs + 4 * min(q0 + u, nq - 1));
+  }
+  // ---- epilogue: the gather kernel's, operation by operation.  (The library is built with -ffp-contract=fast: the gate multiply and the
+  // accumulate add below stay two roundings in both kernels because each sits behind its own uniform branch; the "extras" cases of
+  // tests/test_gpu_pointwise.py compare exactly this form bit for bit.)
+  if (j.den == 2) {
+#pragma unroll
+    for (int e = 0; e < CO_T; ++e) acc[e] = ok ? acc[e] : 0.f;      // no source voxel: the gather kernel's untouched accumulator (no bias here)
+  }
+  if (j.relu_src) {
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) {
+      const float m[4] = {rs[q].x, rs[q].y, rs[q].z, rs[q].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (!(m[e] > 0.f)) acc[q * 4 + e] = 0.f;
+    }
+  }
+  if (j.out_gate) {
+#pragma unroll
+    for (int e = 0; e < CO_T; ++e) acc[e] *= j.out_gate[(int64_t)b * j.Cd + c0 + e];
+  }
+  if (accum) {
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) {
+      acc[q * 4 + 0] += prev[q].x; acc[q * 4 + 1] += prev[q].y; acc[q * 4 + 2] += prev[q].z; acc[q * 4 + 3] += prev[q].w;
+    }
+  }
+  if (valid) {
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) st4(o + 4 * q, make_float4(acc[q * 4], acc[q * 4 + 1], acc[q * 4 + 2], acc[q * 4 + 3]));
+  }
+  if (j.stats) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int sel = classsum4_sel(lane);
+#pragma unroll
+    for (int q = 0; q < CO_T; q += 4) {
+      float sv[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sv[e] = valid ? acc[q + e] : 0.f;
+      const float s = wave_classsum4_f<1>(sv[0], sv[1], sv[2], sv[3]);
+      const float ss = wave_classsum4_f<1>(sv[0] * sv[0], sv[1] * sv[1], sv[2] * sv[2], sv[3] * sv[3]);
+      if ((lane & 15) == 0) { red[wave][(q + sel) * 2] = (double)s; red[wave][(q + sel) * 2 + 1] = (double)ss; }
+    }
+    __syncthreads();
+    if (threadIdx.x < CO_T * 2) {
+      const double s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+      j.stats[(((int64_t)b * j.nblk + blockIdx.x) * j.Cd + c0 + (threadIdx.x >> 1)) * 2 + (threadIdx.x & 1)] = s;
+    }
+  }
+}
+
+constexpr size_t POINT_LDS_MAX = 48 * 1024;    // weight tile + input gate
+static std::atomic<int64_t> g_point_launches{0}, g_point_jobs{0};    // n3d_conv_pointwise_counts
+
+// output channels per workgroup: the largest of {16, 8, 4} that divides Cd and still gives the launch `POINT_MIN_WG` workgroups,
+// else the one with the most workgroups -- these launches are a few MFLOP, so a thread's serial FMA chain and the number of
+// compute units that share the loads decide, not the reuse of a source voxel (DESIGN.md section 4 has the measurement)
+constexpr int64_t POINT_MIN_WG = 256;
+static int point_cot(int Cd, int Cs, int64_t blocks) {
+  for (int t = 16; t > 4; t >>= 1)
+    if (Cd % t == 0 && blocks * (Cd / t) >= POINT_MIN_WG && (size_t)Cs * (t + 1) * 4 <= POINT_LDS_MAX) return t;
+  return 4;
+}
+
+template <int CO_T, int BQ>
+static void launch_point_x(const PointArgs& a, bool xin, dim3 grid, size_t shm, hipStream_t s) {
+  const EntrySignal es = entry_take(s);
+  if (xin) N3D_LAUNCH((conv_point_kernel<CO_T, BQ, true>), grid, dim3(256), shm, s, a, es);
+  else N3D_LAUNCH((conv_point_kernel<CO_T, BQ, false>), grid, dim3(256), shm, s, a, es);
+}
+template <int CO_T>
+static void launch_point_t(const PointArgs& a, int nq, bool xin, dim3 grid, size_t shm, hipStream_t s) {
+  if (nq <= 4) launch_point_x<CO_T, 4>(a, xin, grid, shm, s);
+  else if (nq <= 8) launch_point_x<CO_T, 8>(a, xin, grid, shm, s);
+  else launch_point_x<CO_T, 12>(a, xin, grid, shm, s);
+}
+
+// one launch for one job (j1 == nullptr) or two; B0 / B1: their batch sizes
+static void launch_point(PointJob* j0, int B0, PointJob* j1, int B1, hipStream_t s) {
+  PointArgs a;
+  a.j[0] = *j0; a.j[1] = j1 ? *j1 : *j0; a.B0 = B0;
+  const int n = j1 ? 2 : 1;
+  int cot = 16, nq = 0; bool xin = false; unsigned gx = 0, gy = 0; size_t shm = 0;
+  for (int i = 0; i < n; ++i) cot = std::min(cot, point_cot(a.j[i].Cd, a.j[i].Cs, a.j[i].nblk * (int64_t)(i ? B1 : B0)));
+  for (int i = 0; i < n; ++i) if (a.j[i].Cd % cot) cot = 4;
+  for (int i = 0; i < n; ++i) {
+    PointJob& j = a.j[i];
+    j.ncot = j.Cd / cot;
+    nq = std::max(nq, j.Cs / 4);
+    xin = xin || (j.flags & N3D_RELU_IN) || j.in_gate;
+    gx = std::max(gx, (unsigned)j.nblk); gy = std::max(gy, (unsigned)j.ncot);
+    shm = std::max(shm, (size_t)j.Cs * (cot + 1) * sizeof(float));
+  }
+  const dim3 grid(gx, gy, (unsigned)(B0 + (j1 ? B1 : 0)));
+  switch (cot) {
+    case 16: launch_point_t<16>(a, nq, xin, grid, shm, s); break;
+    case 8: launch_point_t<8>(a, nq, xin, grid, shm, s); break;
+    default: launch_point_t<4>(a, nq, xin, grid, shm, s); break;
+  }
+  g_point_launches += 1; g_point_jobs += n;
+}
+
+// the calls the pointwise kernel takes (include/n3d.h, N3D_NO_POINTWISE); fills the job record
+static bool point_job(const GatherArgs& a, int B, PointJob* j) {
+  if (a.k != 1 || (a.flags & (N3D_NO_POINTWISE | N3D_SRC_BF16 | N3D_DST_BF16)) || a.off != 0 || !a.src || !a.dst) return false;
+  if (a.Cs % 4 != 0 || a.Cd % 4 != 0 || a.Cs < 4 || a.Cd < 4 || a.Cdp % 4 != 0 || a.sld % 4 != 0 || a.dld % 4 != 0 || a.sld < a.Cs || a.dld < a.Cd) return false;
+  if (!aligned16(a.src) || !aligned16(a.dst) || !aligned16(a.wp)) return false;
+  if (a.relu_src && (a.rld % 4 != 0 || a.rld < a.Cd || !aligned16(a.relu_src))) return false;
+  if ((size_t)a.Cs * (4 + 1) * sizeof(float) > POINT_LDS_MAX) return false;
+  const bool fwd = a.den == 1 && (a.sn == 1 || a.sn == 2), up = a.den == 2 && a.sn == 1 && !a.bias && !a.stats;
+  if (!fwd && !up) return false;
+  // every source voxel the map reaches lies inside the source (holds for the geometries check_geom accepts; checked, not assumed)
+  const int64_t sn = a.sn;
+  if (fwd && ((a.Dd - 1) * sn >= a.Ds || (a.Hd - 1) * sn >= a.Hs || (a.Wd - 1) * sn >= a.Ws)) return false;
+  if (up && ((a.Dd - 1) / 2 >= a.Ds || (a.Hd - 1) / 2 >= a.Hs || (a.Wd - 1) / 2 >= a.Ws)) return false;
+  const int64_t Nd = (int64_t)a.Dd * a.Hd * a.Wd;
+  if (Nd >= (1ll << 31) || B <= 0 || B > 32767) return false;
+  j->src = (const float*)a.src; j->sld = a.sld; j->dst = (float*)a.dst; j->dld = a.dld; j->wp = a.wp; j->bias = a.bias; j->in_gate = a.in_gate;
+  j->relu_src = (const float*)a.relu_src; j->rld = a.rld; j->out_gate = a.out_gate; j->stats = a.stats;
+  j->Nd = Nd; j->Ns = (int64_t)a.Ds * a.Hs * a.Ws;
+  j->Cs = a.Cs; j->Cd = a.Cd; j->Cdp = a.Cdp; j->flags = a.flags; j->sn = a.sn; j->den = a.den; j->Hs = a.Hs; j->Ws = a.Ws;
+  j->nblk = (int)cdiv(Nd, 256); j->ncot = 0;
+  j->fWd = a.fWd; j->fHd = a.fHd;
+  return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1909,9 +2161,14 @@ static DwArgs dw_args(const n3d_conv_geom* g, bool data_grad, const float* src, 
 struct K1Norm { const float* oscale; const float* oshift; bool nostore; bool used; };
 static thread_local K1Norm* g_k1_norm = nullptr;
 
+// a pointwise job held back by run_gather for a two-job launch (n3d_conv_fwd2 / n3d_conv_bwd_data2)
+// `before`: the held job of the pair's earlier call -- launched first if this call turns out to launch in place, so the pair keeps its order
+struct PointHold { PointJob job; int B; bool held; PointHold* before; };
+
 static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
                       int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate,
-                      double* stats, void* ws, size_t ws_bytes, void* stream) {
+                      double* stats, void* ws, size_t ws_bytes, void* stream, PointHold* hold = nullptr) {
+  if (hold) hold->held = false;
   hipStream_t s = (hipStream_t)stream;
   const bool sb16 = flags & N3D_SRC_BF16, db16 = flags & N3D_DST_BF16;
   if (g->depthwise) {
@@ -2018,7 +2275,49 @@ static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, 
       return N3D_ERR_UNSUPPORTED;
     }
   }
+  {
+    // small pointwise convs (conv_point_kernel): the weights are packed by now, the launch may be left to the caller (hold)
+    PointJob pj;
+    if (!src_planar && !dst_planar && !g_k1_norm && point_job(a, g->B, &pj)) {
+      if (hold) { hold->job = pj; hold->B = g->B; hold->held = true; return N3D_OK; }
+      launch_point(&pj, g->B, nullptr, 0, s);
+      N3D_LAUNCH_CHECK();
+      return N3D_OK;
+    }
+  }
+  if (hold && hold->before && hold->before->held) {      // this call launches in place: the pair's held first call goes in front of it
+    launch_point(&hold->before->job, hold->before->B, nullptr, 0, s);
+    hold->before->held = false;
+  }
   launch_gather(a, g->B, s);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+// a call of a pair that no kernel family in front of the pointwise kernel takes (the MFMA family needs channel counts that are multiples
+// of 16, the streaming kernel its own shapes): run_gather then either holds it as a pointwise job or launches the gather kernel -- behind
+// the held job of the pair's first call (PointHold::before) -- so the calls of a pair keep their order and the first launch of the pair
+// carries the armed entry signals
+static bool point_pair_candidate(const n3d_conv_geom* g, bool data_grad, int flags) {
+  const int Cs = data_grad ? g->Co : g->Ci, Cd = data_grad ? g->Ci : g->Co;
+  return g->k == 1 && !g->depthwise && g->pad == 0 && !(flags & (N3D_NO_POINTWISE | N3D_SRC_BF16 | N3D_DST_BF16)) && Cs % 4 == 0 && Cd % 4 == 0 &&
+         (Cs % 16 != 0 || Cd % 16 != 0 || (flags & N3D_NO_MFMA)) && !k1_dims_ok(g, data_grad, Cs, Cd);
+}
+// A two-job launch reads both calls' packed weights at once, and run_gather packs a call's weights into its workspace before it holds
+// the launch back: two calls may fold only if the second call's packing cannot touch the first one's packed copy -- both N3D_PREPACKED
+// (nothing is packed), or workspaces that do not overlap.  A C-ABI caller may reuse one scratch buffer for both calls: that pair runs
+// as the two sequential launches it always was (conv_mfma.hip keeps the same rule for its pair / multi launches).
+static bool point_pair_ws_ok(int flags0, const void* ws0, size_t n0, int flags1, const void* ws1, size_t n1) {
+  if ((flags0 & N3D_PREPACKED) && (flags1 & N3D_PREPACKED)) return true;
+  const uintptr_t a0 = (uintptr_t)ws0, a1 = (uintptr_t)ws1;
+  return ws0 && ws1 && (a0 + n0 <= a1 || a1 + n1 <= a0);
+}
+// launches what run_gather held back of a pair: one launch for two jobs, else the held one alone (also on the error path of the second
+// call: the first call then has run, as it would have on the sequential path)
+static int point_pair_finish(PointHold* h, hipStream_t s) {
+  if (h[0].held && h[1].held) launch_point(&h[0].job, h[0].B, &h[1].job, h[1].B, s);
+  else if (h[0].held) launch_point(&h[0].job, h[0].B, nullptr, 0, s);
+  else if (h[1].held) launch_point(&h[1].job, h[1].B, nullptr, 0, s);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -2397,6 +2696,21 @@ int n3d_conv_fwd2(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1, void
     if (r < 0) return r;
     if (r == 1) return N3D_OK;
   }
+  if (c0->y != c1->y && !c0->transposed && !c1->transposed && point_pair_candidate(c0->g, false, c0->flags) && point_pair_candidate(c1->g, false, c1->flags) &&
+      point_pair_ws_ok(c0->flags, c0->ws, c0->ws_bytes, c1->flags, c1->ws, c1->ws_bytes)) {
+    // two small pointwise convs: one launch of conv_point_kernel (a call run_gather routes elsewhere launches in place, as alone)
+    for (int i = 0; i < 2; ++i)      // (both calls' arguments are checked before anything is enqueued)
+      N3D_CHECK_ARG((cs[i]->xld >= cs[i]->g->Ci || (cs[i]->xld >= 4 && cs[i]->g->Ci % cs[i]->xld == 0)) && cs[i]->yld >= cs[i]->g->Co, "conv_fwd2: bad pointers/pitches");
+    PointHold h[2] = {};
+    h[1].before = &h[0];
+    for (int i = 0; i < 2; ++i) {
+      const n3d_conv_fwd_call* c = cs[i];
+      const int e = run_gather(c->g, false, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, nullptr, 0, nullptr, c->stats, c->ws,
+                               c->ws_bytes, stream, &h[i]);
+      if (e) { point_pair_finish(h, (hipStream_t)stream); return e; }
+    }
+    return point_pair_finish(h, (hipStream_t)stream);
+  }
   for (int i = 0; i < 2; ++i) {
     const n3d_conv_fwd_call* c = cs[i];
     const int e = c->transposed ? n3d_convT_fwd(c->g, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, c->stats, c->ws, c->ws_bytes, stream)
@@ -2476,6 +2790,23 @@ int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
     if (r < 0) return r;
     if (r == 1) return N3D_OK;
   }
+  if (c0->dx != c1->dx && !c0->transposed && !c1->transposed && point_pair_candidate(c0->g, true, c0->flags_data) &&
+      point_pair_candidate(c1->g, true, c1->flags_data) &&
+      point_pair_ws_ok(c0->flags_data, c0->ws_data, c0->ws_data_bytes, c1->flags_data, c1->ws_data, c1->ws_data_bytes)) {
+    // two small pointwise data gradients with distinct targets: one launch of conv_point_kernel
+    for (int i = 0; i < 2; ++i)      // (both calls' arguments are checked before anything is enqueued)
+      N3D_CHECK_ARG(cs[i]->dyld >= cs[i]->g->Co && (cs[i]->dxld >= cs[i]->g->Ci || (cs[i]->dxld >= 4 && cs[i]->g->Ci % cs[i]->dxld == 0)),
+                    "conv_bwd_data2: bad pointers/pitches");
+    PointHold h[2] = {};
+    h[1].before = &h[0];
+    for (int i = 0; i < 2; ++i) {
+      const n3d_conv_bwd_call* c = cs[i];
+      const int e = run_gather(c->g, true, c->dy, c->dyld, c->w, nullptr, c->dx, c->dxld, c->flags_data & ~N3D_RELU_IN, nullptr, c->relu_src, c->rld,
+                               c->out_gate, nullptr, c->ws_data, c->ws_data_bytes, stream, &h[i]);
+      if (e) { point_pair_finish(h, (hipStream_t)stream); return e; }
+    }
+    return point_pair_finish(h, (hipStream_t)stream);
+  }
   for (int i = 0; i < 2; ++i) {
     const n3d_conv_bwd_call* c = cs[i];
     const int e = c->transposed ? n3d_convT_bwd_data(c->g, c->dy, c->dyld, c->w, c->dx, c->dxld, c->flags_data, c->ws_data, c->ws_data_bytes, stream)
@@ -2549,6 +2880,12 @@ int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
                                           c->ws_weight_bytes, c->deferred, stream);
     if (e) return e;
   }
+  return N3D_OK;
+}
+
+int n3d_conv_pointwise_counts(int64_t* launches, int64_t* jobs) {
+  N3D_CHECK_ARG(launches && jobs, "conv_pointwise_counts: null outputs");
+  *launches = g_point_launches.load(); *jobs = g_point_jobs.load();
   return N3D_OK;
 }
 

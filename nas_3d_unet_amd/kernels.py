@@ -89,6 +89,16 @@ def entry_signal_pending():
     return sum(len(q) for q in _entry_pending.values()) + int(_lib.load().n3d_entry_signal_pending())
 
 
+NO_POINTWISE = _lib.NO_POINTWISE
+
+
+def conv_pointwise_counts():
+    """(launches of the small pointwise conv kernel, jobs they carried) since the library was loaded: a two-job launch counts (1, 2)"""
+    a, b = C.c_int64(0), C.c_int64(0)
+    check(_lib.load().n3d_conv_pointwise_counts(C.byref(a), C.byref(b)), "n3d_conv_pointwise_counts")
+    return a.value, b.value
+
+
 def entry_signal_counts():
     """(signals carried by a kernel entry, signals the library launched stand-alone) since the library was loaded"""
     a, b = C.c_int64(0), C.c_int64(0)
@@ -632,7 +642,8 @@ def conv_k1_norm_bwd_apply_wgrad(g, x: View, w, bias, dout: View, a, b, A, Bc, C
 
 
 def conv_fwd2(calls):
-    """Two forward convs, one launch where libn3d can fold them.  calls = [(g, x, w, bias, y, flags, in_gate, stats, transposed)] * 2"""
+    """Two forward convs, one launch where libn3d can fold them (small MFMA problems; two small pointwise convs: one two-job launch of
+    conv_point_kernel).  calls = [(g, x, w, bias, y, flags, in_gate, stats, transposed)] * 2"""
     cs, keep = [], []
     for (g, x, w, bias, y, flags, in_gate, stats, transposed) in calls:
         flags = _cflags(flags, x, y)
@@ -701,7 +712,8 @@ def dwconv_batch(jobs):
 
 
 def conv_bwd_data2(calls):
-    """Data gradients of two convs, one launch where libn3d can fold them (distinct dx targets, small-tensor MFMA shapes).
+    """Data gradients of two convs, one launch where libn3d can fold them (distinct dx targets; small-tensor MFMA shapes or two small
+    pointwise convs).
     calls = [(g, dy, w, dx, flags, relu_src, out_gate, transposed)] * 2, arguments as conv_bwd_data."""
     cs, keep = [], []
     for (g, dy, w, dx, flags, relu_src, out_gate, transposed) in calls:
