@@ -242,6 +242,10 @@ int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
  * n3d_conv_pointwise_counts: launches of the pointwise kernel / jobs they carried since the library was loaded (a two-job launch
  * counts 1 / 2): lets a test see which path a call took. */
 int n3d_conv_pointwise_counts(int64_t* launches, int64_t* jobs);
+/* n3d_conv_fold_counts: launches of the folded conv kernels since the library was loaded, counts[5] = one-wave-tile 3x3x3 convs in one
+ * launch (n3d_conv_fwd2 / fwdN / bwd_data2), two K-split GEMM convs, three or four of them, data + weight gradient of one conv
+ * (n3d_conv_bwd_both), of two (n3d_conv_bwd_both2): lets a test see that a call took the folded kernel and not single launches. */
+int n3d_conv_fold_counts(int64_t* counts);
 /* transposed convolution y[i side] = convT(x[o side]) + bias; same kernels with the roles swapped */
 int n3d_convT_fwd(const n3d_conv_geom* g, const float* x, int64_t xld, const float* w, const float* bias,
                   float* y, int64_t yld, int flags, const float* in_gate, double* stats,

@@ -2036,6 +2036,7 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
                   int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate, double* stats,
                   void* ws, size_t ws_bytes, hipStream_t s);
 int mfma_conv_stats_rows(const n3d_conv_geom* g, bool data_grad, int flags);
+extern std::atomic<int64_t> g_fold_launches[5];
 // bf16-storage vox64 family (conv_bf16.hip)
 int vox16_layout(const n3d_conv_geom* g, bool data_grad, int flags);
 int vox16_stats_rows(const n3d_conv_geom* g, bool data_grad, int flags);
@@ -2886,6 +2887,12 @@ int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
 int n3d_conv_pointwise_counts(int64_t* launches, int64_t* jobs) {
   N3D_CHECK_ARG(launches && jobs, "conv_pointwise_counts: null outputs");
   *launches = g_point_launches.load(); *jobs = g_point_jobs.load();
+  return N3D_OK;
+}
+
+int n3d_conv_fold_counts(int64_t* counts) {
+  N3D_CHECK_ARG(counts, "conv_fold_counts: null output");
+  for (int i = 0; i < 5; ++i) counts[i] = g_fold_launches[i].load();
   return N3D_OK;
 }
 

@@ -14,11 +14,16 @@
 #include <stdlib.h>
 #include "n3d_common.h"
 #include <type_traits>
+#include <atomic>
 // cache policy of the weight-gradient kernels' LDS-DMA loads (cpol bits: 1 = sc0, 2 = nt, 16 = sc1).  These kernels run on the side
 // stream next to the backward chain and stream 8-25 MB tensors through the L2s that hold the chain's working set.
 #define N3D_WGRAD_AUX 0
 
 namespace n3d {
+
+// launches of the folded conv kernels since the library was loaded (n3d_conv_fold_counts): vox multi, gemm16 pair, gemm16 multi,
+// backward dual (data + weight gradient of one conv), backward quad (of two)
+std::atomic<int64_t> g_fold_launches[5];
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1523,6 +1528,7 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
   q.start[4] = at;
   if (C == 4) N3D_LAUNCH(conv_vox_multi_kernel<4>, dim3((unsigned)at), dim3(64), lds, s, q);
   else N3D_LAUNCH(conv_vox_multi_kernel<8>, dim3((unsigned)at), dim3(64), lds, s, q);
+  g_fold_launches[0] += 1;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(vox multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -2994,6 +3000,7 @@ int mfma_conv_pair_try(const n3d_conv_geom* g0, bool dg0, const float* src0, int
   const EntrySignal es = entry_take(s);
   if (p0.ksplit == 16) N3D_LAUNCH(conv_gemm16_pair_kernel<16>, dim3((unsigned)(q.n0 + n1)), dim3(1024), shm, s, q, es);
   else N3D_LAUNCH(conv_gemm16_pair_kernel<4>, dim3((unsigned)(q.n0 + n1)), dim3(256), shm, s, q, es);
+  g_fold_launches[1] += 1;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(pair) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -3033,6 +3040,7 @@ int mfma_conv_multi_try(int n, const n3d_conv_geom* const* g, const bool* dg, co
   const size_t shm = (size_t)(ksplit - 1) * 256 * sizeof(float) + (size_t)16 * 16 * 2 * sizeof(double);
   if (ksplit == 16) N3D_LAUNCH(conv_gemm16_multi_kernel<16>, dim3((unsigned)total), dim3(1024), shm, s, q);
   else N3D_LAUNCH(conv_gemm16_multi_kernel<4>, dim3((unsigned)total), dim3(256), shm, s, q);
+  g_fold_launches[2] += 1;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -3310,6 +3318,7 @@ int mfma_bwd_dual_try(const n3d_conv_geom* g, bool transposed, const float* dy, 
   const dim3 grid((unsigned)(q.nA + cdiv(q.nB, units)));
   if (p.ksplit == 16) N3D_LAUNCH(conv_bwd16_dual_kernel<16>, grid, dim3(1024), shm, s, q);
   else N3D_LAUNCH(conv_bwd16_dual_kernel<4>, grid, dim3(256), shm, s, q);
+  g_fold_launches[3] += 1;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(bwd dual) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;
@@ -3354,6 +3363,7 @@ int mfma_bwd_quad_try(BwdOne* c0, BwdOne* c1, hipStream_t s) {
   const size_t shm = shm_a > shm_b ? shm_a : shm_b;
   if (k0 == 16) N3D_LAUNCH(conv_bwd16_quad_kernel<16>, dim3((unsigned)(z.n0 + n1)), dim3(1024), shm, s, z);
   else N3D_LAUNCH(conv_bwd16_quad_kernel<4>, dim3((unsigned)(z.n0 + n1)), dim3(256), shm, s, z);
+  g_fold_launches[4] += 1;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(bwd quad) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
   return 1;

@@ -99,6 +99,16 @@ def conv_pointwise_counts():
     return a.value, b.value
 
 
+FOLD_KINDS = ("vox_multi", "gemm16_pair", "gemm16_multi", "bwd_dual", "bwd_quad")
+
+
+def conv_fold_counts():
+    """launches of the folded conv kernels since the library was loaded, by kind (FOLD_KINDS; include/n3d.h, n3d_conv_fold_counts)"""
+    a = (C.c_int64 * 5)()
+    check(_lib.load().n3d_conv_fold_counts(a), "n3d_conv_fold_counts")
+    return dict(zip(FOLD_KINDS, (int(v) for v in a)))
+
+
 def entry_signal_counts():
     """(signals carried by a kernel entry, signals the library launched stand-alone) since the library was loaded"""
     a, b = C.c_int64(0), C.c_int64(0)
