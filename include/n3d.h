@@ -563,6 +563,32 @@ typedef struct n3d_patch_gdesc { n3d_patch_desc d; int32_t vol; } n3d_patch_gdes
 int n3d_patch_gather(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_gdesc* descs, int B, int P, int flags,
                      float* x_out, int64_t xld, void* t_out, void* stream);
 
+/* ---- the step before the data step (preprocess.py:77-144, create_h5:58-66): raw scanner counts to the statistics of the data
+ * set and to each subject's normalised brain-wise box.  raw: DEVICE int16 (Cm, X, Y, Z) contiguous, 2-byte aligned (a modality's
+ * base need not be 16-byte aligned: X * Y * Z may be odd); X * Y * Z < 2^31.  "Brain" = the voxels with raw != 0, per modality.
+ * Nothing here synchronises.
+ * n3d_brain_scan: ONE launch per subject.  totals: int64 [Cm][2] = {count, sum of values} of the brain voxels, ADDED to what is
+ * there (zero it once, keep it across the subjects of a data set: exact integer totals).  rec: int32 [Cm][N3D_BRAIN_REC_WORDS] =
+ * {min value, max value, min index x, y, z, max index x, y, z} over the brain voxels, combined with atomic min / max: the caller
+ * fills it per subject with {INT32_MAX, INT32_MIN, INT32_MAX x 3, -1 x 3}, which is also what a modality without brain keeps. */
+#define N3D_BRAIN_REC_WORDS 8
+int n3d_brain_scan(const int16_t* raw, int Cm, int X, int Y, int Z, int64_t* totals, int32_t* rec, void* stream);
+/* n3d_brain_sqdev: acc[c] += sum over modality c's brain voxels of (x - mean[c])^2 in fp64 (two roundings per term, no
+ * contraction).  N = X * Y * Z.  mean, acc: DEVICE double [Cm]; ws: DEVICE double [Cm * n3d_brain_sqdev_rows(N)] partial rows,
+ * reduced in a fixed order (no floating-point atomics): the same data at the same 16-byte phase gives the same bits, and
+ * subjects enqueued on one stream accumulate in that order. */
+int n3d_brain_sqdev_rows(int64_t N);
+int n3d_brain_sqdev(const int16_t* raw, int Cm, int64_t N, const double* mean, double* ws, double* acc, void* stream);
+/* n3d_brain_normalize: normalize (preprocess.py:87-93) fused with the crop to the box [lo, hi) (HOST int32[3] each, inside the
+ * image): out is DEVICE fp32 (Cm, bx, by, bz), b = hi - lo.  A brain voxel becomes, each operation rounded once in fp64,
+ *   z = (x - mean) / std;  q = (z - zmin) / (zmax - zmin);  v = (q + 0.1) * 100;  out = (float)(int16)v  (truncated toward zero:
+ * the reference writes v back into its int16 array); other voxels 0.  mean_std: DEVICE double [Cm][2]; zmin / zmax are z of
+ * rec's min / max value (rec as n3d_brain_scan left it for THIS subject, read on the device).  The caller rules out a modality
+ * without brain or with min == max beforehand (the quotient is undefined there).  truth / truth_out: DEVICE uint8 (X, Y, Z) ->
+ * (bx, by, bz) crop in the same launch, or both NULL. */
+int n3d_brain_normalize(const int16_t* raw, int Cm, int X, int Y, int Z, const double* mean_std, const int32_t* rec, const int32_t* lo,
+                        const int32_t* hi, float* out, const uint8_t* truth, uint8_t* truth_out, void* stream);
+
 /* ---- step after the hot path (prediction.py:120-170): stitch the per-patch predictions into the brain-wide volume with
  * mean blending (patches.py:172-207) and fuse the three sigmoid channels into one label volume.
  * n3d_stitch: patches element (b, c, voxel v = (lx*P+ly)*P+lz) at patches[b*sb + c*sc + v*sv] (any of the layouts the

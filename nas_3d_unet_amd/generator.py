@@ -6,7 +6,7 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
 
   * VolumeSet keeps the brain-wise boxes resident in HBM with two summed-area tables per volume (n3d_volume_sat, built once
     at load), so that one n3d_patch_qualify launch answers both filters for every candidate of an epoch (8 lookups per table
-    and candidate, whatever the patch size or overlap);
+    and candidate, whatever the patch size or overlap); add_subject takes a raw int16 scan there (preprocess.normalize_subject);
   * Generator reproduces the reference class's epoch exactly, random stream included: the overlap drawn per epoch, the candidate
     order, the shuffle and pop() from the end, one isometry key per KEPT patch, the batch boundaries and the smaller last batch,
     steps_per_epoch -- and produces each batch with ONE n3d_patch_gather launch (patches of different volumes in one batch), no
@@ -22,7 +22,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib, datastep, predict
+from . import _lib, datastep, predict, preprocess
 from . import kernels as K
 from ._lib import GatherDesc, N3DError, PatchDesc, PatchVolume, check
 
@@ -92,6 +92,7 @@ class VolumeSet:
         if self.device.type != "cuda":
             raise N3DError("VolumeSet: volumes live on a HIP device (got %s); there is no CPU fallback" % self.device)
         self.volumes, self.truths, self.tables, self.boxes = [], [], [], []
+        self.origins, self.full_shapes = [], []     # per volume: the box's corner in its image and the image's shape (add_subject), else None
         self.channels = None
         self.has_truth = None
         self.records = None        # device table of n3d_patch_volume records (rebuilt by add)
@@ -126,12 +127,25 @@ class VolumeSet:
         self.truths.append(t)
         self.tables.append(sat)
         self.boxes.append((X, Y, Z))
+        self.origins.append(None)
+        self.full_shapes.append(None)
         self.channels, self.has_truth = Cv, truth is not None
         recs = (PatchVolume * len(self.volumes))()
         for i, (vv, tt, ss, b) in enumerate(zip(self.volumes, self.truths, self.tables, self.boxes)):
             recs[i] = PatchVolume(vv.data_ptr(), tt.data_ptr() if tt is not None else None, ss.data_ptr(), (C.c_int32 * 3)(*b), 0)
         self.records = torch.frombuffer(bytearray(recs), dtype=torch.uint8).to(self.device)
         return len(self.volumes) - 1
+
+    def add_subject(self, raw, truth, mean_std, mods=preprocess.MODS):
+        """raw: (Cm, X, Y, Z) int16 scanner counts (numpy or tensor); truth: (X, Y, Z) / (1, X, Y, Z) uint8 or None; mean_std: the
+        dictionary of preprocess.cal_mean_std.  Normalises and crops on the device (preprocess.normalize_subject), add()s the box
+        and notes where it sits: origins[i] (brain_width[0]) and full_shapes[i] are what SubjectPredictor.predict takes as
+        origin / full_shape.  Returns the volume's index."""
+        vol, t, brain_width = preprocess.normalize_subject(raw, mean_std, truth, mods, self.device)
+        i = self.add(vol, t)
+        self.origins[i] = tuple(int(v) for v in brain_width[0])
+        self.full_shapes[i] = tuple(int(v) for v in raw.shape[-3:])
+        return i
 
     def table(self, i):
         """volume i's summed-area tables: (X+1, Y+1, Z+1, 2) int32, (modality mask, label mask), zero planes at the low ends"""
