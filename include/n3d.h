@@ -662,6 +662,46 @@ int n3d_adam_step_guarded(float* param, const float* grad, float* exp_avg, float
                           int32_t* step_ptr, int inc_step, const void* timeouts, const void* acked, const float* peer_flag,
                           float* loss, void* host_word, void* stream);
 int n3d_guard_flag(const void* timeouts, const void* acked, float* flag, void* stream);
+/* n3d_adam_step_guarded with a clip coefficient: *coef (a device float, e.g. out + 1 of n3d_grad_clip_coef; NULL = 1) multiplies
+ * grad_scale, read once per launch.  With coef == NULL this IS n3d_adam_step_guarded (the two entry points above pass NULL). */
+int n3d_adam_step_coef(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_ptr,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, const float* coef, int32_t* step_ptr,
+                       int inc_step, const void* timeouts, const void* acked, const float* peer_flag, float* loss, void* host_word,
+                       void* stream);
+
+/* ---- flat AdaBound / AdaBoundW (adabound.py:50-118 / 164-234; imported by train.py:10, search.py:14) ----------------
+ * The same flat buffers, step counter (inc_step 0 / 1 / 2), device learning rate, guard and clip coefficient as the Adam entry
+ * points; max_exp_avg_sq is the AMSBound buffer (NULL = amsbound off).  Per element, in fp32 and in the reference's order:
+ *   g' = coef * grad_scale * g;  coupled (decoupled == 0) and weight_decay != 0: g' += wd * p
+ *   m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  vh = amsbound ? (vmax = max(vmax, v)) : v
+ *   r = clamp(step_size / (sqrt(vh) + eps), lo, hi);  p -= r m;  decoupled and weight_decay != 0: p -= wd * p_old (NOT times lr)
+ * Once per launch, in double from the device step t and the device rate lr, each rounded to fp32 once:
+ *   step_size = lr sqrt(1 - b2^t) / (1 - b1^t);  final = final_lr * lr / base_lr
+ *   lo = final (1 - 1 / (gamma t + 1));  hi = final (1 + 1 / (gamma t))
+ * base_lr: the fp32 rate the trainer started with (adabound.py:43), so lr / base_lr is exact while a plateau schedule halves it.
+ * Unlike Adam's there is no 1/sqrt(1 - b2^t) on sqrt(v).  betas, eps, weight_decay, final_lr and gamma are doubles -- the
+ * reference's Python floats -- and 1 - beta is taken in double before the one rounding, as torch does for an fp32 tensor.
+ * Traffic per element: 16 B in + 12 B out (20 + 16 with amsbound). */
+int n3d_adabound_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, float lr,
+                      const float* lr_ptr, float base_lr, double beta1, double beta2, double eps, double weight_decay,
+                      double final_lr, double gamma, int decoupled, float grad_scale, const float* coef, int32_t* step_ptr,
+                      int inc_step, void* stream);
+int n3d_adabound_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                              float lr, const float* lr_ptr, float base_lr, double beta1, double beta2, double eps,
+                              double weight_decay, double final_lr, double gamma, int decoupled, float grad_scale,
+                              const float* coef, int32_t* step_ptr, int inc_step, const void* timeouts, const void* acked,
+                              const float* peer_flag, float* loss, void* host_word, void* stream);
+
+/* ---- global gradient norm and clip coefficient (config.yml:49 grad_clip; train.py:126-127, search.py:236-237) --------
+ * torch.nn.utils.clip_grad_norm_(params, max_norm) with norm_type 2 and error_if_nonfinite=False over ONE flat buffer, in one
+ * launch and without a host sync:  out[0] = || grad_scale * grad ||_2 (fp64 sums, rounded to fp32 once),
+ * out[1] = min(1, max_norm / (out[0] + 1e-6)) (quotient in fp64, rounded once).  A NaN norm gives a NaN coefficient.  The
+ * optimiser entry points read out + 1 as `coef`.  The grid depends on n alone, every workgroup adds its elements in a fixed
+ * order and the workgroup that draws the last ticket adds the partial sums in index order: the same input gives the same bits
+ * on every launch and every graph replay.  scratch: n3d_grad_clip_scratch_bytes() bytes, 8-byte aligned, zeroed once (word 0
+ * is the ticket, cleared again by the launch). */
+size_t n3d_grad_clip_scratch_bytes(void);
+int n3d_grad_clip_coef(const float* grad, int64_t n, float grad_scale, double max_norm, void* scratch, float* out, void* stream);
 /* 64 bytes of pinned, device-mapped, coherent host memory (zeroed); the pointer is valid on the host and in kernels */
 int n3d_host_word_alloc(void** host_ptr);
 int n3d_host_word_free(void* host_ptr);

@@ -120,6 +120,7 @@ _i = C.c_int
 _i64 = C.c_int64
 _f = C.c_float
 _sz = C.c_size_t
+_d = C.c_double
 _gp = C.POINTER(ConvGeom)
 
 # name -> (restype, argtypes); must list every function declared in include/n3d.h
@@ -234,6 +235,12 @@ PROTOTYPES = {
     "n3d_adam_step": (_i, [_p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _i, _p]),
     "n3d_adam_step_guarded": (_i, [_p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _i, _p, _p, _p, _p, _p, _p]),
     "n3d_guard_flag": (_i, [_p, _p, _p, _p]),
+    "n3d_adam_step_coef": (_i, [_p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "n3d_adabound_step": (_i, [_p, _p, _p, _p, _p, _i64, _f, _p, _f, _d, _d, _d, _d, _d, _d, _i, _f, _p, _p, _i, _p]),
+    "n3d_adabound_step_guarded": (_i, [_p, _p, _p, _p, _p, _i64, _f, _p, _f, _d, _d, _d, _d, _d, _d, _i, _f, _p, _p, _i,
+                                       _p, _p, _p, _p, _p, _p]),
+    "n3d_grad_clip_scratch_bytes": (_sz, []),
+    "n3d_grad_clip_coef": (_i, [_p, _i64, _f, _d, _p, _p, _p]),
     "n3d_host_word_alloc": (_i, [C.POINTER(C.c_void_p)]),
     "n3d_host_word_free": (_i, [_p]),
     "n3d_stream_create_low_priority": (_i, [C.POINTER(C.c_void_p)]),

@@ -6,7 +6,9 @@ them back in check_resume (train.py:52-67; search.py:108-127); the genotype trav
 that is `eval`ed (search.py:189-194; train.py:36-38).  Module state-dicts need no conversion (same keys and shapes).
 What does need one is the optimizer: the trainers keep Adam's moments in flat buffers with ONE step counter, torch's
 Adam keeps per-parameter tensors -- `adam_state_dict` / `load_adam_state_dict` translate both ways, and the plateau
-schedulers export / import torch's ReduceLROnPlateau field names.
+schedulers export / import torch's ReduceLROnPlateau field names.  A trainer built with optimizer="adabound" / "adaboundw" writes the
+state_dict() layout of the reference's adabound.py classes instead (`adabound_state_dict`) and records its optimiser's name under
+"optimizer" ("optimizer_kernel" in a search checkpoint); loading state another optimiser wrote raises ValueError.
 """
 from __future__ import annotations
 
@@ -80,6 +82,86 @@ def load_adam_state_dict(fp, sd, twin=None, real=None):
     return float(sd["param_groups"][0]["lr"])
 
 
+# ------------------------------------------------------------------------------------------------ AdaBound / AdaBoundW
+def _optim_of(trainer):
+    """the trainer's train.OptimSpec (a trainer without one runs Adam)"""
+    return getattr(trainer, "optim", None)
+
+
+def adabound_state_dict(fp, optim, lr, twin=None, real=None):
+    """state_dict() of the reference's AdaBound / AdaBoundW (adabound.py) for a train.FlatParams: per parameter `step` (an int, as
+    the class counts it), `exp_avg`, `exp_avg_sq` and, with amsbound, `max_exp_avg_sq`; the param group holds lr, betas, final_lr,
+    gamma, eps, weight_decay, amsbound.  Parameter order and shapes as adam_state_dict."""
+    step = int(fp.step.item())
+    bufs = [("exp_avg", fp.exp_avg), ("exp_avg_sq", fp.exp_avg_sq)] + ([("max_exp_avg_sq", fp.max_exp_avg_sq)] if optim.amsbound else [])
+    state = {}
+    ents = _entries(fp, twin, real)
+    for i, (o, shape, name) in enumerate(ents):
+        n = int(torch.Size(shape).numel())
+        if step > 0:
+            st = {"step": step}
+            for key, buf in bufs:
+                t = buf[o:o + n].view(shape)
+                st[key] = (twin.extract(name, t) if name is not None else t).clone()
+            state[i] = st
+    wd = optim.weight_decay
+    group = {"lr": lr, "betas": tuple(optim.betas), "final_lr": optim.final_lr, "gamma": optim.gamma, "eps": optim.eps,
+             "weight_decay": int(wd) if wd == 0 else wd, "amsbound": optim.amsbound, "params": list(range(len(ents)))}
+    return {"state": state, "param_groups": [group]}
+
+
+def load_adabound_state_dict(fp, optim, sd, twin=None, real=None):
+    """inverse of adabound_state_dict; returns the learning rate stored in the checkpoint.  Moments and step are loaded; final_lr,
+    gamma, weight_decay, betas and eps stay the trainer's.  A file whose amsbound differs from the trainer's is refused rather than
+    half loaded."""
+    group = sd["param_groups"][0]
+    if "final_lr" not in group:
+        raise ValueError("checkpoint's optimizer state is not AdaBound's (param group keys: %s)" % sorted(group))
+    if bool(group.get("amsbound", False)) != optim.amsbound:
+        raise ValueError("checkpoint was written with amsbound=%s, the trainer runs amsbound=%s" % (group.get("amsbound", False), optim.amsbound))
+    if optim.amsbound:
+        fp.ensure_amsbound()
+    bufs = [("exp_avg", fp.exp_avg), ("exp_avg_sq", fp.exp_avg_sq)] + ([("max_exp_avg_sq", fp.max_exp_avg_sq)] if optim.amsbound else [])
+    for _, buf in bufs:
+        buf.zero_()
+    steps = set()
+    for i, (o, shape, name) in enumerate(_entries(fp, twin, real)):
+        st = sd["state"].get(i)
+        if st is None:
+            continue
+        n = int(torch.Size(shape).numel())
+        for key, buf in bufs:
+            t = st[key].to(buf.device)
+            if name is not None:     # reference shapes -> the twin's (zeros at the padded entries, which no optimiser here moves)
+                t = twin.embed_tensor(name, t, shape)
+            buf[o:o + n].copy_(t.reshape(-1))
+        steps.add(int(float(st["step"])))
+    if len(steps) > 1:
+        raise ValueError("checkpoint has different step counts per parameter: %s" % sorted(steps))
+    fp.step.fill_(steps.pop() if steps else 0)
+    return float(group["lr"])
+
+
+def _optim_state_dict(trainer, fp, lr, twin, real):
+    optim = _optim_of(trainer)
+    if optim is None or optim.name == "adam":
+        return adam_state_dict(fp, lr, trainer.betas, trainer.eps, twin, real)
+    return adabound_state_dict(fp, optim, lr, twin, real)
+
+
+def _load_optim_state_dict(trainer, fp, sd, written_by, twin, real):
+    """written_by: the optimiser name the checkpoint records (files from before the record, and the reference's own Adam
+    checkpoints, carry none: "adam")"""
+    optim = _optim_of(trainer)
+    mine = "adam" if optim is None else optim.name
+    if written_by != mine:
+        raise ValueError("checkpoint's optimizer state was written by %r, this trainer runs %r: build the trainer with optimizer=%r "
+                         "(or load with new_lr=True to take the weights only)" % (written_by, mine, written_by))
+    if mine == "adam":
+        return load_adam_state_dict(fp, sd, twin, real)
+    return load_adabound_state_dict(fp, optim, sd, twin, real)
+
+
 # ------------------------------------------------------------------------------------------------ scheduler
 _SCHED_FIELDS = ("factor", "patience", "threshold", "cooldown", "eps", "best", "num_bad_epochs", "cooldown_counter", "last_epoch")
 
@@ -114,11 +196,21 @@ def _twin_of(trainer, real):
     return (tw, real) if tw is not None else (None, None)
 
 
+def _record_optimizer(sd, key, trainer):
+    """which optimiser wrote the kernel weights' state: AdaBound and AdaBoundW share one layout, so the name goes next to it.  An Adam
+    checkpoint stays key for key the reference's (train.py:85-93; search.py:166-176) and carries no record"""
+    optim = _optim_of(trainer)
+    if optim is not None and optim.name != "adam":
+        sd[key] = optim.name
+    return sd
+
+
 def train_state_dicts(trainer, epoch, history, best_loss):
     _checked(trainer)
-    return {"epoch": epoch, "history": history, "model_param": trainer.model.state_dict(),
-            "optim": adam_state_dict(trainer.fp, trainer.lr, trainer.betas, trainer.eps, *_twin_of(trainer, trainer.model)),
-            "scheduler": scheduler_state_dict(trainer.scheduler), "best_loss": best_loss}
+    sd = {"epoch": epoch, "history": history, "model_param": trainer.model.state_dict(),
+          "optim": _optim_state_dict(trainer, trainer.fp, trainer.lr, *_twin_of(trainer, trainer.model)),
+          "scheduler": scheduler_state_dict(trainer.scheduler), "best_loss": best_loss}
+    return _record_optimizer(sd, "optimizer", trainer)
 
 
 def load_train_state_dicts(trainer, sd, new_lr=False):
@@ -126,7 +218,7 @@ def load_train_state_dicts(trainer, sd, new_lr=False):
     trainer.model.load_state_dict(sd["model_param"])   # parameters are views of the flat buffer: copied in place
     getattr(trainer, "sync_from_module", lambda: None)()   # (a padded twin re-embeds the loaded parameters)
     if not new_lr:
-        trainer.set_lr(load_adam_state_dict(trainer.fp, sd["optim"], *_twin_of(trainer, trainer.model)))
+        trainer.set_lr(_load_optim_state_dict(trainer, trainer.fp, sd["optim"], sd.get("optimizer", "adam"), *_twin_of(trainer, trainer.model)))
         load_scheduler_state_dict(trainer.scheduler, sd["scheduler"])
     return sd["epoch"] + 1, sd["history"], sd["best_loss"]
 
@@ -136,11 +228,12 @@ def search_state_dicts(trainer, epoch, geno_count, history, best_loss):
     """the reference's search checkpoint: two optimizers, two schedulers (the reference stores the KERNEL scheduler under
     both scheduler keys, search.py:174; here each key holds its own scheduler)"""
     _checked(trainer)
-    return {"epoch": epoch, "geno_count": geno_count, "history": history, "model_param": trainer.model.state_dict(),
-            "optim_shell": adam_state_dict(trainer.afp, trainer.lr_shell, trainer.betas, trainer.eps),
-            "optim_kernel": adam_state_dict(trainer.fp, trainer.lr_kernel, trainer.betas, trainer.eps, *_twin_of(trainer, trainer.model.kernel)),
-            "kernel_scheduler": scheduler_state_dict(trainer.kernel_scheduler),
-            "shell_scheduler": scheduler_state_dict(trainer.shell_scheduler), "best_loss": best_loss}
+    sd = {"epoch": epoch, "geno_count": geno_count, "history": history, "model_param": trainer.model.state_dict(),
+          "optim_shell": adam_state_dict(trainer.afp, trainer.lr_shell, trainer.betas, trainer.eps),
+          "optim_kernel": _optim_state_dict(trainer, trainer.fp, trainer.lr_kernel, *_twin_of(trainer, trainer.model.kernel)),
+          "kernel_scheduler": scheduler_state_dict(trainer.kernel_scheduler),
+          "shell_scheduler": scheduler_state_dict(trainer.shell_scheduler), "best_loss": best_loss}
+    return _record_optimizer(sd, "optimizer_kernel", trainer)
 
 
 def load_search_state_dicts(trainer, sd, new_lr=False):
@@ -149,7 +242,8 @@ def load_search_state_dicts(trainer, sd, new_lr=False):
     getattr(trainer, "sync_from_module", lambda: None)()   # (a padded twin re-embeds the loaded parameters)
     if not new_lr:
         trainer.set_shell_lr(load_adam_state_dict(trainer.afp, sd["optim_shell"]))
-        trainer.set_kernel_lr(load_adam_state_dict(trainer.fp, sd["optim_kernel"], *_twin_of(trainer, trainer.model.kernel)))
+        trainer.set_kernel_lr(_load_optim_state_dict(trainer, trainer.fp, sd["optim_kernel"], sd.get("optimizer_kernel", "adam"),
+                                                     *_twin_of(trainer, trainer.model.kernel)))
         load_scheduler_state_dict(trainer.shell_scheduler, sd["shell_scheduler"])
         load_scheduler_state_dict(trainer.kernel_scheduler, sd["kernel_scheduler"])
     return sd["epoch"] + 1, sd["geno_count"], sd["history"], sd["best_loss"]

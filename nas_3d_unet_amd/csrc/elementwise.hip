@@ -2255,7 +2255,8 @@ __global__ void guard_flag_kernel(const unsigned* timeouts, const unsigned* acke
 }
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                    int64_t n, float lr_imm, const float* __restrict__ lr_ptr, float b1, float b2, float eps,
-                                                   float wd, float gscale, int32_t* __restrict__ step_ptr, int ticketed, AdamGuard gd) {
+                                                   float wd, float gscale, const float* __restrict__ coef, int32_t* __restrict__ step_ptr,
+                                                   int ticketed, AdamGuard gd) {
   // guard (include/n3d.h, n3d_adam_step_guarded): a device-side wait of this step's stream hand-offs gave up (time-outs counted
   // != time-outs the host has acknowledged) or a peer rank reported one (all-reduced flag != 0) -> the gradients are not to be
   // trusted: NO update, moments and step counter untouched (the ticket counter stays 0), the loss scalar becomes NaN and the
@@ -2278,6 +2279,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const double bc2 = 1.0 - pow((double)b2, (double)step);
   const float step_size = (float)((double)lr / bc1);
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  if (coef) gscale *= *coef;       // the clip coefficient of n3d_grad_clip_coef (one load per launch; NULL: gscale as it is)
   auto upd = [&](float& pi, float gi, float& mi, float& vi) {
     gi *= gscale;
     if (wd != 0.f) gi = fmaf(wd, pi, gi);
@@ -2330,6 +2332,157 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 __global__ void step_inc_kernel(int32_t* step_ptr) { *step_ptr += 1; }
+
+// ------------------------------------------------------------------------------------------------
+// AdaBound / AdaBoundW (adabound.py:50-118, 164-234), flat like Adam above: same guard, same ticketed step count, same float4
+// path with an element-wise tail.  The per-element order is the reference's; what differs from adam_kernel is the denominator
+// (sqrt(v) + eps, no 1/sqrt(bc2): the bias corrections sit in step_size) and the clamp of step_size / denom to [lo, hi].
+// ------------------------------------------------------------------------------------------------
+struct AdaBoundArgs {
+  double b1, b2, eps, wd, final_lr, gamma;   // the reference's Python floats: rounded to fp32 once each, as torch does for an fp32 tensor
+  float lr_imm, base_lr, gscale;
+  int decoupled;                             // 1: AdaBoundW (p -= wd * p_old next to the step, not scaled by lr)
+};
+template <bool AMS>
+__global__ __launch_bounds__(256) void adabound_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ vmax, int64_t n, const float* __restrict__ lr_ptr, AdaBoundArgs a,
+                                                       const float* __restrict__ coef, int32_t* __restrict__ step_ptr, int ticketed, AdamGuard gd) {
+  {  // the guard of adam_kernel: a withheld launch touches nothing but the loss scalar and the host word
+    bool skip = false;
+    if (gd.timeouts) skip = __hip_atomic_load(gd.timeouts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != *gd.acked;
+    if (gd.peer_flag) skip = skip || (*gd.peer_flag != 0.f);
+    if (skip) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (gd.loss) *gd.loss = __builtin_nanf("");
+        if (gd.host_word) __hip_atomic_store(gd.host_word, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      return;
+    }
+  }
+  const int step = *step_ptr + 1;
+  const double lr = (double)(lr_ptr ? *lr_ptr : a.lr_imm);
+  const double bc1 = 1.0 - pow(a.b1, (double)step);
+  const double bc2 = 1.0 - pow(a.b2, (double)step);
+  const float step_size = (float)(lr * sqrt(bc2) / bc1);
+  // lr / base_lr is exactly 1 until the schedule first reduces the rate and exactly 0.5 after (both are fp32 values of one device word)
+  const double final_lr = a.final_lr * lr / (double)a.base_lr;
+  const float lo = (float)(final_lr * (1.0 - 1.0 / (a.gamma * (double)step + 1.0)));
+  const float hi = (float)(final_lr * (1.0 + 1.0 / (a.gamma * (double)step)));
+  const float b1 = (float)a.b1, b2 = (float)a.b2, omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), eps = (float)a.eps, wd = (float)a.wd;
+  const bool coupled = wd != 0.f && !a.decoupled, decoupled = wd != 0.f && a.decoupled;
+  const float gs = coef ? a.gscale * *coef : a.gscale;
+  auto upd = [&](float& pi, float gi, float& mi, float& vi, float& xi) {
+    gi *= gs;
+    if (coupled) gi = fmaf(wd, pi, gi);
+    mi = fmaf(b1, mi, omb1 * gi);
+    vi = fmaf(b2, vi, omb2 * gi * gi);
+    float vh = vi;
+    if (AMS) { xi = xi > vi ? xi : vi; vh = xi; }     // (torch.max: a NaN second moment stays NaN only through v itself)
+    const float q = step_size / (sqrtf(vh) + eps);
+    const float r = q < lo ? lo : (q > hi ? hi : q);  // clamp_ order, NaN passes through
+    const float p_old = pi;
+    pi = pi - r * mi;
+    if (decoupled) pi = pi - wd * p_old;
+  };
+  constexpr int U = 2;
+  const bool vec = (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                      (AMS ? reinterpret_cast<uintptr_t>(vmax) : (uintptr_t)0)) & 15) == 0);
+  const int64_t n4 = vec ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 p4[U], g4[U], m4[U], v4[U], x4[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      const int64_t ic = i < n4 ? i : i0;
+      p4[u] = reinterpret_cast<const float4*>(p)[ic]; g4[u] = reinterpret_cast<const float4*>(g)[ic];
+      m4[u] = reinterpret_cast<const float4*>(m)[ic]; v4[u] = reinterpret_cast<const float4*>(v)[ic];
+      x4[u] = AMS ? reinterpret_cast<const float4*>(vmax)[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < n4) {
+        upd(p4[u].x, g4[u].x, m4[u].x, v4[u].x, x4[u].x); upd(p4[u].y, g4[u].y, m4[u].y, v4[u].y, x4[u].y);
+        upd(p4[u].z, g4[u].z, m4[u].z, v4[u].z, x4[u].z); upd(p4[u].w, g4[u].w, m4[u].w, v4[u].w, x4[u].w);
+        reinterpret_cast<float4*>(m)[i] = m4[u]; reinterpret_cast<float4*>(v)[i] = v4[u]; reinterpret_cast<float4*>(p)[i] = p4[u];
+        if (AMS) reinterpret_cast<float4*>(vmax)[i] = x4[u];
+      }
+    }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i], xi = AMS ? vmax[i] : 0.f;
+    upd(pi, g[i], mi, vi, xi);
+    m[i] = mi; v[i] = vi; p[i] = pi;
+    if (AMS) vmax[i] = xi;
+  }
+  if (ticketed) {   // as in adam_kernel: the workgroup that draws the last ticket counts the step and clears the counter
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(step_ptr + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tk == gridDim.x - 1) {
+        __hip_atomic_store(reinterpret_cast<unsigned*>(step_ptr + 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(step_ptr, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// global gradient norm -> clip coefficient (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite=False), one launch.
+// The grid depends on n alone and every workgroup adds a fixed set of elements in a fixed order (lane-strided fp64 sums, then a
+// fixed tree over the 256 lanes), so partial b is the same on every launch; the workgroup that draws the last ticket adds the
+// partials in index order.  scratch: word 0 = ticket (zero between launches), doubles from byte 8 = partials.
+// ------------------------------------------------------------------------------------------------
+constexpr int GRAD_NORM_MAX_WG = 256;
+constexpr int GRAD_NORM_EPB = 8192;
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict__ g, int64_t n, float gscale, double max_norm,
+                                                        unsigned* __restrict__ ticket, double* __restrict__ partial, float* __restrict__ out) {
+  __shared__ double red[256];
+  __shared__ bool last_one;
+  const int t = threadIdx.x;
+  const double gs = (double)gscale;
+  double acc = 0.0;
+  const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+  const int64_t n4 = vec ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n4; i += stride) {
+    const float4 q = reinterpret_cast<const float4*>(g)[i];
+    const double x = gs * (double)q.x, y = gs * (double)q.y, z = gs * (double)q.z, w = gs * (double)q.w;
+    acc += x * x; acc += y * y; acc += z * z; acc += w * w;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + t; i < n; i += stride) {
+    const double x = gs * (double)g[i];
+    acc += x * x;
+  }
+  red[t] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  if (t == 0) {
+    __hip_atomic_store(partial + blockIdx.x, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    last_one = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last_one) return;
+  __threadfence();
+  red[t] = t < (int)gridDim.x ? __hip_atomic_load(partial + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+  __syncthreads();
+  if (t == 0) {
+    double sum = 0.0;
+    for (int b = 0; b < (int)gridDim.x; ++b) sum += red[b];
+    const float norm = (float)sqrt(sum);
+    out[0] = norm;
+    // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1.0) of the fp32 norm, the quotient taken in fp64 and rounded once;
+    // a NaN norm gives a NaN coefficient, an infinite one 0 (0 * inf = NaN in the update, as in torch)
+    const double c = max_norm / ((double)norm + 1e-6);
+    out[1] = (float)(c > 1.0 ? 1.0 : c);
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
 
 }  // namespace n3d
 
@@ -3132,6 +3285,12 @@ int n3d_guard_flag(const void* timeouts, const void* acked, float* flag, void* s
 int n3d_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_ptr, float beta1,
                           float beta2, float eps, float weight_decay, float grad_scale, int32_t* step_ptr, int inc_step,
                           const void* timeouts, const void* acked, const float* peer_flag, float* loss, void* host_word, void* stream) {
+  return n3d_adam_step_coef(param, grad, exp_avg, exp_avg_sq, n, lr, lr_ptr, beta1, beta2, eps, weight_decay, grad_scale, nullptr, step_ptr,
+                            inc_step, timeouts, acked, peer_flag, loss, host_word, stream);
+}
+int n3d_adam_step_coef(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_ptr, float beta1,
+                       float beta2, float eps, float weight_decay, float grad_scale, const float* coef, int32_t* step_ptr, int inc_step,
+                       const void* timeouts, const void* acked, const float* peer_flag, float* loss, void* host_word, void* stream) {
   N3D_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step_ptr && n > 0, "adam_step: bad args");
   N3D_CHECK_ARG((timeouts == nullptr) == (acked == nullptr), "adam_step_guarded: timeouts and acked come together");
   N3D_CHECK_ARG(inc_step != 1 || (!timeouts && !peer_flag), "adam_step_guarded: a guarded update counts its own step (inc_step 0 or 2)");
@@ -3143,8 +3302,50 @@ int n3d_adam_step_guarded(float* param, const float* grad, float* exp_avg, float
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   N3D_LAUNCH(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, lr_ptr,
-                     beta1, beta2, eps, weight_decay, grad_scale, step_ptr, inc_step == 2 ? 1 : 0, gd);
+                     beta1, beta2, eps, weight_decay, grad_scale, coef, step_ptr, inc_step == 2 ? 1 : 0, gd);
   if (inc_step == 1) N3D_LAUNCH(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_adabound_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, float lr,
+                      const float* lr_ptr, float base_lr, double beta1, double beta2, double eps, double weight_decay, double final_lr, double gamma,
+                      int decoupled, float grad_scale, const float* coef, int32_t* step_ptr, int inc_step, void* stream) {
+  return n3d_adabound_step_guarded(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, lr, lr_ptr, base_lr, beta1, beta2, eps, weight_decay,
+                                   final_lr, gamma, decoupled, grad_scale, coef, step_ptr, inc_step, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   stream);
+}
+int n3d_adabound_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, float lr,
+                              const float* lr_ptr, float base_lr, double beta1, double beta2, double eps, double weight_decay, double final_lr,
+                              double gamma, int decoupled, float grad_scale, const float* coef, int32_t* step_ptr, int inc_step,
+                              const void* timeouts, const void* acked, const float* peer_flag, float* loss, void* host_word, void* stream) {
+  N3D_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step_ptr && n > 0 && base_lr > 0.f, "adabound_step: bad args");
+  N3D_CHECK_ARG((timeouts == nullptr) == (acked == nullptr), "adabound_step_guarded: timeouts and acked come together");
+  N3D_CHECK_ARG(inc_step != 1 || (!timeouts && !peer_flag), "adabound_step_guarded: a guarded update counts its own step (inc_step 0 or 2)");
+  const AdamGuard gd{(const unsigned*)timeouts, (const unsigned*)acked, peer_flag, loss, (unsigned*)host_word};
+  const AdaBoundArgs a{beta1, beta2, eps, weight_decay, final_lr, gamma, lr, base_lr, grad_scale, decoupled ? 1 : 0};
+  constexpr int epb = 8192;      // as n3d_adam_step_guarded
+  int64_t blocks = cdiv(n, epb);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  if (max_exp_avg_sq)
+    N3D_LAUNCH(adabound_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq,
+               n, lr_ptr, a, coef, step_ptr, inc_step == 2 ? 1 : 0, gd);
+  else
+    N3D_LAUNCH(adabound_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq,
+               n, lr_ptr, a, coef, step_ptr, inc_step == 2 ? 1 : 0, gd);
+  if (inc_step == 1) N3D_LAUNCH(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+size_t n3d_grad_clip_scratch_bytes(void) { return 8 + sizeof(double) * GRAD_NORM_MAX_WG; }
+int n3d_grad_clip_coef(const float* grad, int64_t n, float grad_scale, double max_norm, void* scratch, float* out, void* stream) {
+  N3D_CHECK_ARG(grad && scratch && out && n > 0 && (reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "grad_clip_coef: bad args");
+  int64_t blocks = cdiv(n, GRAD_NORM_EPB);
+  if (blocks > GRAD_NORM_MAX_WG) blocks = GRAD_NORM_MAX_WG;
+  N3D_LAUNCH(grad_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, n, grad_scale, max_norm, (unsigned*)scratch,
+             reinterpret_cast<double*>((char*)scratch + 8), out);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }

@@ -1521,6 +1521,51 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step_t, lr=1e-3, beta1=0.9, beta
           "n3d_adam_step_guarded")
 
 
+def _guard_args(guard):
+    vp = lambda v: C.c_void_p(v) if v else None
+    if guard is None:
+        return (None,) * 5
+    return vp(guard.timeouts), vp(guard.acked), vp(guard.peer_flag), vp(guard.loss), vp(guard.host_word)
+
+
+def adam_step_coef(param, grad, exp_avg, exp_avg_sq, step_t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                   grad_scale=1.0, inc_step=True, lr_dev=None, guard=None, coef=None):
+    """adam_step through n3d_adam_step_coef: `coef` is a 1-element device tensor (the clip coefficient of grad_clip_coef) that
+    multiplies grad_scale inside the launch; None = 1, and the launch is then adam_step's bit for bit"""
+    inc = 0 if not inc_step else (2 if getattr(step_t, "_n3d_ticketed", False) else 1)
+    check(_lib.load().n3d_adam_step_coef(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, ptr(lr_dev),
+                                         beta1, beta2, eps, weight_decay, grad_scale, ptr(coef), ptr(step_t), inc,
+                                         *_guard_args(guard), stream_ptr()), "n3d_adam_step_coef")
+
+
+def adabound_step(param, grad, exp_avg, exp_avg_sq, step_t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                  grad_scale=1.0, inc_step=True, lr_dev=None, guard=None, coef=None, final_lr=0.1, gamma=1e-3, base_lr=None,
+                  max_exp_avg_sq=None, decoupled=False):
+    """AdaBound (decoupled=False) / AdaBoundW (decoupled=True) over flat buffers (include/n3d.h, "flat AdaBound"); the arguments
+    of adam_step plus: max_exp_avg_sq (the AMSBound buffer; None = amsbound off), base_lr (the rate the run started with, as the
+    fp32 value first written to lr_dev; default: lr), coef (see adam_step_coef)"""
+    inc = 0 if not inc_step else (2 if getattr(step_t, "_n3d_ticketed", False) else 1)
+    base_lr = lr if base_lr is None else base_lr
+    args = (ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), ptr(max_exp_avg_sq), param.numel(), lr, ptr(lr_dev), base_lr,
+            beta1, beta2, eps, weight_decay, final_lr, gamma, 1 if decoupled else 0, grad_scale, ptr(coef), ptr(step_t), inc)
+    if guard is None:
+        check(_lib.load().n3d_adabound_step(*args, stream_ptr()), "n3d_adabound_step")
+    else:
+        check(_lib.load().n3d_adabound_step_guarded(*args, *_guard_args(guard), stream_ptr()), "n3d_adabound_step_guarded")
+
+
+def grad_clip_scratch(device):
+    """zeroed scratch of one grad_clip_coef call site (ticket word + fp64 partial sums)"""
+    return torch.zeros(int(_lib.load().n3d_grad_clip_scratch_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def grad_clip_coef(grad, max_norm, scratch, out, grad_scale=1.0):
+    """out[0] = ||grad_scale * grad||_2, out[1] = min(1, max_norm / (out[0] + 1e-6)): torch.nn.utils.clip_grad_norm_ over one flat
+    fp32 buffer, one launch, no host sync, the same bits on every launch (include/n3d.h).  out: 2 device floats"""
+    check(_lib.load().n3d_grad_clip_coef(ptr(grad), grad.numel(), grad_scale, float(max_norm), ptr(scratch), ptr(out), stream_ptr()),
+          "n3d_grad_clip_coef")
+
+
 def guard_flag(timeouts_ptr, acked_ptr, flag_ptr):
     """*flag = 1.0 if a hand-off of this rank timed out and is not acknowledged, else 0.0 (all-reduced with the gradients)"""
     check(_lib.load().n3d_guard_flag(C.c_void_p(timeouts_ptr), C.c_void_p(acked_ptr), C.c_void_p(flag_ptr), stream_ptr()), "n3d_guard_flag")

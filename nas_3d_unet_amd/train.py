@@ -59,6 +59,7 @@ class FlatParams:
         self.grad = self.grad_full[GRAD_HEADER:]
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=device)
+        self.max_exp_avg_sq = None      # (AMSBound only: ensure_amsbound)
         self.step = K.step_counter(device) if torch.device(device).type == "cuda" else torch.zeros(1, dtype=torch.int32, device=device)
         self.offsets = offs
         with torch.no_grad():
@@ -73,6 +74,77 @@ class FlatParams:
     def adam(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, lr_dev=None, guard=None):
         K.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step, lr, betas[0], betas[1], eps,
                     weight_decay, grad_scale, True, lr_dev, guard)
+
+    def ensure_amsbound(self):
+        """the AMSBound buffer (adabound.py:79-81, max_exp_avg_sq): allocated only for an optimiser that asks for it"""
+        if self.max_exp_avg_sq is None:
+            self.max_exp_avg_sq = torch.zeros_like(self.exp_avg_sq)
+
+    def update(self, optim, lr, grad_scale=1.0, lr_dev=None, guard=None, coef=None):
+        """one step of `optim` (an OptimSpec) on the flat buffers; coef: 1-element device tensor holding the clip coefficient
+        (K.grad_clip_coef), None = no clipping.  Adam without a coefficient is `adam()`, launch for launch."""
+        b1, b2 = optim.betas
+        if optim.name == "adam":
+            if coef is None:
+                return self.adam(lr, optim.betas, optim.eps, optim.weight_decay, grad_scale, lr_dev, guard)
+            return K.adam_step_coef(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step, lr, b1, b2, optim.eps,
+                                    optim.weight_decay, grad_scale, True, lr_dev, guard, coef)
+        if optim.amsbound:
+            self.ensure_amsbound()
+        K.adabound_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step, lr, b1, b2, optim.eps, optim.weight_decay,
+                        grad_scale, True, lr_dev, guard, coef, optim.final_lr, optim.gamma, optim.base_lr,
+                        self.max_exp_avg_sq if optim.amsbound else None, optim.name == "adaboundw")
+
+
+class OptimSpec:
+    """Which optimiser a trainer runs on its kernel weights and with what constants: "adam" (torch.optim.Adam defaults,
+    train.py:49), "adabound" or "adaboundw" (the reference's adabound.py, imported by train.py:10 / search.py:14).  optim_args
+    are the reference classes' keyword arguments next to lr / betas / eps: final_lr, gamma, weight_decay, amsbound; validation
+    as adabound.py:27-38.  base_lr is the rate the run started with, as the fp32 value the device scalar holds (adabound.py:43)."""
+
+    NAMES = ("adam", "adabound", "adaboundw")
+    ARGS = dict(final_lr=0.1, gamma=1e-3, weight_decay=0, amsbound=False)
+
+    def __init__(self, name="adam", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, optim_args=None):
+        if name not in self.NAMES:
+            raise ValueError("Invalid optimizer: %r (one of %s)" % (name, ", ".join(self.NAMES)))
+        args = dict(optim_args or {})
+        unknown = sorted(set(args) - set(self.ARGS))
+        if unknown or (name == "adam" and args):
+            raise ValueError("Invalid optim_args for %s: %s" % (name, unknown or sorted(args)))
+        args = {**self.ARGS, **args}
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        if not 0.0 <= args["final_lr"]:
+            raise ValueError("Invalid final learning rate: {}".format(args["final_lr"]))
+        if not 0.0 <= args["gamma"] < 1.0:
+            raise ValueError("Invalid gamma parameter: {}".format(args["gamma"]))
+        if name != "adam" and not 0.0 < lr:
+            raise ValueError("Invalid learning rate: {} (the bounds scale with lr / base_lr)".format(lr))
+        self.name, self.betas, self.eps = name, (float(betas[0]), float(betas[1])), float(eps)
+        self.final_lr, self.gamma = float(args["final_lr"]), float(args["gamma"])
+        self.weight_decay, self.amsbound = float(args["weight_decay"]), bool(args["amsbound"])
+        self.base_lr = float(torch.tensor(float(lr), dtype=torch.float32))
+
+
+class _GradClip:
+    """global-norm gradient clipping in front of an update (config.yml:49 grad_clip; train.py:126-127, search.py:236-237):
+    one launch writes {norm, coefficient} to `out`, the optimiser launch behind it reads the coefficient -- no host sync"""
+
+    def __init__(self, max_norm, device):
+        self.max_norm = float(max_norm)
+        self.out = torch.zeros(2, dtype=torch.float32, device=device)
+        self.scratch = K.grad_clip_scratch(device) if torch.device(device).type == "cuda" else None
+
+    def launch(self, grad, grad_scale):
+        K.grad_clip_coef(grad, self.max_norm, self.scratch, self.out, grad_scale)
+        return self.out[1:]
 
 
 class PlateauLR:
@@ -1241,7 +1313,8 @@ class _GraphTrainer:
 
     def _state(self):
         """optimizer-visible state the schedule timing must leave as it found it"""
-        return [self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full]
+        ams = [self.fp.max_exp_avg_sq] if self.fp.max_exp_avg_sq is not None else []
+        return [self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full] + ams
 
     def _choose_schedule(self):
         """time the two captured schedules on the real step (state saved and restored around it) and keep the faster one.  Data
@@ -1270,7 +1343,9 @@ class Trainer(_GraphTrainer):
     n_buckets >= 2 (data parallel only): bucketed gradient exchange overlapped with backward, see the module docstring."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None,
-                 n_buckets=None, params=None, comm=None, storage=None, side_wgrad=None):
+                 n_buckets=None, params=None, comm=None, storage=None, side_wgrad=None, optimizer="adam", optim_args=None,
+                 grad_clip=None):
+        self.optim = OptimSpec(optimizer, lr, betas, eps, optim_args)
         super().__init__(model, model, lr, betas, eps, graph, process_group, side_wgrad)
         self.net = model      # the module whose kernels run (the model itself, or its padded twin)
         if self._twin is not None:
@@ -1299,7 +1374,12 @@ class Trainer(_GraphTrainer):
         if self._twin is not None:
             # gradients of the twin's PADDED parameter entries are not zero (GroupNorm couples a padded channel to its group) and Adam would
             # move them by lr per step: they are masked in front of every update, so the padded entries stay exactly 0
+            # (AdaBound / AdaBoundW as well, with weight_decay != 0 too: a masked entry has g = 0 and p = 0, so g' = wd * p = 0,
+            # m stays 0, the step r * m is 0 whatever the clamp gives, and the decoupled decay takes wd * 0 off it)
             self._pad_mask = _pad_mask_for(self._twin, self.model, self.fp, self.device)
+        if self.optim.amsbound:
+            self.fp.ensure_amsbound()
+        self._clip = _GradClip(grad_clip, self.device) if grad_clip is not None else None
         if n_buckets is None:
             n_buckets = int(os.environ.get("N3D_DP_BUCKETS", "1"))
         self.n_buckets = max(1, n_buckets)
@@ -1464,7 +1544,15 @@ class Trainer(_GraphTrainer):
     def _update(self, loss=None):
         if self._pad_mask is not None:
             self.fp.grad.mul_(self._pad_mask)
-        self.fp.adam(self.lr, self.betas, self.eps, 0.0, 1.0 / self.world, self.lr_dev, self._guard(loss, self.sync))
+        # grad_clip: the norm of the gradient the optimiser is about to see (slabs reduced, padded entries masked, ranks averaged)
+        coef = self._clip.launch(self.fp.grad, 1.0 / self.world) if self._clip is not None else None
+        self.fp.update(self.optim, self.lr, 1.0 / self.world, self.lr_dev, self._guard(loss, self.sync), coef)
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor: the global gradient norm of the last step as clip_grad_norm_ returns it (None without grad_clip).
+        Written by the step's own launches; reading it here costs no sync"""
+        return self._clip.out[0] if self._clip is not None else None
 
     def set_lr(self, lr):
         """new learning rate for the following steps (also inside an already captured graph)"""
@@ -1623,7 +1711,11 @@ class SearchTrainer(_GraphTrainer):
     N_INPUTS = 4
     TIMING = (1, 3)
 
-    def __init__(self, shell, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None, comm=None, side_wgrad=None):
+    def __init__(self, shell, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None, comm=None, side_wgrad=None,
+                 optimizer="adam", optim_args=None, grad_clip=None):
+        # optimizer / optim_args / grad_clip: the weight pass (search.py:236-238: the commented clip line sits in front of
+        # optim_kernel.step()); the alphas stay on Adam (search.py:103)
+        self.optim = OptimSpec(optimizer, lr, betas, eps, optim_args)
         super().__init__(shell, shell.kernel, lr, betas, eps, graph, process_group, side_wgrad)
         # a kernel net with channel counts that are not multiples of 4: the shell's own alphas around its zero-padded twin
         self.net = shell if self._twin is None else _TwinShell(shell, self._twin.twin)
@@ -1643,6 +1735,9 @@ class SearchTrainer(_GraphTrainer):
         self.aparams = list(shell.alphas())
         self.fp = FlatParams(self.kparams, self.device)
         self._pad_mask = _pad_mask_for(self._twin, shell.kernel, self.fp, self.device) if self._twin is not None else None
+        if self.optim.amsbound:
+            self.fp.ensure_amsbound()
+        self._clip = _GradClip(grad_clip, self.device) if grad_clip is not None else None
         self.aflat, self.agrad, aoffs = flatten_params(self.aparams, self.device)
         self.a_m = torch.zeros_like(self.aflat)
         self.a_v = torch.zeros_like(self.aflat)
@@ -1746,7 +1841,13 @@ class SearchTrainer(_GraphTrainer):
         else:
             if self._pad_mask is not None:
                 self.fp.grad.mul_(self._pad_mask)       # (padded twin: the padded entries' gradients are not zero -- see Trainer)
-            self.fp.adam(self.lr_kernel, self.betas, self.eps, 0.0, 1.0 / self.world, self.lr_kernel_dev, guard)
+            coef = self._clip.launch(self.fp.grad, 1.0 / self.world) if self._clip is not None else None
+            self.fp.update(self.optim, self.lr_kernel, 1.0 / self.world, self.lr_kernel_dev, guard, coef)
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor: the kernel weights' global gradient norm of the last weight pass (None without grad_clip)"""
+        return self._clip.out[0] if self._clip is not None else None
 
     def _both(self, x, t, vx, vt, update=True):
         la = self._pass(vx, vt, True, update)
