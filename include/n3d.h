@@ -621,6 +621,30 @@ int n3d_stitch_add(const float* patches, int64_t sb, int64_t sc, int64_t sv, int
 int n3d_stitch_finish(const double* sum, const int32_t* cnt, int C, int X, int Y, int Z, double* probs, uint8_t* labels, double threshold,
                       int inclusive, const float* mask_vol, int Cv, int FX, int FY, int FZ, int ox, int oy, int oz, void* stream);
 
+/* ---- whole-image prediction (prediction.py:102-119, `fs_pred`): one forward on the full image zero-padded at the high end; no
+ * patches, no stitch.  full / padded / flip / origin: HOST int32[3] each.  The image (FX, FY, FZ) sits at the low corner of the
+ * padded grid (PX, PY, PZ), P >= F per axis; FX * FY * FZ < 2^31 (and PX * PY * PZ < 2^31 for the embed).  flip[a] != 0 mirrors
+ * the image within [0, F_a) -- the pad stays at the high end -- i.e. np.pad(permute_data(image, key)) for a flip-only key.
+ * n3d_image_embed: box = the subject's (Cv, bx, by, bz) contiguous fp32 box at `origin` inside the image; x_out = the net's input,
+ * pitched NDHWC (1, Cv, PX, PY, PZ), xld >= Cv.  Every voxel is written exactly once (the box, zeros around it and in the pad), so
+ * the caller clears nothing; the pitch gap is not touched (as n3d_patch_batch).
+ * n3d_image_add / n3d_image_finish: y = the net's fp32 prediction of the image embedded under `flip`, element (c, padded voxel v)
+ * at y[c*sc + v*sv] (any layout the net produces, as n3d_stitch); it is un-flipped and cropped to the image here.  sum: the fp64
+ * running sum (C, FX, FY, FZ) of an ensemble's earlier keys.  n3d_image_add (every key but the last): sum = y if `first`, else
+ * sum + y -- the first key writes, so sum needs no clearing.  n3d_image_finish (the last key): ONE pass over the image,
+ * mean = (sum + (double)y) / K in key order; sum NULL exactly when K == 1, and then mean is exactly (double)y.  probs (float64
+ * (C, FX, FY, FZ)) and labels (uint8 (FX, FY, FZ); C == 3) may each be NULL (not both); labels = the fusion of n3d_tumor_labels on
+ * the mean; with mask_box -- the subject's box again -- the label is 0 where every channel of the box is zero ("zero" as
+ * n3d_volume_sat: prediction.py:83-96) and everywhere outside the box.  Every voxel of an output is written exactly once.  One
+ * thread owns a voxel, fixed order, no atomics: the same inputs give the same bits.  1 <= C <= 4. */
+int n3d_image_embed(const float* box, int Cv, int bx, int by, int bz, const int32_t* origin, const int32_t* full, const int32_t* padded,
+                    const int32_t* flip, float* x_out, int64_t xld, void* stream);
+int n3d_image_add(const float* y, int64_t sc, int64_t sv, int C, const int32_t* full, const int32_t* padded, const int32_t* flip, double* sum,
+                  int first, void* stream);
+int n3d_image_finish(const float* y, int64_t sc, int64_t sv, int C, const int32_t* full, const int32_t* padded, const int32_t* flip,
+                     const double* sum, int K, double* probs, uint8_t* labels, double threshold, int inclusive, const float* mask_box, int Cv,
+                     int bx, int by, int bz, const int32_t* origin, void* stream);
+
 /* ---- RCCL exchange step of data-parallel training (no reference counterpart: config.yml:54 `multi_gpus` is never read;
  * SURVEY 8(e)).  One process per GPU; the hot path's only exchange is a SUM all-reduce of the flat fp32 gradient buffer, in
  * place, stream-ordered on `stream` (a side HIP stream lets it run under the backward kernels of the next bucket).

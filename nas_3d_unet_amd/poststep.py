@@ -125,3 +125,94 @@ def stitch_finish(sum_, cnt, full_shape=None, origin=(0, 0, 0), want_probs=True,
                                         1 if inclusive_label else 0, K.ptr(mask_vol), Cv, FX, FY, FZ, int(origin[0]), int(origin[1]),
                                         int(origin[2]), K.stream_ptr()), "n3d_stitch_finish")
     return labels, probs
+
+
+# ---- whole-image prediction (predict.ImagePredictor; prediction.py:102-119): the passes around the one forward
+def _i3(v, what):
+    v = [int(a) for a in v]
+    if len(v) != 3:
+        raise N3DError("%s: expected three values, got %s" % (what, v))
+    return (C.c_int32 * 3)(*v)
+
+
+def _image_y(y, padded, what):
+    """the net's (1, C, PX, PY, PZ) fp32 prediction -> (tensor, channels, channel stride, voxel stride)"""
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 5 and y.shape[0] == 1
+            and tuple(int(s) for s in y.shape[2:]) == tuple(int(p) for p in padded)):
+        raise N3DError("%s: y must be a (1, C, %d, %d, %d) fp32 tensor on a HIP device" % ((what,) + tuple(int(p) for p in padded)))
+    st = K._bcv_strides(y)
+    if st is None:
+        y = y.contiguous()
+        st = K._bcv_strides(y)
+    return y, int(y.shape[1]), st[1], st[2]
+
+
+def _image_sum(sum_, Cc, full, device, what):
+    if not (isinstance(sum_, torch.Tensor) and sum_.device == device and sum_.dtype == torch.float64 and sum_.is_contiguous()
+            and tuple(sum_.shape) == (Cc,) + tuple(int(f) for f in full)):
+        raise N3DError("%s: the running sum is a contiguous float64 (%d, %d, %d, %d) tensor on y's device" % ((what, Cc) + tuple(int(f) for f in full)))
+
+
+def _image_box(box, device, what):
+    if not (isinstance(box, torch.Tensor) and box.device == device and box.dtype == torch.float32 and box.dim() == 4 and box.is_contiguous()):
+        raise N3DError("%s: the subject's box must be a contiguous (Cv, bx, by, bz) fp32 tensor on the HIP device" % what)
+    return tuple(int(s) for s in box.shape)
+
+
+def image_embed(box, origin, full_shape, padded_shape, flip=(False, False, False), out=None):
+    """the subject's (Cv, bx, by, bz) box at `origin` inside the (FX, FY, FZ) image -> the net's input (1, Cv, PX, PY, PZ) in NDHWC
+    storage: the image mirrored along the axes of `flip`, zero-padded at the high end (n3d_image_embed).  out: written in place
+    (every voxel is written; a pitch gap is left as it is)."""
+    if not (isinstance(box, torch.Tensor) and box.is_cuda):
+        raise N3DError("image_embed: the box lives on a HIP device; there is no CPU fallback")
+    Cv, bx, by, bz = _image_box(box, box.device, "image_embed")
+    PX, PY, PZ = (int(p) for p in padded_shape)
+    if out is None:
+        out = K.empty_ndhwc(1, Cv, PX, PY, PZ, box.device, torch.float32)
+    if not (isinstance(out, torch.Tensor) and out.device == box.device and out.dtype == torch.float32 and tuple(out.shape) == (1, Cv, PX, PY, PZ)):
+        raise N3DError("image_embed: out must be a (1, %d, %d, %d, %d) fp32 tensor on the box's device" % (Cv, PX, PY, PZ))
+    ld = K._pitch_of(out)
+    if ld is None:
+        raise N3DError("image_embed: out must be in NDHWC (channels-last) storage, as K.empty_ndhwc gives it")
+    check(_lib.load().n3d_image_embed(K.ptr(box), Cv, bx, by, bz, _i3(origin, "origin"), _i3(full_shape, "full_shape"),
+                                      _i3(padded_shape, "padded_shape"), _i3([bool(f) for f in flip], "flip"), K.ptr(out), ld, K.stream_ptr()),
+          "n3d_image_embed")
+    return out
+
+
+def image_add(y, full_shape, padded_shape, flip, sum_=None):
+    """one key of an ensemble that is not its last (n3d_image_add): y un-flipped and cropped to the image is written into (sum_ None:
+    a fresh buffer, the first key) or added to the fp64 running sum (C, FX, FY, FZ), which is returned"""
+    y, Cc, sc, sv = _image_y(y, padded_shape, "image_add")
+    first = sum_ is None
+    if first:
+        sum_ = torch.empty((Cc,) + tuple(int(f) for f in full_shape), dtype=torch.float64, device=y.device)
+    _image_sum(sum_, Cc, full_shape, y.device, "image_add")
+    check(_lib.load().n3d_image_add(K.ptr(y), sc, sv, Cc, _i3(full_shape, "full_shape"), _i3(padded_shape, "padded_shape"),
+                                    _i3([bool(f) for f in flip], "flip"), K.ptr(sum_), 1 if first else 0, K.stream_ptr()), "n3d_image_add")
+    return sum_
+
+
+def image_finish(y, full_shape, padded_shape, flip=(False, False, False), sum_=None, n_keys=1, want_probs=True, want_labels=True,
+                 threshold=0.5, inclusive_label=False, mask_box=None, origin=(0, 0, 0)):
+    """the last (or only) key: one pass over the image (n3d_image_finish) -> (labels uint8 (FX, FY, FZ) or None, probs float64
+    (C, FX, FY, FZ) or None).  mean = (sum_ + y) / n_keys with y un-flipped and cropped (n_keys == 1: no sum_, exactly y);
+    mask_box: the subject's (Cv, bx, by, bz) box at `origin` -- labels are 0 where all of its channels are and outside it."""
+    y, Cc, sc, sv = _image_y(y, padded_shape, "image_finish")
+    if not (want_probs or want_labels):
+        raise N3DError("image_finish: neither probabilities nor labels asked for")
+    if (sum_ is None) != (int(n_keys) == 1):
+        raise N3DError("image_finish: a running sum goes with more than one key, and only with it")
+    if sum_ is not None:
+        _image_sum(sum_, Cc, full_shape, y.device, "image_finish")
+    Cv = bx = by = bz = 0
+    if mask_box is not None:
+        Cv, bx, by, bz = _image_box(mask_box, y.device, "image_finish")
+    full = tuple(int(f) for f in full_shape)
+    probs = torch.empty((Cc,) + full, dtype=torch.float64, device=y.device) if want_probs else None
+    labels = torch.empty(full, dtype=torch.uint8, device=y.device) if want_labels else None
+    check(_lib.load().n3d_image_finish(K.ptr(y), sc, sv, Cc, _i3(full, "full_shape"), _i3(padded_shape, "padded_shape"),
+                                       _i3([bool(f) for f in flip], "flip"), K.ptr(sum_), int(n_keys), K.ptr(probs), K.ptr(labels),
+                                       float(threshold), 1 if inclusive_label else 0, K.ptr(mask_box), Cv, bx, by, bz, _i3(origin, "origin"),
+                                       K.stream_ptr()), "n3d_image_finish")
+    return labels, probs

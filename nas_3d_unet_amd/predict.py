@@ -5,7 +5,11 @@ are n3d_patch_batch, the net's own ops, n3d_stitch and n3d_tumor_labels.
 
 SubjectPredictor is the subject-level pass (prediction.py:64-170) over a generator.VolumeSet: empty patches never reach the net
 (n3d_patch_qualify), the forward is one captured graph replayed per chunk, chunks are stitched as they come (n3d_stitch_add, which
-also brings the prediction of an isometry of the patch back) and one pass fuses mean, labels and skull mask (n3d_stitch_finish)."""
+also brings the prediction of an isometry of the patch back) and one pass fuses mean, labels and skull mask (n3d_stitch_finish).
+
+ImagePredictor is the reference's other mode (prediction.py:102-119, predict(no_patch=True)): ONE forward per subject on the whole
+image zero-padded at the high end (n3d_image_embed), cropped, averaged over flips and fused into labels in one pass
+(n3d_image_finish).  Both predictors share the forward -- eval mode, weight packing, the captured graph -- through _ForwardHost."""
 from __future__ import annotations
 
 import collections
@@ -137,34 +141,21 @@ def plan_subject(dead, n_keys, batch):
     return SubjectPlan(corner, key, slot, chunks)
 
 
-class SubjectPredictor:
-    """prediction.py:64-170 for one subject of a generator.VolumeSet, on the device end to end.
+class _ForwardHost:
+    """What the subject-level predictors share: the forward of the model (or of the module a trainer's step trains) in eval mode on a
+    static input buffer, weight packing included -- graph=True: captured once per signature (device, input shape, parameter
+    storage) and replayed -- and the counters captures / replays / forwards of `stats`."""
+    _what = "predictor"
 
-    predict(volumes, index, ...) -> (labels uint8 (FX, FY, FZ), probs float64 (n_labels, FX, FY, FZ) or None).
-    One n3d_patch_qualify launch and one read of its flag bytes per subject (the only host sync) mark the all-zero patches; they are
-    never gathered and never run (the reference's rule, prediction.py:133-135) -- they only count as covering.  The live
-    (corner, key) entries go `batch` at a time: VolumeSet.patch_batch writes the chunk into the static input buffer, the net runs
-    -- graph=True: ONE captured graph of the forward in eval mode, weight packing included, replayed for every chunk of every
-    subject whatever its box -- and n3d_stitch_add adds the chunk to the subject's running fp64 sums, inverting each entry's
-    isometry on the way.  n3d_stitch_finish then writes the labels (skull mask included) and, only if asked for, the fp64 image.
-    keys: isometry keys of datastep.generate_permutation_keys() (None: the identity); the prediction is the mean over every
-    (corner, key) patch, for a net trained with `permute`.
-
-    stats: entries / live / chunks of the last subject; captures / replays / forwards since the predictor was made."""
-
-    def __init__(self, model, patch=64, batch=8, graph=True, _net=None, _padded=False):
-        self.model, self.patch, self.batch, self.use_graph = model, int(patch), int(batch), bool(graph)
-        if not 1 <= self.batch <= 64:
-            raise N3DError("SubjectPredictor: batch must be 1..64 (N3D_PATCH_MAX_BATCH)")
+    def _init_forward(self, model, graph, _net, _padded):
+        self.model, self.use_graph = model, bool(graph)
         # a trainer hands over the module its step trains (Trainer.predictor): the model itself, or its zero-padded twin
         self._net, self._padded = _net, bool(_padded)
-        self.stats = types.SimpleNamespace(entries=0, live=0, chunks=0, captures=0, replays=0, forwards=0)
         self._ctx = None          # weight packing of this pass (the trainers' contexts stay as their steps left them)
         self._x = self._t = self._y = None
         self._graph = None
-        self._sig = None          # (device, parameter storage pointers, input channels) the buffers and the graph were made for
+        self._sig = None          # (device, input shape key, parameter storage pointers) the buffers and the graph were made for
 
-    # -- the forward ------------------------------------------------------------------------------
     def _modules(self):
         seen = {}
         for root in (self.model, self._net):
@@ -172,6 +163,22 @@ class SubjectPredictor:
                 for m in root.modules():
                     seen.setdefault(id(m), m)
         return list(seen.values())
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        """every module of the model (and of the trainer's module) in eval mode; the caller's modes come back"""
+        mods = self._modules()
+        was = [m.training for m in mods]
+        try:
+            for m in mods:
+                m.training = False
+            yield
+        finally:
+            for m, w in zip(mods, was):
+                m.training = w
+
+    def _the_net(self):
+        return self._net if self._net is not None else self.model
 
     def _run(self, x):
         if self._net is None:
@@ -190,21 +197,23 @@ class SubjectPredictor:
         return y
 
     def _signature(self, device, channels):
-        net = self._net if self._net is not None else self.model
-        return (device, int(channels), tuple(p.data_ptr() for p in net.parameters()))
+        return (device, channels if isinstance(channels, tuple) else int(channels), tuple(p.data_ptr() for p in self._the_net().parameters()))
 
-    def _prepare(self, volumes):
-        """the static buffers and (graph=True) the captured forward, made again when the weights have moved to other storage"""
-        net = self._net if self._net is not None else self.model
-        device = next(net.parameters()).device
+    def _device_for(self, volumes):
+        device = next(self._the_net().parameters()).device
         if device != volumes.device:
-            raise N3DError("SubjectPredictor: the model is on %s, the volumes on %s" % (device, volumes.device))
-        sig = self._signature(device, volumes.channels)
-        if sig == self._sig:
-            return
-        B, P = self.batch, self.patch
+            raise N3DError("%s: the model is on %s, the volumes on %s" % (self._what, device, volumes.device))
+        return device
+
+    def _drop_forward(self):
+        """let go of the graph and the static buffers (before their successors are allocated: a full-size set is large)"""
+        self._graph = self._y = self._t = self._x = self._ctx = None
+        self._sig = None
+
+    def _make_forward(self, device, x, sig):
+        """a fresh packing context on the static input x and (graph=True) the captured forward"""
         self._ctx = K.StepContext(device)
-        self._x = K.empty_ndhwc(B, volumes.channels, P, P, P, device, torch.float32).zero_()
+        self._x = x
         self._graph = self._y = self._t = None
         if self.use_graph:
             from .train import capture_stream
@@ -230,6 +239,39 @@ class SubjectPredictor:
             return self._y
         return self._pass(self._x)
 
+
+class SubjectPredictor(_ForwardHost):
+    """prediction.py:64-170 for one subject of a generator.VolumeSet, on the device end to end.
+
+    predict(volumes, index, ...) -> (labels uint8 (FX, FY, FZ), probs float64 (n_labels, FX, FY, FZ) or None).
+    One n3d_patch_qualify launch and one read of its flag bytes per subject (the only host sync) mark the all-zero patches; they are
+    never gathered and never run (the reference's rule, prediction.py:133-135) -- they only count as covering.  The live
+    (corner, key) entries go `batch` at a time: VolumeSet.patch_batch writes the chunk into the static input buffer, the net runs
+    -- graph=True: ONE captured graph of the forward in eval mode, weight packing included, replayed for every chunk of every
+    subject whatever its box -- and n3d_stitch_add adds the chunk to the subject's running fp64 sums, inverting each entry's
+    isometry on the way.  n3d_stitch_finish then writes the labels (skull mask included) and, only if asked for, the fp64 image.
+    keys: isometry keys of datastep.generate_permutation_keys() (None: the identity); the prediction is the mean over every
+    (corner, key) patch, for a net trained with `permute`.
+
+    stats: entries / live / chunks of the last subject; captures / replays / forwards since the predictor was made."""
+    _what = "SubjectPredictor"
+
+    def __init__(self, model, patch=64, batch=8, graph=True, _net=None, _padded=False):
+        self.patch, self.batch = int(patch), int(batch)
+        if not 1 <= self.batch <= 64:
+            raise N3DError("SubjectPredictor: batch must be 1..64 (N3D_PATCH_MAX_BATCH)")
+        self._init_forward(model, graph, _net, _padded)
+        self.stats = types.SimpleNamespace(entries=0, live=0, chunks=0, captures=0, replays=0, forwards=0)
+
+    def _prepare(self, volumes):
+        """the static buffers and (graph=True) the captured forward, made again when the weights have moved to other storage"""
+        device = self._device_for(volumes)
+        sig = self._signature(device, volumes.channels)
+        if sig == self._sig:
+            return
+        B, P = self.batch, self.patch
+        self._make_forward(device, K.empty_ndhwc(B, volumes.channels, P, P, P, device, torch.float32).zero_(), sig)
+
     # -- one subject ------------------------------------------------------------------------------
     def predict(self, volumes, index, overlap=None, both_ps=False, keys=(None,), full_shape=None, origin=(0, 0, 0), threshold=0.5,
                 inclusive_label=True, skull_mask=True, want_probs=False):
@@ -242,11 +284,7 @@ class SubjectPredictor:
         isos = [poststep.IDENTITY if k is None else datastep.isometry_of_key(k) for k in keys]
         box = tuple(volumes.box(index))
         corners = patching(box, (P, P, P), overlap, both_ps)
-        mods = self._modules()
-        was = [m.training for m in mods]
-        try:
-            for m in mods:
-                m.training = False
+        with self._eval_mode():
             self._prepare(volumes)
             # the subject's one host sync: which corners are dead (bit 0 clear: every modality zero)
             flags = volumes.qualify([index] * len(corners), corners, P).cpu().numpy()
@@ -267,11 +305,168 @@ class SubjectPredictor:
                 poststep.stitch_add(y, table, ch.first, ch.last - ch.first, cs.min(axis=0), cs.max(axis=0) + P, sum_, cnt)
             if sum_ is None:
                 # no live patch: the prediction is 0 everywhere (the head's channel count is then the net's to tell)
-                net = self._net if self._net is not None else self.model
-                sum_, cnt = poststep.stitch_buffers(int(net.last_conv[0].conv.weight.shape[0]), box, volumes.device)
+                sum_, cnt = poststep.stitch_buffers(int(self._the_net().last_conv[0].conv.weight.shape[0]), box, volumes.device)
             self.stats.entries, self.stats.live, self.stats.chunks = n, int((plan.slot >= 0).sum()), len(plan.chunks)
-        finally:
-            for m, w in zip(mods, was):
-                m.training = w
         return poststep.stitch_finish(sum_, cnt, full_shape, origin, want_probs, True, threshold, inclusive_label,
                                       volumes.volumes[index] if skull_mask else None)
+
+
+# ---- whole-image inference ---------------------------------------------------------------------------------------------------
+def _u_net(net):
+    """the module that holds stems, cells and head: the net itself, or the supernet's kernel (nas.py:101)"""
+    return getattr(net, "kernel", net)
+
+
+def net_halvings(net):
+    """how many times the net halves its input grid: stem1 and every down cell (searched.py:72,78-83), i.e. depth + 1"""
+    return len(_u_net(net).down_cells) + 1
+
+
+def image_pad(full_shape, halvings, pad=None):
+    """voxels of zero padding at the high end of each axis of a whole-image forward, D = 2 ** halvings (the net must halve the
+    padded grid `halvings` times and double it back onto the skips).  Default: D - F % D, 1..D voxels on EVERY axis -- an axis that
+    is a multiple of D already gets D more: that is the reference's literal (0, 16), (0, 16), (0, 5) at 240 x 240 x 155
+    (prediction.py:116), and since zero padding enters the GroupNorm statistics the amount is part of the result.  An explicit
+    `pad` must make every padded axis a multiple of D."""
+    D = 2 ** int(halvings)
+    full = tuple(int(f) for f in full_shape)
+    if len(full) != 3 or min(full) < 1:
+        raise N3DError("image_pad: full_shape must be three positive sizes, got %s" % (full_shape,))
+    if pad is None:
+        return tuple(D - f % D for f in full)
+    pad = tuple(int(p) for p in pad)
+    if len(pad) != 3 or min(pad) < 0 or any((f + p) % D for f, p in zip(full, pad)):
+        raise N3DError("image_pad: pad %s does not bring every axis of %s to a multiple of %d (the net halves the grid %d times)"
+                       % (pad, full, D, int(halvings)))
+    return pad
+
+
+def image_flip_of_key(key):
+    """the per-axis flip of a whole-image key: None (no flip) or a flip-only key of datastep.generate_permutation_keys() -- rotate
+    (0, 0), transpose 0.  An image that is not a cube has no other isometries onto its own grid."""
+    if key is None:
+        return (False, False, False)
+    try:
+        ok = key in datastep.generate_permutation_keys() and tuple(key[0]) == (0, 0) and key[4] == 0
+    except (TypeError, IndexError):
+        ok = False
+    if not ok:
+        raise N3DError("ImagePredictor: key %r is not None or a flip-only key ((0, 0), fx, fy, fz, 0): rotations and the transpose "
+                       "do not map a non-cubic image onto its own grid" % (key,))
+    perm, flip = datastep.isometry_of_key(key)
+    assert perm == [0, 1, 2]
+    return tuple(bool(f) for f in flip)
+
+
+def image_tensor_fits(voxels, pitch, elem_bytes=4):
+    """may a (voxels x pitch) activation tensor go through the forward?  The MFMA conv kernels for multiples of 16 channels address
+    their operands through buffer resources of 2^31 - 1 bytes with lane byte offsets formed in 32-bit int ((voxel * pitch +
+    channel) * 4; conv_mfma.hip -- they decline from 2^30 bytes on, conv_bf16.hip's from 2^31 - 1), and the gather and
+    weight-gradient kernels count voxels in 32 bits (conv_generic.hip): voxels < 2^31 and voxels * pitch * elem_bytes < 2^31 keep
+    every such offset in range, whichever kernel the plan picks (an fp32 element index then stays below 2^29)."""
+    voxels, pitch = int(voxels), int(pitch)
+    return voxels < 2 ** 31 and voxels * pitch * int(elem_bytes) < 2 ** 31
+
+
+def image_forward_tensors(net, in_channels, padded_shape):
+    """[(name, voxels, channel pitch)] of the widest tensor at each stage of the eval forward at batch 1 on `padded_shape`: the input
+    (padded to a quad), the stems, and per cell its preprocessed inputs (node width) and its output buffer (n_nodes x node width:
+    the nodes are channel slices of it, or its node planes -- the same bytes).  Channel counts that are not multiples of 4 count as
+    their zero-padded twin's (unet.PaddedTwin)."""
+    net = _u_net(net)
+    pad4 = lambda c: (int(c) + 3) // 4 * 4
+
+    def vox(level):
+        return int(np.prod([-(-int(p) // 2 ** level) for p in padded_shape]))
+
+    out_c = lambda conv_ops: pad4(conv_ops.conv.weight.shape[0])
+    res = [("input", vox(0), pad4(in_channels)), ("stem0", vox(0), out_c(net.stem0)), ("stem1", vox(1), out_c(net.stem1))]
+    level = 1
+    for i, cell in enumerate(net.down_cells):
+        res.append(("down_cells.%d inputs" % i, vox(level), pad4(cell.c_node)))
+        level += 1
+        res.append(("down_cells.%d" % i, vox(level), pad4(cell.c_node) * int(cell.n_nodes)))
+    for i, cell in enumerate(net.up_cells):
+        res.append(("up_cells.%d inputs" % i, vox(level), pad4(cell.c_node)))
+        level -= 1
+        res.append(("up_cells.%d" % i, vox(level), pad4(cell.c_node) * int(cell.n_nodes)))
+    res.append(("head", vox(0), int(net.last_conv[0].conv.weight.shape[0])))
+    return res
+
+
+def check_image_size(net, in_channels, padded_shape):
+    """raise N3DError, with the numbers, unless every tensor of the forward on `padded_shape` passes image_tensor_fits (fp32
+    elements: the bf16 configuration stores some of them in half the bytes, the bound is kept at the fp32 figure)"""
+    for name, voxels, pitch in image_forward_tensors(net, in_channels, padded_shape):
+        if not image_tensor_fits(voxels, pitch):
+            raise N3DError("ImagePredictor: %s on a padded image of %s is %d voxels x %d channels x 4 bytes = %d bytes; the conv kernels "
+                           "index a tensor with 32-bit byte offsets and need it below 2^31 = %d (a narrower net, or the patch path)"
+                           % (name, tuple(int(p) for p in padded_shape), voxels, pitch, voxels * pitch * 4, 2 ** 31))
+
+
+class ImagePredictor(_ForwardHost):
+    """prediction.py:102-119 (`fs_pred`, predict(no_patch=True)) for one subject of a generator.VolumeSet, on the device end to end.
+
+    predict(volumes, index, ...) -> (labels uint8 (FX, FY, FZ), probs float64 (n_labels, FX, FY, FZ) or None), as SubjectPredictor.
+    The subject's box is written into the full image zero-padded at the high end (n3d_image_embed; pad: image_pad's rule), the
+    net runs ONCE per key on it -- graph=True: one captured graph of the forward in eval mode, weight packing included, for the
+    most recent padded shape (one entry: a full-size set of activations is large; another shape, or weights in other storage,
+    captures again) -- and n3d_image_finish crops, averages over the keys, and writes labels (skull mask included) and, only if
+    asked for, the fp64 image.  keys: None or flip-only keys (image_flip_of_key); every key but the last goes through
+    n3d_image_add.  An all-zero subject runs no forward (prediction.py:114-115): the far corner of its summed-area table says so,
+    the subject's one host sync.
+
+    stats: captures / replays / forwards since the predictor was made."""
+    _what = "ImagePredictor"
+
+    def __init__(self, model, graph=True, _net=None, _padded=False):
+        self._init_forward(model, graph, _net, _padded)
+        self.stats = types.SimpleNamespace(captures=0, replays=0, forwards=0)
+
+    def _prepare(self, volumes, padded):
+        device = self._device_for(volumes)
+        sig = self._signature(device, (int(volumes.channels),) + tuple(padded))
+        if sig == self._sig:
+            return
+        self._drop_forward()
+        # zeroed once, for the warm-up passes: n3d_image_embed then writes every voxel of it per key
+        self._make_forward(device, K.zeros_ndhwc(1, volumes.channels, *padded, device, torch.float32), sig)
+
+    def predict(self, volumes, index, full_shape=None, origin=None, pad=None, keys=(None,), threshold=0.5, inclusive_label=True,
+                skull_mask=True, want_probs=False):
+        index = int(index)
+        if not 0 <= index < len(volumes):
+            raise N3DError("ImagePredictor: volume index %d outside the set of %d" % (index, len(volumes)))
+        flips = [image_flip_of_key(k) for k in keys]
+        if not flips:
+            raise N3DError("ImagePredictor: need at least one key (None: no flip)")
+        box = tuple(volumes.box(index))
+        if full_shape is None:
+            full_shape = volumes.full_shapes[index]
+        if origin is None:
+            origin = volumes.origins[index]
+        full = tuple(int(f) for f in full_shape) if full_shape is not None else box      # neither recorded nor given: the box is the image
+        org = tuple(int(o) for o in origin) if origin is not None else (0, 0, 0)
+        if len(full) != 3 or len(org) != 3 or any(o < 0 or o + b > f for o, b, f in zip(org, box, full)):
+            raise N3DError("ImagePredictor: the box %s at %s is not inside the image %s" % (box, org, full))
+        net = self._the_net()
+        widths = image_pad(full, net_halvings(net), pad)
+        padded = tuple(f + w for f, w in zip(full, widths))
+        vol = volumes.volumes[index]
+        self._device_for(volumes)
+        check_image_size(net, volumes.channels, padded)      # before anything is allocated or launched
+        # the subject's one host sync: how many voxels of the box have a nonzero modality (the table's far corner)
+        if int(volumes.table(index)[-1, -1, -1, 0]) == 0:
+            n_out = int(_u_net(net).last_conv[0].conv.weight.shape[0])
+            labels = torch.zeros(full, dtype=torch.uint8, device=volumes.device)
+            return labels, (torch.zeros((n_out,) + full, dtype=torch.float64, device=volumes.device) if want_probs else None)
+        with self._eval_mode():
+            self._prepare(volumes, padded)
+            sum_ = None
+            for k, flip in enumerate(flips):
+                poststep.image_embed(vol, org, full, padded, flip, out=self._x)
+                y = self._forward()
+                if k + 1 < len(flips):
+                    sum_ = poststep.image_add(y, full, padded, flip, sum_)
+            return poststep.image_finish(y, full, padded, flip, sum_, len(flips), want_probs, True, threshold, inclusive_label,
+                                         vol if skull_mask else None, org)

@@ -1398,12 +1398,16 @@ class Trainer(_GraphTrainer):
         self.sync.broadcast(self.fp.flat)
 
     # -- subject-level inference -------------------------------------------------------------------
-    def predictor(self, patch=64, batch=8):
+    def predictor(self, patch=64, batch=8, no_patch=False):
         """a predict.SubjectPredictor (prediction.py:64-170 on the device) on the module this trainer's step trains -- its padded
         twin, its storage configuration -- behind a host-visible point (check_sync()).  Its captured forward packs the weights
-        inside the graph, so a predictor made once goes on predicting with the weights as later steps leave them."""
-        from .predict import SubjectPredictor
+        inside the graph, so a predictor made once goes on predicting with the weights as later steps leave them.
+        no_patch=True (the reference's predict(no_patch=True)): a predict.ImagePredictor on the same module -- one forward per subject
+        on the whole padded image; patch and batch do not apply."""
+        from .predict import ImagePredictor, SubjectPredictor
         self.check_sync()
+        if no_patch:
+            return ImagePredictor(self.model, graph=self.use_graph, _net=self.net, _padded=self._twin is not None)
         return SubjectPredictor(self.model, patch, batch, graph=self.use_graph, _net=self.net, _padded=self._twin is not None)
 
     # -- bucket plan ------------------------------------------------------------------------------
