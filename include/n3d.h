@@ -563,6 +563,25 @@ typedef struct n3d_patch_gdesc { n3d_patch_desc d; int32_t vol; } n3d_patch_gdes
 int n3d_patch_gather(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_gdesc* descs, int B, int P, int flags,
                      float* x_out, int64_t xld, void* t_out, void* stream);
 
+/* n3d_patch_gather with the reference's scale / flip distortion (augment.py:50-67, generator.py:208-211) in the same launch.  The
+ * reference crops the patch, flips it on the drawn axes, rescales it around its centre by resampling with nearest neighbour
+ * (nilearn's resample_to_img -> scipy.ndimage.affine_transform with a diagonal matrix, order 0, mode "constant", cval 0), and only
+ * then applies the isometry.  So for output voxel i, on each source axis a:
+ *   j = the patch index the isometry of g.d gives (as n3d_patch_gather);
+ *   unless `identity`:  c = ((double)j + sh[a]) * A[a]   -- scipy's zoom-shift coordinate: an fp64 add, then an fp64 multiply;
+ *                       0 <= c && c <= P-1, tested on c itself, else the voxel is 0 (data and every target);
+ *                       j = (int)floor(c + 0.5);
+ *   with aflip[a]:      j = P-1-j;
+ *   source voxel corner[a] + j, zero outside the volume (as n3d_patch_gather); the same voxel for data and labels.
+ * A: the diagonal of the resampling matrix, finite and nonzero (negative allowed); sh = offset / A, finite; identity != 0: the
+ * patch is not resampled (no scale drawn, or a scale so close to 1 that nilearn returns the image as it is) and A, sh are only
+ * checked.  With identity set and aflip clear everywhere the output is bit-identical to n3d_patch_gather.  descs: HOST array of
+ * at most N3D_PATCH_AUG_MAX_BATCH (the widened descriptors travel in the 4 KB of kernel arguments). */
+#define N3D_PATCH_AUG_MAX_BATCH 32
+typedef struct n3d_patch_adesc { n3d_patch_gdesc g; int32_t aflip[3]; int32_t identity; double A[3]; double sh[3]; } n3d_patch_adesc;
+int n3d_patch_gather_aug(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_adesc* descs, int B, int P, int flags,
+                         float* x_out, int64_t xld, void* t_out, void* stream);
+
 /* ---- the step before the data step (preprocess.py:77-144, create_h5:58-66): raw scanner counts to the statistics of the data
  * set and to each subject's normalised brain-wise box.  raw: DEVICE int16 (Cm, X, Y, Z) contiguous, 2-byte aligned (a modality's
  * base need not be 16-byte aligned: X * Y * Z may be odd); X * Y * Z < 2^31.  "Brain" = the voxels with raw != 0, per modality.

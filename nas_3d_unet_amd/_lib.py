@@ -105,6 +105,11 @@ class GatherDesc(C.Structure):
     _fields_ = [("d", PatchDesc), ("vol", C.c_int32)]
 
 
+class AugDesc(C.Structure):
+    """n3d_patch_adesc (include/n3d.h)"""
+    _fields_ = [("g", GatherDesc), ("aflip", C.c_int32 * 3), ("identity", C.c_int32), ("A", C.c_double * 3), ("sh", C.c_double * 3)]
+
+
 class StitchEntry(C.Structure):
     """n3d_stitch_entry (include/n3d.h)"""
     _fields_ = [("d", PatchDesc), ("slot", C.c_int32)]
@@ -217,6 +222,7 @@ PROTOTYPES = {
     "n3d_volume_sat": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
     "n3d_patch_qualify": (_i, [_p, _i, _p, _i64, _i, _p, _p]),
     "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
+    "n3d_patch_gather_aug": (_i, [_p, _i, _i, C.POINTER(AugDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_brain_scan": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "n3d_brain_sqdev_rows": (_i, [_i64]),
     "n3d_brain_sqdev": (_i, [_p, _i, _i64, _p, _p, _p, _p]),

@@ -3,7 +3,18 @@
 // the 48 cube isometries per patch (augment.py:73-131, the same key for data and truth) and the expansion of the
 // BraTS label volume into three binary channels (generator.py:230-248).  ONE gather launch produces the NDHWC input
 // batch and the target batch straight from the volume resident in HBM: integer index arithmetic, HBM-bound.
+//
+// patch_gather_aug_kernel adds the reference's other augmentation (augment.py:50-67: random axis flips and a random per-axis scale
+// around the patch centre, resampled with nearest neighbour) to the same launch: an output voxel is still one source voxel or
+// zero, so only the index changes -- per axis one fp64 add, multiply, add and floor (scipy's zoom-shift rule, include/n3d.h),
+// each rounded on its own: this file is compiled with -ffp-contract=off (Makefile), its other kernels have no floating-point
+// arithmetic to contract.  It stays HBM-bound: per output voxel 4 * Cv bytes stored (+ 3 or 12 of targets) and at most
+// 4 * Cv + 1 loaded, against 3 fp64 adds + 3 multiplies + 3 floors -- 2 x 4 x 64^3 writes 14.7 MB (fp32 targets) and reads at most
+// 8.9 MB, 3 us at 8 TB/s.  A scale > 1 (A < 1) repeats source voxels and reads fewer source bytes; a scale < 1 (A > 1) reads lines strided along z
+// and leaves a border of zeros.
 #include "n3d_common.h"
+
+#include <cmath>
 
 namespace n3d {
 
@@ -14,22 +25,14 @@ struct GatherDescs { n3d_patch_gdesc d[N3D_PATCH_MAX_BATCH]; };
 // patch_batch_kernel (one volume per launch) and patch_gather_kernel (a volume per patch).  v < P^3.
 // TT: storage of the three target maps -- float, or uint8_t (N3D_PATCH_T_U8: the generator's booleans as bytes, what n3d_head_fwd /
 // n3d_head_bwd read with t_dtype = N3D_U8)
+// the loads, the stores and the label expansion of output voxel v of patch b, given its source voxel s of the volume (ok = false:
+// the patch voxel has no source -- resampled from outside the patch -- and reads as outside the volume does: zero, label 0)
 template <typename TT>
-__device__ __forceinline__ void patch_voxel(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
-                                            const n3d_patch_desc& d, int b, uint32_t v, int P, int inclusive, float* __restrict__ x_out,
-                                            int64_t xld, TT* __restrict__ t_out, FastDiv fP, FastDiv fPP) {
+__device__ __forceinline__ void patch_voxel_store(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
+                                                  const int (&s)[3], bool ok, int b, uint32_t v, int P, int inclusive,
+                                                  float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out) {
   const uint32_t P3 = (uint32_t)P * P * P;
-  uint32_t i0, r, i1, i2;
-  fPP.divmod(v, i0, r);
-  fP.divmod(r, i1, i2);
-  const int idx[3] = {(int)i0, (int)i1, (int)i2};
-  int s[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int t = d.perm[a] == 0 ? idx[0] : (d.perm[a] == 1 ? idx[1] : idx[2]);
-    s[a] = d.corner[a] + (d.flip[a] ? P - 1 - t : t);
-  }
-  const bool in = s[0] >= 0 && s[0] < X && s[1] >= 0 && s[1] < Y && s[2] >= 0 && s[2] < Z;
+  const bool in = ok && s[0] >= 0 && s[0] < X && s[1] >= 0 && s[1] < Y && s[2] >= 0 && s[2] < Z;
   const int64_t sv = in ? ((int64_t)s[0] * Y + s[1]) * Z + s[2] : 0;
   const int64_t XYZ = (int64_t)X * Y * Z;
   float* xo = x_out + ((int64_t)b * P3 + v) * xld;
@@ -51,6 +54,30 @@ __device__ __forceinline__ void patch_voxel(const float* __restrict__ vol, int C
     TT* to = t_out + (int64_t)b * 3 * P3 + v;
     to[0] = c0; to[P3] = c1; to[2 * (int64_t)P3] = c2;
   }
+}
+
+// patch index of output voxel v on source axis a under the isometry of d: j_a = i[perm[a]], or P-1-i[perm[a]] with flip[a]
+__device__ __forceinline__ void patch_index(const n3d_patch_desc& d, uint32_t v, int P, FastDiv fP, FastDiv fPP, int (&j)[3]) {
+  uint32_t i0, r, i1, i2;
+  fPP.divmod(v, i0, r);
+  fP.divmod(r, i1, i2);
+  const int idx[3] = {(int)i0, (int)i1, (int)i2};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int t = d.perm[a] == 0 ? idx[0] : (d.perm[a] == 1 ? idx[1] : idx[2]);
+    j[a] = d.flip[a] ? P - 1 - t : t;
+  }
+}
+
+template <typename TT>
+__device__ __forceinline__ void patch_voxel(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
+                                            const n3d_patch_desc& d, int b, uint32_t v, int P, int inclusive, float* __restrict__ x_out,
+                                            int64_t xld, TT* __restrict__ t_out, FastDiv fP, FastDiv fPP) {
+  int s[3];
+  patch_index(d, v, P, fP, fPP, s);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) s[a] += d.corner[a];
+  patch_voxel_store<TT>(vol, Cv, truth, X, Y, Z, s, true, b, v, P, inclusive, x_out, xld, t_out);
 }
 
 // one thread = one output voxel (b, i0, i1, i2); writes are lane-consecutive along i2 (x: Cv floats per voxel)
@@ -76,6 +103,38 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const n3d_patch_volum
   if (v >= (uint32_t)P * P * P) return;
   const n3d_patch_volume r = vols[g.vol];
   patch_voxel<TT>(r.data, Cv, r.truth, r.dims[0], r.dims[1], r.dims[2], g.d, b, v, P, inclusive, x_out, xld, t_out, fP, fPP);
+}
+
+// patch_gather_kernel with the scale / flip distortion between the isometry and the crop (include/n3d.h, n3d_patch_adesc): patch
+// index j of the isometry -> c = (j + sh) * A, nearest voxel r = floor(c + 0.5) if 0 <= c <= P-1, else no source -> P-1-r on a
+// flipped axis -> corner + r.  One thread = one output voxel, writes lane-consecutive along i2, as the kernels above.
+struct AugDescs { n3d_patch_adesc d[N3D_PATCH_AUG_MAX_BATCH]; };
+
+template <typename TT>
+__global__ __launch_bounds__(256) void patch_gather_aug_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, AugDescs descs, int P, int inclusive,
+                                                               float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out, FastDiv fP,
+                                                               FastDiv fPP) {
+  const int b = blockIdx.y;
+  const n3d_patch_adesc& ad = descs.d[b];
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= (uint32_t)P * P * P) return;
+  const n3d_patch_volume r = vols[ad.g.vol];
+  int s[3];
+  patch_index(ad.g.d, v, P, fP, fPP, s);
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    int q = s[a];
+    if (!ad.identity) {
+      // scipy's zoom-shift coordinate: add, then multiply, each rounded to fp64; the bounds test is on the unrounded coordinate
+      const double c = ((double)q + ad.sh[a]) * ad.A[a];
+      const bool inside = 0.0 <= c && c <= (double)(P - 1);
+      ok = ok && inside;
+      q = inside ? (int)floor(c + 0.5) : 0;
+    }
+    s[a] = ad.g.d.corner[a] + (ad.aflip[a] ? P - 1 - q : q);
+  }
+  patch_voxel_store<TT>(r.data, Cv, r.truth, r.dims[0], r.dims[1], r.dims[2], s, ok, b, v, P, inclusive, x_out, xld, t_out);
 }
 
 }  // namespace n3d
@@ -139,6 +198,42 @@ extern "C" int n3d_patch_gather(const n3d_patch_volume* vols, int nvol, int Cv, 
                        (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   else
     N3D_LAUNCH(patch_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, gd, P, inclusive, x_out, xld,
+                       (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_patch_gather_aug(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_adesc* descs, int B, int P, int flags,
+                                    float* x_out, int64_t xld, void* t_out, void* stream) {
+  N3D_CHECK_ARG(vols && descs && x_out && nvol >= 1 && Cv >= 1 && P > 0 && B >= 1 && xld >= Cv, "patch_gather_aug: bad args");
+  N3D_CHECK_ARG(B <= N3D_PATCH_AUG_MAX_BATCH, "patch_gather_aug: at most N3D_PATCH_AUG_MAX_BATCH = %d patches per call (got %d)",
+                N3D_PATCH_AUG_MAX_BATCH, B);
+  N3D_CHECK_ARG((int64_t)P * P * P < (1ll << 31), "patch_gather_aug: patch too large");
+  static_assert(sizeof(AugDescs) + 64 <= 4096, "the descriptors travel by value in the kernel arguments (4 KB)");
+  AugDescs ad;
+  for (int i = 0; i < B; ++i) {
+    const n3d_patch_adesc& d = descs[i];
+    ad.d[i] = d;
+    N3D_CHECK_ARG(d.g.vol >= 0 && d.g.vol < nvol, "patch_gather_aug: descriptor %d names volume %d of a set of %d", i, d.g.vol, nvol);
+    int seen = 0;
+    for (int a = 0; a < 3; ++a) {
+      N3D_CHECK_ARG(d.g.d.perm[a] >= 0 && d.g.d.perm[a] < 3, "patch_gather_aug: perm entries must be 0..2");
+      seen |= 1 << d.g.d.perm[a];
+      N3D_CHECK_ARG(std::isfinite(d.A[a]) && d.A[a] != 0.0 && std::isfinite(d.sh[a]),
+                    "patch_gather_aug: descriptor %d axis %d: A must be finite and nonzero and sh finite (got %g, %g)", i, a, d.A[a], d.sh[a]);
+    }
+    N3D_CHECK_ARG(seen == 7, "patch_gather_aug: perm must be a permutation of (0,1,2)");
+  }
+  for (int i = B; i < N3D_PATCH_AUG_MAX_BATCH; ++i) ad.d[i] = ad.d[0];
+  N3D_CHECK_ARG((flags & ~(N3D_PATCH_INCLUSIVE | N3D_PATCH_T_U8)) == 0, "patch_gather_aug: unknown flag bits %d", flags);
+  const uint32_t P3 = (uint32_t)P * P * P;
+  const int inclusive = flags & N3D_PATCH_INCLUSIVE;
+  const dim3 grid((unsigned)cdiv(P3, 256), B);
+  if (flags & N3D_PATCH_T_U8)
+    N3D_LAUNCH(patch_gather_aug_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, ad, P, inclusive, x_out, xld,
+                       (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  else
+    N3D_LAUNCH(patch_gather_aug_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, ad, P, inclusive, x_out, xld,
                        (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   N3D_LAUNCH_CHECK();
   return N3D_OK;

@@ -10,13 +10,19 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
   * Generator reproduces the reference class's epoch exactly, random stream included: the overlap drawn per epoch, the candidate
     order, the shuffle and pop() from the end, one isometry key per KEPT patch, the batch boundaries and the smaller last batch,
     steps_per_epoch -- and produces each batch with ONE n3d_patch_gather launch (patches of different volumes in one batch), no
-    host sync and no host -> device copy per batch.
+    host sync and no host -> device copy per batch;
+  * augment=True (the reference's scale / flip distortion, augment.py:50-67, applied to the crop ahead of the isometry) draws
+    from numpy's generator exactly as the reference does and composes the resampling into the same single launch
+    (n3d_patch_gather_aug): draw_augment, scale_affine, resample_transform and resample_params below are the reference's and
+    nilearn's fp64 host arithmetic; the resampler is scipy.ndimage.affine_transform's rule for a diagonal matrix (order 0, mode
+    "constant") restated -- nilearn itself was never run against this package.
 
-Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify and n3d_patch_gather (include/n3d.h).
+Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather and n3d_patch_gather_aug (include/n3d.h).
 """
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 import random
 
 import numpy as np
@@ -24,12 +30,13 @@ import torch
 
 from . import _lib, datastep, predict, preprocess
 from . import kernels as K
-from ._lib import GatherDesc, N3DError, PatchDesc, PatchVolume, check
+from ._lib import AugDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, check
 
 # augment.py:95-100 draws from list(set(...)): that (deterministic) order, NOT the sorted one of datastep.random_permutation_key
 KEYS = list(datastep.generate_permutation_keys())
 LABELS = [1, 2, 4]
 MAX_BATCH = 64      # N3D_PATCH_MAX_BATCH
+AUG_MAX_BATCH = 32  # N3D_PATCH_AUG_MAX_BATCH: the widened descriptors of an augmented batch travel in 4 KB of kernel arguments
 
 _ISO = {None: ([0, 1, 2], [False, False, False])}
 
@@ -65,11 +72,66 @@ def kept_mask(flags, skip_health):
     return keep
 
 
-def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False):
+def draw_augment(np_rng, distortion_factor=0.25, flip=True):
+    """do_augment's draws (augment.py:26-39,55-57) from an np.random-like object, in the reference's order: the per-axis scale
+    np_rng.normal(1, distortion_factor, 3) unless distortion_factor is None, then one np_rng.choice([True, False]) per axis if
+    `flip`.  Returns (scale (3,) float64 or None, list of flipped axes -- None without `flip`)."""
+    scale = np_rng.normal(1, distortion_factor, 3) if distortion_factor is not None else None
+    axes = [a for a in range(3) if np_rng.choice([True, False])] if flip else None
+    return scale, axes
+
+
+def check_affine(affine):
+    """the data set's affine as a (4, 4) float64 array (None: identity); its 3x3 part must be diagonal -- what the gather resamples
+    is one source voxel per axis index"""
+    M = np.eye(4) if affine is None else np.array(affine, dtype=np.float64)
+    if M.shape != (4, 4) or not np.isfinite(M).all():
+        raise N3DError("Generator: affine must be a finite 4x4 array (got shape %s)" % (M.shape,))
+    if not np.all(np.diag(np.diag(M[:3, :3])) == M[:3, :3]):
+        raise N3DError("Generator: augment=True supports affines whose 3x3 part is diagonal; got\n%s" % M)
+    return M
+
+
+def scale_affine(affine, P, scale):
+    """scale_image (augment.py:8-13) of a P^3 image with affine `affine`: the affine of the rescaled image"""
+    M, s, n = np.asarray(affine, dtype=np.float64), np.asarray(scale), np.array((P, P, P))
+    N = M.copy()
+    N[:3, :3] = M[:3, :3] * s                                       # column a scaled by s[a]
+    N[:3, 3] = M[:3, 3] + (n * np.diag(M)[:3] * (1 - s)) / 2        # ... around the centre, in this order of operations
+    return N
+
+
+def resample_transform(affine, P, scale):
+    """what nilearn's resample_to_img(scale_image(img, scale), img) hands to scipy for a P^3 image: (A, b, identity).  identity:
+    no scale was drawn, or np.allclose(affine, scaled affine) -- nilearn returns the image as it is (A = 1, b = 0 then).  Otherwise
+    T = inv(scaled affine) . affine, A = diag(T[:3, :3]) (scipy's 1-D matrix), b = T[:3, 3] (its offset).  A singular scaled affine
+    raises numpy.linalg.LinAlgError as in the reference; a T that is not diagonal raises N3DError."""
+    M = np.asarray(affine, dtype=np.float64)
+    if scale is None:
+        return np.ones(3), np.zeros(3), True
+    N = scale_affine(M, P, scale)
+    if np.allclose(M, N):
+        return np.ones(3), np.zeros(3), True
+    T = np.linalg.inv(N).dot(M)
+    if not np.all(np.diag(np.diag(T[:3, :3])) == T[:3, :3]):
+        raise N3DError("Generator: the resampling matrix of scale %s under this affine is not diagonal" % (scale,))
+    return np.diag(T[:3, :3]).copy(), T[:3, 3].copy(), False
+
+
+def resample_params(affine, P, scale):
+    """(A, sh, identity) of n3d_patch_adesc: resample_transform with sh = b / A, the division scipy.ndimage.affine_transform does
+    in numpy before its zoom-shift loop"""
+    A, b, identity = resample_transform(affine, P, scale)
+    return A, b / A, identity
+
+
+def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None):
     """generator.py:170-217 on qualification flags: yields each batch as a list of (candidate index, isometry key or None).
     The candidate order is shuffled at the first next() (rng.shuffle, if `shuffle`), then pop()ped from the end; a kept candidate
     draws its key (rng.choice over KEYS, if `permute`) when it is popped; a batch is yielded when full, or when the list is empty.
-    skip_health: the caller's skip_health AND the set has truth (without truth the reference skips nothing as healthy)."""
+    skip_health: the caller's skip_health AND the set has truth (without truth the reference skips nothing as healthy).
+    augment: None, or (np_rng, distortion_factor, flip): a kept candidate then draws draw_augment(...) just before its key
+    (generator.py:208-214), and the batch entries are (candidate index, key, (scale, flipped axes))."""
     keep = kept_mask(flags, skip_health).tolist()
     order = list(range(len(keep)))
     if shuffle:
@@ -78,7 +140,8 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
     while order:
         i = order.pop()
         if keep[i]:
-            batch.append((i, rng.choice(KEYS) if permute else None))
+            aug = (draw_augment(*augment),) if augment is not None else ()      # drawn before the key
+            batch.append((i, rng.choice(KEYS) if permute else None) + aug)
         if len(batch) == batch_size or (not order and batch):
             yield batch
             batch = []
@@ -194,21 +257,36 @@ class VolumeSet:
         return (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == target_dtype and t.is_contiguous()
                 and tuple(t.shape) == (B, 3, P, P, P))
 
-    def patch_batch(self, refs, patch, inclusive_label=False, target_dtype=torch.float32, out=None):
+    def patch_batch(self, refs, patch, inclusive_label=False, target_dtype=torch.float32, out=None, augment=None):
         """One batch whose patches come from any volumes of the set: refs = [(volume index, corner, isometry key or None)].
         What datastep.patch_batch makes of each patch on its own volume, bit for bit, in ONE n3d_patch_gather launch on the current
         stream.  Returns (x, t): x (B, Cv, P, P, P) fp32 in NDHWC storage, t (B, 3, P, P, P) of target_dtype (None without truth).
-        out=(x, t): written in place (NDHWC x, contiguous t; t's dtype then decides the target dtype), as datastep.patch_batch."""
+        out=(x, t): written in place (NDHWC x, contiguous t; t's dtype then decides the target dtype), as datastep.patch_batch.
+        augment: None, or one entry per ref -- None, or (A, sh, identity, flipped axes) as resample_params gives them: the crop
+        of that ref is flipped on those axes and resampled (include/n3d.h, n3d_patch_adesc) ahead of its isometry.  With some
+        entry not None the batch is ONE n3d_patch_gather_aug launch (at most 32 patches); otherwise exactly the launch above."""
         if target_dtype not in (torch.float32, torch.uint8):
             raise N3DError("VolumeSet.patch_batch: targets are float32 or uint8")
         B, P = len(refs), int(patch)
         if B < 1 or not self.volumes:
             raise N3DError("VolumeSet.patch_batch: need at least one patch of a non-empty set")
-        descs = (GatherDesc * B)()
+        augmented = augment is not None and any(a is not None for a in augment)
+        if augmented and len(augment) != B:
+            raise N3DError("VolumeSet.patch_batch: one augmentation (or None) per ref")
+        if augmented and B > AUG_MAX_BATCH:
+            raise N3DError("VolumeSet.patch_batch: an augmented batch holds at most %d patches (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
+        descs = ((AugDesc if augmented else GatherDesc) * B)()
         for i, (v, corner, key) in enumerate(refs):
             perm, flip = _isometry(key)
-            descs[i] = GatherDesc(PatchDesc((C.c_int32 * 3)(*[int(c) for c in corner]), (C.c_int32 * 3)(*perm),
-                                            (C.c_int32 * 3)(*[int(f) for f in flip])), int(v))
+            g = GatherDesc(PatchDesc((C.c_int32 * 3)(*[int(c) for c in corner]), (C.c_int32 * 3)(*perm),
+                                     (C.c_int32 * 3)(*[int(f) for f in flip])), int(v))
+            if not augmented:
+                descs[i] = g
+                continue
+            A, sh, identity, axes = augment[i] if augment[i] is not None else ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0), True, None)
+            aflip = [int(a in axes) for a in range(3)] if axes else [0, 0, 0]
+            descs[i] = AugDesc(g, (C.c_int32 * 3)(*aflip), int(bool(identity)), (C.c_double * 3)(*[float(a) for a in A]),
+                               (C.c_double * 3)(*[float(h) for h in sh]))
         Cv = self.channels
         if out is not None:
             x, t = out
@@ -230,28 +308,40 @@ class VolumeSet:
             t = torch.empty((B, 3, P, P, P), dtype=target_dtype, device=self.device) if self.has_truth else None
             xv = K.as_view(x)
         flags = (_lib.PATCH_INCLUSIVE if inclusive_label else 0) | (_lib.PATCH_T_U8 if target_dtype == torch.uint8 else 0)
-        check(_lib.load().n3d_patch_gather(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
-                                           K.stream_ptr()), "n3d_patch_gather")
+        if augmented:
+            check(_lib.load().n3d_patch_gather_aug(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
+                                                   K.stream_ptr()), "n3d_patch_gather_aug")
+        else:
+            check(_lib.load().n3d_patch_gather(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
+                                               K.stream_ptr()), "n3d_patch_gather")
         return x, t
 
 
 class Generator:
     """generator.py:68-217 (class Generator) over a VolumeSet.  The reference's signature, except: `data_file` is a VolumeSet (its
-    indices are the reference's h5 key indices); the file-only arguments (affine_file, spe_file, augment_flip,
-    augment_distortion_factor) are gone; augment=True (nilearn distortions) is not built; labels is None or [1, 2, 4]; patches are
-    cubic.  rng: any random.Random-like object (default: the `random` module, as the reference) -- it sees exactly the reference's
-    calls: randint (overlap, per epoch_init), shuffle (per epoch), choice (one key per kept patch with permute).
+    indices are the reference's h5 key indices); spe_file is gone; affine_file is `affine`, the 4x4 array itself (np.load of that
+    file; None: the identity); labels is None or [1, 2, 4]; patches are cubic.  rng: any random.Random-like object (default: the
+    `random` module, as the reference) -- it sees exactly the reference's calls: randint (overlap, per epoch_init), shuffle (per
+    epoch), choice (one key per kept patch with permute).
+
+    augment=True: the reference's scale / flip distortion of every kept patch (augment.py:50-67), ahead of its isometry: a scale
+    drawn per axis around the patch centre (augment_distortion_factor: the standard deviation around 1, None: no scale), axis flips
+    (augment_flip), data and truth resampled alike with nearest neighbour.  np_rng: any np.random-like object (default: the
+    np.random module, as the reference -- its global generator, NOT `random`): it sees normal(1, factor, 3) and then three
+    choice([True, False]) per kept patch, just before rng's key draw.  The affine's 3x3 part must be diagonal and batch_size at
+    most 32 (N3D_PATCH_AUG_MAX_BATCH); a `data_file` whose patch_batch takes no `augment` raises NotImplementedError at
+    construction.  The resampler is scipy.ndimage.affine_transform's rule as nilearn calls it (order 0, mode "constant"),
+    restated in the kernel; nilearn itself was never run against it.
 
     epoch_init(): one n3d_patch_qualify launch and one device -> host copy of the candidates' flag bytes.
-    epoch(out=None): a generator of (x, t) device tensors (t None without truth), one n3d_patch_gather launch per batch on the
-    current stream.  out: a tuple (x, t) or a zero-argument callable returning one (e.g. trainer.input_buffers), evaluated per
+    epoch(out=None): a generator of (x, t) device tensors (t None without truth), one n3d_patch_gather launch per batch
+    (n3d_patch_gather_aug with augment) on the current stream.  out: a tuple (x, t) or a zero-argument callable returning one (e.g. trainer.input_buffers), evaluated per
     batch; a batch is written into it when it fits (shape, dtype, NDHWC x), else -- None entries, the smaller last batch -- into
     fresh tensors.  A batch written into a trainer's buffers is overwritten by the next next(): step on it first."""
 
     def __init__(self, indices_list, volumes, patch_shape, patch_overlap=None, batch_size=1, labels=None, augment=False, permute=False,
-                 shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None):
-        if augment:
-            raise NotImplementedError("Generator: augment=True (the nilearn scale / flip distortions, augment.py:50-67) is not built")
+                 shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None,
+                 augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None):
         if labels is not None and list(labels) != LABELS:
             raise N3DError("Generator: labels must be None or [1, 2, 4] (the three BraTS regions the kernels expand)")
         ps = [patch_shape] * 3 if isinstance(patch_shape, int) else [int(p) for p in patch_shape]
@@ -261,6 +351,20 @@ class Generator:
             raise N3DError("Generator: batch_size must be 1..%d" % MAX_BATCH)
         if target_dtype not in (torch.float32, torch.uint8):
             raise N3DError("Generator: targets are float32 or uint8")
+        if augment and int(batch_size) > AUG_MAX_BATCH:
+            raise N3DError("Generator: batch_size must be 1..%d with augment=True (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
+        self.affine = check_affine(affine) if augment else affine
+        if augment:
+            # fail here, not in the middle of an epoch with draws already consumed: the batches are made by volumes.patch_batch,
+            # and a volume set that stands in for VolumeSet may not have the augmented gather
+            gather = getattr(volumes, "patch_batch", None)
+            if gather is None or "augment" not in inspect.signature(gather).parameters:
+                raise NotImplementedError("Generator: augment=True needs a volume set whose patch_batch(..., augment=) resamples in "
+                                          "the gather (VolumeSet); %s has none" % type(volumes).__name__)
+        self.augment = bool(augment)
+        self.augment_flip = augment_flip
+        self.augment_distortion_factor = augment_distortion_factor
+        self.np_rng = np.random if np_rng is None else np_rng
         self.indices_list = list(indices_list)
         self.volumes = volumes
         self.patch_shape = ps
@@ -296,11 +400,14 @@ class Generator:
 
     def epoch(self, out=None):
         cand = self.candidates
-        for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute):
+        draws = (self.np_rng, self.augment_distortion_factor, self.augment_flip) if self.augment else None
+        for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
+                                 augment=draws):
             o = out() if callable(out) else out
             B = len(batch)
-            refs = [(cand[i, 0], cand[i, 1:], key) for i, key in batch]
+            refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
+            aug = [resample_params(self.affine, self.patch, scale) + (axes,) for _, _, (scale, axes) in batch] if self.augment else None
             fit = o if self.volumes.fits(o, B, self.patch, self.target_dtype) else None
-            yield self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit)
+            yield self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug)
         if self.patch_overlap:
             self.epoch_init()
