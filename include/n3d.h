@@ -213,8 +213,16 @@ int n3d_conv_fwd2(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1, void
  * all are small MFMA problems of one K-split plan, or all one-plane-tile 3x3x3 convs of one channel count in {4, 8} (stride 1 or 2,
  * distinct outputs); otherwise two at a time as n3d_conv_fwd2, a leftover alone.  Results and statistics rows are those of the
  * single calls bit for bit whatever the grouping.  Calls that are not N3D_PREPACKED should bring distinct workspaces: calls that share
- * one are never folded (a folded launch reads every call's packed weights at once) and run one after the other. */
+ * one are never folded (a folded launch reads every call's packed weights at once) and run one after the other.
+ * The one-plane-tile launch also takes the stride-2 transposed forms (n3d_convT_fwd of a stride-2 conv on an exactly doubled grid, the
+ * data gradient of a stride-2 conv), and it is an entry-signal carrier ("Entry signals" below): a signal armed in front of a call whose
+ * weights are N3D_PREPACKED rides in the folded launch; packing launches in front of it issue the signal stand-alone, as for a single conv. */
 int n3d_conv_fwdN(const n3d_conv_fwd_call* calls, int n, void* stream);
+/* 1 exactly when n3d_conv_fwd2(c0, c1, .) would be ONE launch of the one-plane-tile multi-conv kernel (the launch
+ * n3d_conv_fold_counts counts in counts[0]), else 0.  Enqueues nothing and touches no memory: a pure function of the geometries, flags,
+ * pointer alignment, destinations and workspaces of the two calls, decided by the code the launch path itself runs, so a scheduler can
+ * choose between folding two convs and running one of them on another stream without launching anything. */
+int n3d_conv_fwd2_folds(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1);
 
 /* The depthwise 3x3x3 convs of up to N3D_MAX_GROUP_TERMS primitives of a supernet node (one depthwise-separable primitive per
  * edge, cell.py:76-81) in ONE launch.  A job is one gather pass: data_grad = 0: dst[o side] = conv(src[i side]) + bias
@@ -238,6 +246,8 @@ int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
  * the reference runs loss.backward() through every conv's input there): fields x, dw, dbias, in_gate, ws_weight, deferred and
  * flags_weight of the calls are ignored.  One launch where both fit the small-tensor MFMA kernel and dx of c0 != dx of c1. */
 int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream);
+/* the same query as n3d_conv_fwd2_folds for n3d_conv_bwd_data2 (two data gradients into one buffer never fold) */
+int n3d_conv_bwd_data2_folds(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1);
 /* (two small pointwise data gradients with dx of c0 != dx of c1 fold the same way as in n3d_conv_fwd2: one two-job launch)
  * n3d_conv_pointwise_counts: launches of the pointwise kernel / jobs they carried since the library was loaded (a two-job launch
  * counts 1 / 2): lets a test see which path a call took. */

@@ -149,6 +149,8 @@ PROTOTYPES = {
     "n3d_conv_fwdN": (_i, [C.POINTER(ConvFwdCall), _i, _p]),
     "n3d_conv_bwd_both2": (_i, [C.POINTER(ConvBwdCall), C.POINTER(ConvBwdCall), _p]),
     "n3d_conv_bwd_data2": (_i, [C.POINTER(ConvBwdCall), C.POINTER(ConvBwdCall), _p]),
+    "n3d_conv_fwd2_folds": (_i, [C.POINTER(ConvFwdCall), C.POINTER(ConvFwdCall)]),
+    "n3d_conv_bwd_data2_folds": (_i, [C.POINTER(ConvBwdCall), C.POINTER(ConvBwdCall)]),
     "n3d_conv_pointwise_counts": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "n3d_conv_fold_counts": (_i, [C.POINTER(C.c_int64)]),
     "n3d_convT_bwd_both": (_i, [_gp, _p, _i64, _p, _i64, _p, _p, _i64, _i, _p, _sz, _p, _i, _p, _sz, C.POINTER(FinalJob), _p]),

@@ -2075,9 +2075,15 @@ struct VoxCall {  // one conv of a multi-conv launch of the vox family (same lay
   const float* in_gate; const float* relu_src; const float* out_gate; double* stats; void* ws; size_t ws_bytes;
 };
 int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s);
+int mfma_vox_multi_folds(int n, const VoxCall* c);      // 1 = mfma_vox_multi_try would launch (the same decision code)
 // forward call -> gather operands (forward conv = gather with data_grad=false, transposed forward = data_grad=true: run_gather's convention)
 static VoxCall vox_call_fwd(const n3d_conv_fwd_call* c) {
   return VoxCall{c->g, c->transposed != 0, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, nullptr, nullptr, c->stats, c->ws, c->ws_bytes};
+}
+// data-gradient call -> gather operands (data gradient of a conv = gather with data_grad=true, of a transposed conv = data_grad=false)
+static VoxCall vox_call_bwd(const n3d_conv_bwd_call* c) {
+  return VoxCall{c->g, !c->transposed, c->dy, c->dyld, c->w, nullptr, c->dx, c->dxld, c->flags_data & ~N3D_RELU_IN, nullptr, c->relu_src,
+                 c->out_gate, nullptr, c->ws_data, c->ws_data_bytes};
 }
 int mfma_conv_pair_try(const n3d_conv_geom* g0, bool dg0, const float* src0, int64_t sld0, const float* w0, const float* bias0, float* dst0,
                        int64_t dld0, int flags0, const float* gate0, double* stats0, void* ws0, size_t wsb0, const n3d_conv_geom* g1, bool dg1,
@@ -2721,6 +2727,14 @@ int n3d_conv_fwd2(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1, void
   return N3D_OK;
 }
 
+int n3d_conv_fwd2_folds(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1) {
+  if (!c0 || !c1 || !c0->g || !c1->g || !c0->x || !c1->x || !c0->w || !c1->w || !c0->y || !c1->y) return 0;
+  if (check_geom(c0->g, "conv_fwd2_folds") || check_geom(c1->g, "conv_fwd2_folds")) return 0;
+  if (((c0->flags | c1->flags) & N3D_NO_MFMA) || c0->g->depthwise || c1->g->depthwise) return 0;      // n3d_conv_fwd2's own conditions
+  const VoxCall vc[2] = {vox_call_fwd(c0), vox_call_fwd(c1)};
+  return mfma_vox_multi_folds(2, vc);
+}
+
 int n3d_conv_fwdN(const n3d_conv_fwd_call* calls, int n, void* stream) {
   N3D_CHECK_ARG(calls && n >= 1 && n <= 4, "conv_fwdN: 1..4 calls");
   if (n >= 3) {
@@ -2773,12 +2787,7 @@ int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
   if (pair) {
     // data gradient of a conv = gather with data_grad=true, of a transposed conv = gather with data_grad=false (run_gather convention)
     {
-      VoxCall vc[2];
-      for (int i = 0; i < 2; ++i) {
-        const n3d_conv_bwd_call* c = cs[i];
-        vc[i] = VoxCall{c->g, !c->transposed, c->dy, c->dyld, c->w, nullptr, c->dx, c->dxld, c->flags_data & ~N3D_RELU_IN, nullptr, c->relu_src,
-                        c->out_gate, nullptr, c->ws_data, c->ws_data_bytes};
-      }
+      const VoxCall vc[2] = {vox_call_bwd(c0), vox_call_bwd(c1)};
       const int r = mfma_vox_multi_try(2, vc, (hipStream_t)stream);
       if (r < 0) return r;
       if (r == 1) return N3D_OK;
@@ -2816,6 +2825,20 @@ int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
     if (e) return e;
   }
   return N3D_OK;
+}
+
+int n3d_conv_bwd_data2_folds(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1) {
+  if (!c0 || !c1 || !c0->g || !c1->g) return 0;
+  const n3d_conv_bwd_call* cs[2] = {c0, c1};
+  for (int i = 0; i < 2; ++i) {      // n3d_conv_bwd_data2's own conditions
+    const n3d_conv_bwd_call* c = cs[i];
+    if (check_geom(c->g, "conv_bwd_data2_folds") || !c->dy || !c->w || !c->dx) return 0;
+    if (c->transposed && (c->relu_src || c->out_gate)) return 0;
+    if ((c->flags_data & N3D_NO_MFMA) || c->g->depthwise) return 0;
+  }
+  if (c0->dx == c1->dx) return 0;
+  const VoxCall vc[2] = {vox_call_bwd(c0), vox_call_bwd(c1)};
+  return mfma_vox_multi_folds(2, vc);
 }
 
 int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream) {

@@ -1182,21 +1182,20 @@ __host__ __device__ constexpr int vup_count(int dil, int s) { return dil == 2 ? 
 __host__ __device__ constexpr int vup_p(int dil, int s, int i) { return dil == 2 ? 0 : (s == 0 ? i : 1); }
 __host__ __device__ constexpr int vup_k(int dil, int s, int i) { return dil == 2 ? 1 - s : (s == 0 ? 1 + i : 0); }
 
+// the kernel BODY: workgroup wg_raw of the nwg that run this conv (conv_vox_up_kernel: the whole grid; conv_vox_multi_kernel: one
+// job's range of workgroups), as vox64_body / vox_s2_body
 template <int C, int DIL>
-__global__ __launch_bounds__(64, 2) void conv_vox_up_kernel(VupArgs a, EntrySignal es) {
-  entry_signal(es);
-  N3D_CHAIN_PRIO();
+__device__ __forceinline__ void vox_up_body(const VupArgs& a, const int wg_raw, const int nwg, float4* const vlds) {
   constexpr int Q = C / 4;
   constexpr int LD = 3, LH = 6, LW = 18;
   constexpr int PLANE = LH * LW, NPOS = (PLANE + 63) / 64, PSTRIDE = NPOS * 64, QSTRIDE = LD * PSTRIDE;
   constexpr int NW4 = 27 * C * Q, NWI = (NW4 + 63) / 64;
-  extern __shared__ __attribute__((aligned(16))) float4 vlds[];
   float4* tile = vlds;
   float4* wl = vlds + Q * QSTRIDE;
   const int lane = threadIdx.x;
-  int wg = blockIdx.x;
-  {  // XCD-aware placement (see conv_vox64_kernel)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7;
+  int wg = wg_raw;
+  {  // XCD-aware placement (see vox64_body)
+    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7;
     wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (wg >> 3);
   }
   uint32_t ub, utile, ubx, uw, ud, uh;
@@ -1351,6 +1350,14 @@ __global__ __launch_bounds__(64, 2) void conv_vox_up_kernel(VupArgs a, EntrySign
   }
 }
 
+template <int C, int DIL>
+__global__ __launch_bounds__(64, 2) void conv_vox_up_kernel(VupArgs a, EntrySignal es) {
+  entry_signal(es);
+  N3D_CHAIN_PRIO();
+  extern __shared__ __attribute__((aligned(16))) float4 vlds[];
+  vox_up_body<C, DIL>(a, blockIdx.x, gridDim.x, vlds);
+}
+
 struct VupPlan { bool ok; int C, dil, tiles; size_t lds; };
 
 // gather form with den = 2 only (transposed conv forward with stride 2; data gradient of a stride-2 conv) on exactly doubled grids
@@ -1425,34 +1432,56 @@ static int launch_vox_c(VxArgs& a, const VxPlan& p, int B, hipStream_t s) {
 // workgroups, one per SIMD at best, so a launch lasts one fill + 216-432 MFMAs + one store whatever the chip has idle; four of them
 // back to back cost 4 x 6.5 us, side by side ~9 (profiles/r05_search_table.log).  Workgroup L belongs to the job whose range
 // [start[k], start[k+1]) holds it and runs that job's kernel BODY (vox64_body / vox_s2_body) on the job's own arguments: results, statistics
-// rows and workspace use are exactly those of the single launches.  Only the one-plane tile forms (38-59 VGPRs) are folded: the
-// deep-tile instantiations hold 130-190 registers and would set the occupancy of every job in the launch.
+// rows and workspace use are exactly those of the single launches.  Only the one-plane tile forms are folded (38-59 VGPRs, and the up
+// form, vox_up_body, which sets the launch's register count: still one tile per SIMD and two waves per SIMD): the deep-tile
+// instantiations of vox64_body hold 130-190 registers on 2048 and more waves, which already fill both slots of every SIMD.
+// The launch is an entry-signal carrier like the single launches (n3d_common.h).
 // ------------------------------------------------------------------------------------------------
-struct VoxMultiArgs { VxArgs x[4]; Vs2Args s[4]; int kind[4]; int start[5]; };
-enum { VOXK_S1_D1 = 0, VOXK_S1_D2 = 1, VOXK_S2_D1 = 2, VOXK_S2_D2 = 3, VOXK_S2_TD2_D1 = 4, VOXK_S2_TD2_D2 = 5 };
+struct VoxMultiArgs { VxArgs x[4]; Vs2Args s[4]; VupArgs u[4]; int kind[4]; int start[5]; };
+static_assert(sizeof(VoxMultiArgs) + sizeof(EntrySignal) <= 4096, "conv_vox_multi_kernel: the argument block must stay under the 4 KB the runtime takes");
+enum { VOXK_S1_D1 = 0, VOXK_S1_D2 = 1, VOXK_S2_D1 = 2, VOXK_S2_D2 = 3, VOXK_S2_TD2_D1 = 4, VOXK_S2_TD2_D2 = 5, VOXK_UP_D1 = 6, VOXK_UP_D2 = 7 };
+
+// job k's descriptor out of the kernel arguments: a switch over constant indices (a run-time index, or the array handed to a function by
+// reference, makes the compiler copy the whole argument block to scratch)
+#define N3D_VOX_MULTI_PICK(dst_, arr_) \
+  switch (k) { case 0: dst_ = q.arr_[0]; break; case 1: dst_ = q.arr_[1]; break; case 2: dst_ = q.arr_[2]; break; default: dst_ = q.arr_[3]; break; }
 
 template <int C>
-__global__ __launch_bounds__(64, 2) void conv_vox_multi_kernel(VoxMultiArgs q) {
+__global__ __launch_bounds__(64, 2) void conv_vox_multi_kernel(VoxMultiArgs q, EntrySignal es) {
+  entry_signal(es);
   N3D_CHAIN_PRIO();
   extern __shared__ __attribute__((aligned(16))) float4 vlds[];
   const int L = blockIdx.x;
   const int k = (L >= q.start[1]) + (L >= q.start[2]) + (L >= q.start[3]);
-  // the job's descriptor is copied out of the kernel arguments by a switch (static indexing), then ONE body per kind
-  VxArgs xa; Vs2Args sa; int kind, s0, s1;
+  // ONE body per kind; the job's descriptor is copied out of the kernel arguments inside the kind's branch, so a path holds one
+  // descriptor in scalar registers, not one of every family
+  int kind, s0, s1;
   switch (k) {
-    case 0: xa = q.x[0]; sa = q.s[0]; kind = q.kind[0]; s0 = q.start[0]; s1 = q.start[1]; break;
-    case 1: xa = q.x[1]; sa = q.s[1]; kind = q.kind[1]; s0 = q.start[1]; s1 = q.start[2]; break;
-    case 2: xa = q.x[2]; sa = q.s[2]; kind = q.kind[2]; s0 = q.start[2]; s1 = q.start[3]; break;
-    default: xa = q.x[3]; sa = q.s[3]; kind = q.kind[3]; s0 = q.start[3]; s1 = q.start[4]; break;
+    case 0: kind = q.kind[0]; s0 = q.start[0]; s1 = q.start[1]; break;
+    case 1: kind = q.kind[1]; s0 = q.start[1]; s1 = q.start[2]; break;
+    case 2: kind = q.kind[2]; s0 = q.start[2]; s1 = q.start[3]; break;
+    default: kind = q.kind[3]; s0 = q.start[3]; s1 = q.start[4]; break;
   }
   const int wg = L - s0, nwg = s1 - s0;
-  switch (kind) {
-    case VOXK_S1_D1: vox64_body<C, 1, 1, 1>(xa, wg, nwg, vlds); break;
-    case VOXK_S1_D2: vox64_body<C, 1, 2, 1>(xa, wg, nwg, vlds); break;
-    case VOXK_S2_D1: vox_s2_body<C, 1, 1>(sa, wg, nwg, vlds); break;
-    case VOXK_S2_D2: vox_s2_body<C, 1, 2>(sa, wg, nwg, vlds); break;
-    case VOXK_S2_TD2_D1: if constexpr (C == 4) vox_s2_body<4, 2, 1>(sa, wg, nwg, vlds); break;
-    default: if constexpr (C == 4) vox_s2_body<4, 2, 2>(sa, wg, nwg, vlds); break;
+  if (kind <= VOXK_S1_D2) {
+    VxArgs xa;
+    N3D_VOX_MULTI_PICK(xa, x)
+    if (kind == VOXK_S1_D1) vox64_body<C, 1, 1, 1>(xa, wg, nwg, vlds);
+    else vox64_body<C, 1, 2, 1>(xa, wg, nwg, vlds);
+  } else if (kind <= VOXK_S2_TD2_D2) {
+    Vs2Args sa;
+    N3D_VOX_MULTI_PICK(sa, s)
+    switch (kind) {
+      case VOXK_S2_D1: vox_s2_body<C, 1, 1>(sa, wg, nwg, vlds); break;
+      case VOXK_S2_D2: vox_s2_body<C, 1, 2>(sa, wg, nwg, vlds); break;
+      case VOXK_S2_TD2_D1: if constexpr (C == 4) vox_s2_body<4, 2, 1>(sa, wg, nwg, vlds); break;
+      default: if constexpr (C == 4) vox_s2_body<4, 2, 2>(sa, wg, nwg, vlds); break;
+    }
+  } else {
+    VupArgs ua;
+    N3D_VOX_MULTI_PICK(ua, u)
+    if (kind == VOXK_UP_D1) vox_up_body<C, 1>(ua, wg, nwg, vlds);
+    else vox_up_body<C, 2>(ua, wg, nwg, vlds);
   }
 }
 
@@ -1472,34 +1501,53 @@ static int vox_multi_kind(const VoxCall& c, int* tiles, size_t* lds) {
     *tiles = v2.tiles; *lds = v2.lds;
     return (v2.td == 2 ? VOXK_S2_TD2_D1 : VOXK_S2_D1) + (v2.dil == 2 ? 1 : 0);
   }
-  if (vup_plan(c.g, c.data_grad).ok) return -1;
+  const VupPlan v3 = vup_plan(c.g, c.data_grad);
+  if (v3.ok) {
+    *tiles = v3.tiles; *lds = v3.lds;
+    return v3.dil == 2 ? VOXK_UP_D2 : VOXK_UP_D1;
+  }
   const VxPlan v = vx_plan(c.g);
   if (!v.ok || v.td != 1 || v.nw != 1) return -1;
   *tiles = v.tiles; *lds = v.lds;
   return v.dil == 2 ? VOXK_S1_D2 : VOXK_S1_D1;
 }
 
-// n = 2..4 independent convs (distinct destinations) in one launch; 1 = launched, 0 = not foldable (nothing touched), < 0 error
-int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
-  if (n < 2 || n > 4) return 0;
-  int kind[4], tiles[4];
+// THE decision whether n convs fold into one launch of conv_vox_multi_kernel (n3d_conv_fwd2_folds / n3d_conv_bwd_data2_folds ask it,
+// mfma_vox_multi_try launches by it): a pure function of geometry, flags, alignment and workspaces
+static bool vox_multi_plan(int n, const VoxCall* c, int* kind, int* tiles, size_t* lds_out) {
+  if (n < 2 || n > 4) return false;
   size_t lds = 0;
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
     size_t l = 0;
     kind[i] = vox_multi_kind(c[i], &tiles[i], &l);
-    if (kind[i] < 0 || c[i].g->Ci != c[0].g->Ci) return 0;
-    if (!c[i].ws || c[i].ws_bytes < (size_t)27 * c[i].g->Ci * c[i].g->Ci * 4) return 0;
+    if (kind[i] < 0 || c[i].g->Ci != c[0].g->Ci) return false;
+    if (!c[i].ws || c[i].ws_bytes < (size_t)27 * c[i].g->Ci * c[i].g->Ci * 4) return false;
     for (int j = 0; j < i; ++j) {
-      if (c[j].dst == c[i].dst) return 0;
+      if (c[j].dst == c[i].dst) return false;
       // ONE kernel reads every call's packed weights: two calls that pack into the same workspace (a C-ABI caller re-using one
       // scratch buffer, fine on the sequential path) would both see the last call's weights -> the sequential path
-      if (c[j].ws == c[i].ws && !((c[j].flags & c[i].flags) & N3D_PREPACKED)) return 0;
+      if (c[j].ws == c[i].ws && !((c[j].flags & c[i].flags) & N3D_PREPACKED)) return false;
     }
     if (l > lds) lds = l;
     total += (int64_t)tiles[i] * c[i].g->B;
   }
-  if (total >= (1ll << 31)) return 0;
+  if (total >= (1ll << 31)) return false;
+  *lds_out = lds;
+  return true;
+}
+
+int mfma_vox_multi_folds(int n, const VoxCall* c) {
+  int kind[4], tiles[4];
+  size_t lds = 0;
+  return vox_multi_plan(n, c, kind, tiles, &lds) ? 1 : 0;
+}
+
+// n = 2..4 independent convs (distinct destinations) in one launch; 1 = launched, 0 = not foldable (nothing touched), < 0 error
+int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
+  int kind[4], tiles[4];
+  size_t lds = 0;
+  if (!vox_multi_plan(n, c, kind, tiles, &lds)) return 0;
   const void* zp = zero_page_ptr();
   if (!zp) return 0;
   const int C = c[0].g->Ci;
@@ -1510,9 +1558,9 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
     const VoxCall& cc = c[k];
     const n3d_conv_geom* g = cc.g;
     float* wq = (float*)cc.ws;
-    const bool s2 = kind[k] >= VOXK_S2_D1;
-    if (i < n && !(cc.flags & N3D_PREPACKED))
-      N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, cc.w, wq, C, (!s2 && cc.data_grad) ? 1 : 0);
+    const bool up = kind[k] >= VOXK_UP_D1, s2 = !up && kind[k] >= VOXK_S2_D1;
+    if (i < n && !(cc.flags & N3D_PREPACKED))      // (the single launchers' conventions: mfma_conv_try)
+      N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, cc.w, wq, C, up ? 2 : ((!s2 && cc.data_grad) ? 1 : 0));
     VxArgs& x = q.x[i];
     x.src = cc.src; x.sld = cc.sld; x.dst = cc.dst; x.dld = cc.dld; x.wq = wq; x.bias = cc.bias; x.D = g->Di; x.H = g->Hi; x.W = g->Wi;
     x.flags = cc.flags; x.stats = cc.stats; x.rows_per_sample = tiles[k]; x.tiles = tiles[k]; x.zero_page = zp;
@@ -1521,13 +1569,18 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
     v.src = cc.src; v.sld = cc.sld; v.D = g->Di; v.H = g->Hi; v.W = g->Wi; v.dst = cc.dst; v.dld = cc.dld; v.oD = g->Do; v.oH = g->Ho; v.oW = g->Wo;
     v.wq = wq; v.bias = cc.bias; v.flags = cc.flags; v.stats = cc.stats; v.rows_per_sample = tiles[k]; v.tiles = tiles[k]; v.zero_page = zp;
     v.fT = FastDiv((uint32_t)tiles[k]); v.fTw = FastDiv((uint32_t)(g->Wo / 16)); v.fTh = FastDiv((uint32_t)(g->Ho / 4));
+    VupArgs& u = q.u[i];      // (the source is the small grid: Do x Ho x Wo of the geometry)
+    u.src = cc.src; u.sld = cc.sld; u.D = g->Do; u.H = g->Ho; u.W = g->Wo; u.dst = cc.dst; u.dld = cc.dld;
+    u.wq = wq; u.bias = cc.bias; u.flags = cc.flags; u.stats = cc.stats; u.rows_per_sample = tiles[k]; u.tiles = tiles[k]; u.zero_page = zp;
+    u.fT = FastDiv((uint32_t)tiles[k]); u.fTw = FastDiv((uint32_t)(g->Wo / 16)); u.fTh = FastDiv((uint32_t)(g->Ho / 4));
     q.kind[i] = kind[k];
     q.start[i] = at;
     if (i < n) at += tiles[k] * g->B;
   }
   q.start[4] = at;
-  if (C == 4) N3D_LAUNCH(conv_vox_multi_kernel<4>, dim3((unsigned)at), dim3(64), lds, s, q);
-  else N3D_LAUNCH(conv_vox_multi_kernel<8>, dim3((unsigned)at), dim3(64), lds, s, q);
+  const EntrySignal es = entry_take(s);      // behind the pack launches, which flush what is armed (as in the single launchers)
+  if (C == 4) N3D_LAUNCH(conv_vox_multi_kernel<4>, dim3((unsigned)at), dim3(64), lds, s, q, es);
+  else N3D_LAUNCH(conv_vox_multi_kernel<8>, dim3((unsigned)at), dim3(64), lds, s, q, es);
   g_fold_launches[0] += 1;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error("conv(vox multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }

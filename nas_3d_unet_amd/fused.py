@@ -325,6 +325,33 @@ SIDE_STEM1_BWD = True   # stem1's backward (parameter gradients only) beside ste
 SIDE_PRE0_BWD = True     # searched cells: the backward of EVERY cell's first preprocess op on the side stream
 SIDE_PAIRS_BOTH = True   # ... and of nodes whose two convs both read node outputs, one conv beside the other (1.756 -> 1.748 ms)
 SIDE_PAIRS_BWD = True   # ... and the data gradients into one preprocess gradient (needs a third stream)
+# A node of a searched cell with C <= 8 whose two 3x3x3 convs libn3d runs as ONE launch (conv_vox_multi_kernel: the one-plane-tile forms)
+# with a SIMD for every wave of the two (K.pair_one_wave_each: down-cell 0 of a 64^3 patch, 2 x 128 waves) issues them together on the main
+# stream -- no fork, no side launch, no join for that node; its two data gradients likewise (P._weight_backward).  Nodes that do not fold
+# (C = 4 at 64^3, the deep-tile forms of the 128^3 steps) or whose waves would share SIMDs (up-cell 3 at 32^3: 1024 + 128 waves, the folded
+# launch costs what conv + signal + join cost the chain) keep the SIDE_PAIRS / SIDE_PAIRS_BOTH forks.
+FOLD_SMALL_PAIRS = True   # (tests and the A/B switch it off to get the forked schedule)
+
+
+def _fold_pair_nodes(plan, xs):
+    """{node} of a searched cell (C <= 8) whose two convs fold into one launch, asked of the library without launching
+    (K.conv_fwd2_folds) once per (node, operand layout) and remembered on the plan.  xs: the cell's states, node Views included."""
+    got = set()
+    cache = plan.__dict__.setdefault("_fold_pairs", {})
+    for node in range(plan.n_nodes):
+        (_, i0, segs0, _, _), (_, i1, segs1, _, _) = plan.edges[2 * node], plan.edges[2 * node + 1]
+        seg0, seg1 = segs0[0][0], segs1[0][0]
+        if not all(isinstance(sg.weight, P.DenseConvW) and P.gn_pairable(sg) and not sg.relu_in for sg in (seg0, seg1)):
+            continue      # (relu_in: the conv call carries N3D_RELU_IN or a materialised input -- not a form the multi launch takes)
+        xa, xb = xs[i0], xs[i1]
+        key = (node, K.FOLD_SHARED_SIMDS) + tuple((x.B, x.C, x.D, x.H, x.W, x.ld, x.dt, x.p.value % 16) for x in (xa, xb))
+        fold = cache.get(key)
+        if fold is None:
+            calls = [sg.weight.fwd_prepare(x, False, None, True)[0] for sg, x in ((seg0, xa), (seg1, xb))]
+            fold = cache[key] = K.conv_fwd2_folds(calls) and K.pair_one_wave_each([(c[0], c[8]) for c in calls])
+        if fold:
+            got.add(node)
+    return got
 
 
 def _early_pair_ops(plan):
@@ -346,6 +373,29 @@ def _early_pair_ops(plan):
         if cands and other_ok:
             got[node] = sorted(cands)[0][1]
     plan._early_pairs = got
+    return got
+
+
+def _fold_pair_nodes_bwd(plan, st, dnodes, dpre):
+    """{node} of a searched cell (C <= 8) whose two data gradients fold into one launch (P._weight_backward with fold_data): asked of the
+    library without launching (K.conv_bwd_data2_folds) once per (node, operand layout) and remembered on the plan"""
+    got = set()
+    cache = plan.__dict__.setdefault("_fold_pairs_bwd", {})
+    for node in range(plan.n_nodes):
+        (_, i0, segs0, _, _), (_, i1, segs1, _, _) = plan.edges[2 * node], plan.edges[2 * node + 1]
+        seg0, seg1 = segs0[0][0], segs1[0][0]
+        s0, s1 = st.saved[2 * node], st.saved[2 * node + 1]
+        if not (s0.kind == "gn" and s1.kind == "gn" and s0.raw.C == s1.raw.C and s0.raw.N == s1.raw.N and K.pair_shape_ok(s0.raw.C)):
+            continue      # (the node's epilogue backwards do not pair: P.pair_backward runs the terms one by one)
+        tg = [dnodes[i - 2] if i >= 2 else dpre[i] for i in (i0, i1)]
+        key = (node, K.FOLD_SHARED_SIMDS) + tuple((v.B, v.C, v.D, v.H, v.W, v.ld, v.dt, v.p.value % 16) for v in (s0.raw, s1.raw, tg[0], tg[1]))
+        fold = cache.get(key)
+        if fold is None:
+            two = [(sg, sv, {"draw": K.like(sv.raw)}, None, (True, t, False)) for sg, sv, t in ((seg1, s1, tg[1]), (seg0, s0, tg[0]))]
+            calls = P.data_pair_calls(two)
+            fold = cache[key] = calls is not None and P.data_pair_folds(calls)
+        if fold:
+            got.add(node)
     return got
 
 
@@ -377,6 +427,14 @@ def _run_forward_impl(plan, x0, x1, alpha1, alpha2, pre0_early=None, planar=Fals
     if plan.pairs:
         # searched cell: each node is one pair (both weight ops, then ONE epilogue launch writing the node slice)
         early = _early_pair_ops(plan) if (SIDE_FWD is not None and SIDE_PAIRS and cn <= 8) else {}
+        folded = set()
+        if FOLD_SMALL_PAIRS and SIDE_FWD is not None and cn <= 8:
+            # (the node buffer is made here instead of at node 0, whose first op reads a preprocess output: the query wants the Views)
+            _, i0, segs0, _, _ = plan.edges[0]
+            out, nodes = _node_buffer(plan, segs0[0][0].weight.out_shape(xs[i0]), xs[i0].t.device, planar)
+            xs.extend(nodes)
+            folded = _fold_pair_nodes(plan, xs)
+            early = {node: e for node, e in early.items() if node not in folded}
         side_res = {}
         if early:
             # C <= 8: the two convs of a node are two launches (no common MFMA problem).  The ones that read a preprocess output do
@@ -394,7 +452,10 @@ def _run_forward_impl(plan, x0, x1, alpha1, alpha2, pre0_early=None, planar=Fals
             if out is None:
                 out, nodes = _node_buffer(plan, seg0.weight.out_shape(xs[i0]), xs[i0].t.device, planar)
                 xs.extend(nodes)
-            if node in side_res:
+            if node in folded:
+                # one launch for both convs (n3d_conv_fwd2 -> conv_vox_multi_kernel) on the main stream
+                s0, s1 = P.pair_forward(seg0, xs[i0], seg1, xs[i1], nodes[node])
+            elif node in side_res:
                 e, res_side, tok = side_res[node]
                 if e == 2 * node:
                     res0, res1 = res_side, P.pair_weight_phase(seg1, xs[i1])
@@ -522,6 +583,12 @@ def _run_backward_nodes(plan, st, dnodes, alpha1, alpha2, need_x0, need_x1, want
         if sb is not None and SIDE_PAIRS_BWD and cn <= 8 and getattr(sb, "split", False):
             writers = [sum(1 for e in plan.edges if e[1] == k) for k in (0, 1)]
             side_idx = 0 if writers[0] > writers[1] else 1
+            if FOLD_SMALL_PAIRS:
+                # a node whose two data gradients are ONE launch has nothing to fork.  All writers of a buffer stay on one stream, so
+                # the side stream is left out only where every node that writes this preprocess gradient folds
+                folded = _fold_pair_nodes_bwd(plan, st, dnodes, dpre)
+                if all(node in folded for node in range(nn) if side_idx in (plan.edges[2 * node][1], plan.edges[2 * node + 1][1])):
+                    side_idx = None
         for node in reversed(range(nn)):
             (_, i0, segs0, _, _), (_, i1, segs1, _, _) = plan.edges[2 * node], plan.edges[2 * node + 1]
             seg0, seg1 = segs0[0][0], segs1[0][0]
@@ -532,7 +599,8 @@ def _run_backward_nodes(plan, st, dnodes, alpha1, alpha2, need_x0, need_x1, want
             if side_idx is not None and side_idx in (i0, i1):
                 items = P.pair_backward_epilogue(seg0, s0, seg1, s1, dnodes[node], (True, t0, a0), (True, t1, a1))
             if items is None:
-                (_, g0), (_, g1) = P.pair_backward(seg0, s0, seg1, s1, dnodes[node], (True, t0, a0), (True, t1, a1))
+                (_, g0), (_, g1) = P.pair_backward(seg0, s0, seg1, s1, dnodes[node], (True, t0, a0), (True, t1, a1),
+                                                   fold_data=FOLD_SMALL_PAIRS and cn <= 8)
             else:
                 it0, it1 = items
                 res = {}

@@ -654,6 +654,11 @@ def conv_k1_norm_bwd_apply_wgrad(g, x: View, w, bias, dout: View, a, b, A, Bc, C
 def conv_fwd2(calls):
     """Two forward convs, one launch where libn3d can fold them (small MFMA problems; two small pointwise convs: one two-job launch of
     conv_point_kernel).  calls = [(g, x, w, bias, y, flags, in_gate, stats, transposed)] * 2"""
+    cs, keep = _fwd2_calls(calls)
+    check(_lib.load().n3d_conv_fwd2(C.byref(cs[0]), C.byref(cs[1]), stream_ptr()), "n3d_conv_fwd2")
+
+
+def _fwd2_calls(calls):
     cs, keep = [], []
     for (g, x, w, bias, y, flags, in_gate, stats, transposed) in calls:
         flags = _cflags(flags, x, y)
@@ -661,7 +666,30 @@ def conv_fwd2(calls):
         keep.append((ws, g))
         cs.append(ConvFwdCall(C.pointer(g), 1 if transposed else 0, flags, x.p.value, x.ld, w.data_ptr(), _vp(bias), y.p.value, y.ld,
                               _vp(in_gate), _vp(stats), wsp.value if hasattr(wsp, "value") else wsp, n))
-    check(_lib.load().n3d_conv_fwd2(C.byref(cs[0]), C.byref(cs[1]), stream_ptr()), "n3d_conv_fwd2")
+    return cs, keep
+
+
+_simds = {}
+FOLD_SHARED_SIMDS = False   # True: pair_one_wave_each says yes to every pair (tests: the folded schedule at patch sizes where no pair passes)
+
+
+def pair_one_wave_each(jobs):
+    """jobs = [(g, transposed forward / data gradient of a plain conv)] of one-wave-tile 3x3x3 convs: do their workgroups (one wave each)
+    together fit one per SIMD of the device?  Then a launch that holds them all lasts as long as its slowest job; beyond that the
+    jobs' waves share SIMDs (two C = 8 jobs at 2 x 32^3, 1152 waves on 1024 SIMDs: 8.8-11 us against 6-7.4 alone, profiles/vox_pair_ab.log)."""
+    if FOLD_SHARED_SIMDS:
+        return True
+    dev = torch.cuda.current_device()
+    if dev not in _simds:
+        _simds[dev] = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
+    return sum(conv_stats_rows(g, up) * g.B for g, up in jobs) <= _simds[dev]
+
+
+def conv_fwd2_folds(calls):
+    """would conv_fwd2(calls) be ONE launch of the one-plane-tile multi-conv kernel (n3d_conv_fwd2_folds)?  Launches nothing: the
+    schedule asks before it decides between folding a node's two convs and forking one of them (fused._run_forward_impl)."""
+    cs, keep = _fwd2_calls(calls)
+    return bool(_lib.load().n3d_conv_fwd2_folds(C.byref(cs[0]), C.byref(cs[1])))
 
 
 def conv_fwdN(calls):
@@ -725,6 +753,11 @@ def conv_bwd_data2(calls):
     """Data gradients of two convs, one launch where libn3d can fold them (distinct dx targets; small-tensor MFMA shapes or two small
     pointwise convs).
     calls = [(g, dy, w, dx, flags, relu_src, out_gate, transposed)] * 2, arguments as conv_bwd_data."""
+    cs, keep = _bwd_data2_calls(calls)
+    check(_lib.load().n3d_conv_bwd_data2(C.byref(cs[0]), C.byref(cs[1]), stream_ptr()), "n3d_conv_bwd_data2")
+
+
+def _bwd_data2_calls(calls):
     cs, keep = [], []
     for (g, dy, w, dx, flags, relu_src, out_gate, transposed) in calls:
         _need_f32("conv_bwd_data2", dy, dx)
@@ -733,7 +766,15 @@ def conv_bwd_data2(calls):
         cs.append(ConvBwdCall(C.pointer(g), 1 if transposed else 0, flags, 0, 0, None, 0, dy.p.value, dy.ld, w.data_ptr(), dx.p.value, dx.ld,
                               relu_src.p.value if relu_src is not None else None, relu_src.ld if relu_src is not None else 0,
                               _vp(out_gate), wsp.value if hasattr(wsp, "value") else wsp, n, None, None, None, None, 0, None))
-    check(_lib.load().n3d_conv_bwd_data2(C.byref(cs[0]), C.byref(cs[1]), stream_ptr()), "n3d_conv_bwd_data2")
+    return cs, keep
+
+
+def conv_bwd_data2_folds(calls):
+    """would conv_bwd_data2(calls) be ONE launch of the one-plane-tile multi-conv kernel (n3d_conv_bwd_data2_folds)?  Launches nothing."""
+    if any(v.dt != _lib.F32 for c in calls for v in (c[1], c[3])):
+        return False
+    cs, keep = _bwd_data2_calls(calls)
+    return bool(_lib.load().n3d_conv_bwd_data2_folds(C.byref(cs[0]), C.byref(cs[1])))
 
 
 def conv_bwd_both(g, x: View, dy: View, w, dx: View, dw, dbias, flags_data=0, relu_src: View | None = None, out_gate=None,

@@ -736,10 +736,11 @@ def pair_epilogue_phase(segA, resA, segB, resB, out, outB=None, accumulate=False
     return sA, sB
 
 
-def pair_backward(segA, sA, segB, sB, dout, argsA, argsB, doutB=None, alphaA=None, alphaB=None):
+def pair_backward(segA, sA, segB, sB, dout, argsA, argsB, doutB=None, alphaA=None, alphaB=None, fold_data=False):
     """Backward of pair_forward.  argsX = (need_dx, dx_out, dx_acc).  Returns ((dxA, gradsA), (dxB, gradsB)) with
     grads ordered like segX.params().  doutB: gradient of segB's own output (independent-outputs mode).
-    alphaX = (alpha row, column, dalpha row | None): MixedOp weight of the term and where its gradient <dout, z> goes."""
+    alphaX = (alpha row, column, dalpha row | None): MixedOp weight of the term and where its gradient <dout, z> goes.
+    fold_data: see _weight_backward."""
     aA = alphaA if alphaA is not None else (None, 0, None)
     aB = alphaB if alphaB is not None else (None, 0, None)
     pair = (sA.kind == "gn" and sB.kind == "gn" and not isinstance(segA.weight, IdentityW) and not isinstance(segB.weight, IdentityW)
@@ -754,7 +755,7 @@ def pair_backward(segA, sA, segB, sB, dout, argsA, argsB, doutB=None, alphaA=Non
     outs = K.affine_act_bwd_gn2(dout, terms, sA.G, doutB)
     # weight-op backward in reverse forward order (B then A), as the unpaired path does
     order = ((segB, sB, terms[1], outs[1], argsB), (segA, sA, terms[0], outs[0], argsA))
-    results = _weight_backward(order)
+    results = _weight_backward(order, fold_data)
     return results[1], results[0]
 
 
@@ -784,10 +785,50 @@ def _gn_bwd_term(seg, s, alpha):
                 draw=K.like(raw))
 
 
-def _weight_backward(order):
+def data_pair_calls(two):
+    """K.conv_bwd_data2 call tuples of two neighbouring `_weight_backward` items if both are plain convs whose data gradients go to
+    given, distinct targets and need nothing but the conv (fold candidates of the one-plane-tile multi launch), else None"""
+    calls = []
+    for seg, s, t, _, (need_dx, dx_out, dx_acc) in two:
+        wp, sv = seg.weight, s.ws
+        if not (isinstance(wp, DenseConvW) and need_dx and dx_out is not None and sv.pre is None and sv.wpad is None
+                and not sv.relu_in and sv.gate is None):
+            return None
+        calls.append((sv.g, t["draw"], wp.m.weight, dx_out, ACCUMULATE if dx_acc else 0, None, None, wp.transposed))
+    if calls[0][3].p.value == calls[1][3].p.value:
+        return None
+    return calls
+
+
+def data_pair_folds(calls):
+    """the schedule's rule for data_pair_calls: one launch where libn3d folds the pair AND every wave of it gets a SIMD of its own"""
+    return K.conv_bwd_data2_folds(calls) and K.pair_one_wave_each([(c[0], not c[7]) for c in calls])
+
+
+def _fold_data_pair(two):
+    """C <= 8 (no launch holds a data and a weight gradient there): the two weight gradients as DenseConvW.bwd issues them, then ONE
+    launch for the two data gradients where libn3d folds them (n3d_conv_bwd_data2 -> conv_vox_multi_kernel).  None: not such a pair."""
+    calls = data_pair_calls(two)
+    if calls is None or not data_pair_folds(calls):
+        return None
+    pre = []
+    for (seg, s, t, (_, _, dcb), _), c in zip(two, calls):
+        wp, sv = seg.weight, s.ws
+        dw = K.grad_target(wp.m.weight)
+        db = None if dcb is not None else K.grad_target(wp.m.bias)
+        if dw is not None or db is not None:
+            K.conv_bwd_weight(sv.g, sv.x, t["draw"], dw, db, 0, None, wp.transposed)
+        pre.append((c[3].t, [dw, db]))
+    K.conv_bwd_data2(calls)
+    return pre
+
+
+def _weight_backward(order, fold_data=False):
     """Weight-op backwards of GroupNorm-type terms whose d(raw) is ready.  order = [(seg, saved, term dict, (dgamma, dbeta,
     dconv_bias), (need_dx, dx_out, dx_acc))] in execution order.  Two neighbouring plain convs with distinct input-gradient
     targets share one launch (data + weight gradients: n3d_conv_bwd_both2; frozen weights: n3d_conv_bwd_data2).
+    fold_data (fused.FOLD_SMALL_PAIRS, searched cells with C <= 8): two neighbouring plain convs that pair in neither way still
+    share ONE data-gradient launch where libn3d folds it (_fold_data_pair).
     Returns [(dx, grads ordered like seg.params())] in the same order."""
     results = []
     i = 0
@@ -804,6 +845,8 @@ def _weight_backward(order):
                 if all(c is not None for c in cands) and cands[0][1].p.value != cands[1][1].p.value:
                     K.conv_bwd_data2([c[0] for c in cands])
                     pre = [(c[1].t, c[2]) for c in cands]
+                elif fold_data:
+                    pre = _fold_data_pair(two)
         npre = 2
         if pre is None and i + 1 < len(order) and isinstance(order[i][0].weight, SEConvW) and isinstance(order[i + 1][0].weight, SEConvW):
             # a run of stride-2 SE convs: conv backwards two per launch, the gate backwards in one launch
