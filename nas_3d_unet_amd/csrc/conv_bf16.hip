@@ -13,7 +13,7 @@
 // The MFMA phase shrinks 4x against the fp32 kernel, the fill moves half the bytes: the kernel is bound by the LDS-DMA fill and
 // HBM, which is where this configuration lives.
 #include <stdlib.h>
-#include "n3d_common.h"
+#include "conv_internal.h"
 
 namespace n3d {
 
@@ -741,38 +741,37 @@ int vox16_stats_rows(const n3d_conv_geom* g, bool data_grad, int flags) {
 }
 
 // 1 = launched, 0 = not applicable, < 0 error
-int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int64_t sld, const float* w, const float* bias, void* dst,
-                   int64_t dld, int flags, const float* in_gate, const void* relu_src, const float* out_gate, double* stats, void* ws,
-                   size_t ws_bytes, hipStream_t s) {
-  const int kind = vox16_kind(g, data_grad, flags);
+int vox16_conv_try(const ConvCall& c, hipStream_t s) {
+  const n3d_conv_geom* g = c.g;
+  const int kind = vox16_kind(g, c.data_grad, c.flags);
   if (!kind) return 0;
   const int C = g->Ci;
-  const bool extras = in_gate || relu_src || out_gate || (flags & N3D_RELU_IN);
-  const bool aligned = sld % 4 == 0 && dld % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 7) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0 &&
-                       (C == 4 || (sld % 8 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0));
+  const bool extras = c.in_gate || c.relu_src || c.out_gate || (c.flags & N3D_RELU_IN);
+  const bool aligned = c.sld % 4 == 0 && c.dld % 4 == 0 && (reinterpret_cast<uintptr_t>(c.src) & 7) == 0 && (reinterpret_cast<uintptr_t>(c.dst) & 7) == 0 &&
+                       (C == 4 || (c.sld % 8 == 0 && (reinterpret_cast<uintptr_t>(c.src) & 15) == 0));
   if (extras || !aligned) {
-    if (stats || (flags & N3D_PREPACKED)) { set_error("conv(bf16 mfma): gate / relu extras or an unaligned tensor on a shape whose statistics rows / packed weights assume this kernel"); return N3D_ERR_UNSUPPORTED; }
+    if (c.stats || (c.flags & N3D_PREPACKED)) { set_error("conv(bf16 mfma): gate / relu extras or an unaligned tensor on a shape whose statistics rows / packed weights assume this kernel"); return N3D_ERR_UNSUPPORTED; }
     return 0;
   }
   const size_t need = (size_t)27 * C * C * 2;
-  if (!ws || ws_bytes < need) { set_error("conv(bf16 mfma): workspace too small"); return N3D_ERR_WORKSPACE; }
+  if (!c.ws || c.ws_bytes < need) { set_error("conv(bf16 mfma): workspace too small"); return N3D_ERR_WORKSPACE; }
   // pack modes: vox64b 0 / 1 (data gradient: transposed + flipped), vox_s2b 0 (forward-type gathers only), vox_upb 2 (transposed)
-  if (!(flags & N3D_PREPACKED))
-    N3D_LAUNCH(pack_vox16_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, w, (bf16_t*)ws, C,
-                       kind == 3 ? 2 : (kind == 1 && data_grad ? 1 : 0));
+  if (!(c.flags & N3D_PREPACKED))
+    N3D_LAUNCH(pack_vox16_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, c.w, (bf16_t*)c.ws, C,
+                       kind == 3 ? 2 : (kind == 1 && c.data_grad ? 1 : 0));
   const void* zp = zero_page16_ptr();
   if (!zp) { set_error("conv(bf16 mfma): zero page symbol unavailable"); return N3D_ERR_HIP; }
   if (kind == 1) {
     // (the fill addresses a sample through a raw buffer resource: 32-bit byte offsets)
-    if ((int64_t)g->Di * g->Hi * g->Wi * sld * 2 >= 0x7fffffffLL) return 0;
+    if ((int64_t)g->Di * g->Hi * g->Wi * c.sld * 2 >= 0x7fffffffLL) return 0;
     const Vx16Plan v = vx16_plan(g);
     Vx16Args a;
-    a.src = (const bf16_t*)src; a.sld = sld; a.dst = (bf16_t*)dst; a.dld = dld; a.wq = (const bf16_t*)ws; a.bias = bias;
-    a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.flags = flags; a.stats = stats; a.rows_per_sample = v.tiles * v.nw; a.tiles = v.tiles; a.zero_page = zp;
+    a.src = (const bf16_t*)c.src; a.sld = c.sld; a.dst = (bf16_t*)c.dst; a.dld = c.dld; a.wq = (const bf16_t*)c.ws; a.bias = c.bias;
+    a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.flags = c.flags; a.stats = c.stats; a.rows_per_sample = v.tiles * v.nw; a.tiles = v.tiles; a.zero_page = zp;
     a.fT = FastDiv((uint32_t)v.tiles); a.fTw = FastDiv((uint32_t)(g->Wi / 16)); a.fTh = FastDiv((uint32_t)(g->Hi / (4 * v.nw)));
-    const bool p2 = v.C == 4 && sld == 4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    const bool p2 = v.C == 4 && c.sld == 4 && (reinterpret_cast<uintptr_t>(c.src) & 15) == 0;
     if (p2 && v.nw == 1 && v.td == 4 && g->Di % 8 == 0 && (int64_t)v.tiles * g->B / 2 >= 2048) {
-      const bool acc = flags & N3D_ACCUMULATE;
+      const bool acc = c.flags & N3D_ACCUMULATE;
       // dense image, many tiles: 8 output planes per tile (the D halo is re-fetched every 8 planes instead of every 4: 24.4 -> 22.1 us at
       // (2,4,128^3)); the kernel still writes one statistics row per 4 planes, in the rows and the order of the 4-plane plan
       a.tiles = v.tiles / 2;
@@ -787,16 +786,15 @@ int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int6
         if (acc) N3D_LAUNCH((conv_vox64b_kernel<4, 8, 2, 1, true, 1>), dim3(a.tiles * g->B), dim3(64), lds8, s, a, es);
         else N3D_LAUNCH((conv_vox64b_kernel<4, 8, 2, 1, true, 0>), dim3(a.tiles * g->B), dim3(64), lds8, s, a, es);
       }
-      hipError_t e__ = hipGetLastError();
-      if (e__ != hipSuccess) { set_error("conv(bf16 mfma): launch error: %s", hipGetErrorString(e__)); return N3D_ERR_HIP; }
+      N3D_LAUNCH_CHECK_AS("conv(bf16 mfma)");
       return 1;
     }
     if (v.C == 4) launch_vox16_c<4>(a, v, g->B, s, p2); else launch_vox16_c<8>(a, v, g->B, s, false);
   } else if (kind == 2) {
-    const Vs2bPlan v = vs2b_plan(g, data_grad);
+    const Vs2bPlan v = vs2b_plan(g, c.data_grad);
     Vs2bArgs a;
-    a.src = (const bf16_t*)src; a.sld = sld; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.dst = (bf16_t*)dst; a.dld = dld; a.oD = g->Do; a.oH = g->Ho; a.oW = g->Wo;
-    a.wq = (const bf16_t*)ws; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v.tiles; a.tiles = v.tiles; a.zero_page = zp;
+    a.src = (const bf16_t*)c.src; a.sld = c.sld; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.dst = (bf16_t*)c.dst; a.dld = c.dld; a.oD = g->Do; a.oH = g->Ho; a.oW = g->Wo;
+    a.wq = (const bf16_t*)c.ws; a.bias = c.bias; a.flags = c.flags; a.stats = c.stats; a.rows_per_sample = v.tiles; a.tiles = v.tiles; a.zero_page = zp;
     a.fT = FastDiv((uint32_t)v.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
     const dim3 grid(v.tiles * g->B), blk(64);
     const EntrySignal es = entry_take(s);
@@ -807,18 +805,17 @@ int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int6
       if (v.dil == 1) N3D_LAUNCH((conv_vox_s2b_kernel<8, 1, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_s2b_kernel<8, 1, 2>), grid, blk, v.lds, s, a, es);
     }
   } else {
-    const VupbPlan v = vupb_plan(g, data_grad);
+    const VupbPlan v = vupb_plan(g, c.data_grad);
     VupbArgs a;
-    a.src = (const bf16_t*)src; a.sld = sld; a.D = g->Do; a.H = g->Ho; a.W = g->Wo; a.dst = (bf16_t*)dst; a.dld = dld;
-    a.wq = (const bf16_t*)ws; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v.tiles; a.tiles = v.tiles; a.zero_page = zp;
+    a.src = (const bf16_t*)c.src; a.sld = c.sld; a.D = g->Do; a.H = g->Ho; a.W = g->Wo; a.dst = (bf16_t*)c.dst; a.dld = c.dld;
+    a.wq = (const bf16_t*)c.ws; a.bias = c.bias; a.flags = c.flags; a.stats = c.stats; a.rows_per_sample = v.tiles; a.tiles = v.tiles; a.zero_page = zp;
     a.fT = FastDiv((uint32_t)v.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
     const dim3 grid(v.tiles * g->B), blk(64);
     const EntrySignal es = entry_take(s);
     if (v.C == 4) { if (v.dil == 1) N3D_LAUNCH((conv_vox_upb_kernel<4, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_upb_kernel<4, 2>), grid, blk, v.lds, s, a, es); }
     else { if (v.dil == 1) N3D_LAUNCH((conv_vox_upb_kernel<8, 1>), grid, blk, v.lds, s, a, es); else N3D_LAUNCH((conv_vox_upb_kernel<8, 2>), grid, blk, v.lds, s, a, es); }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(bf16 mfma) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(bf16 mfma)");
   return 1;
 }
 

@@ -5,7 +5,7 @@
 // from the packed [tap][cs][cd] copy; activations are 16-byte vector loads of NDHWC voxels.
 // These kernels cover every shape of the path; the MFMA kernels in conv_mfma.hip take over the
 // FLOP-heavy 3x3x3 shapes.
-#include "n3d_common.h"
+#include "conv_internal.h"
 #define N3D_WG16_SLABS 1024   // 256-float partial slabs reserved for the gemm16 weight-gradient kernels (+ one per tile)
 #include <algorithm>
 #include <atomic>
@@ -2030,66 +2030,14 @@ static int check_geom(const n3d_conv_geom* g, const char* who) {
   return 0;
 }
 
-namespace n3d {
-// implemented in conv_mfma.hip: returns 1 if it handled the call, 0 to fall through, <0 on error
-int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
-                  int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate, double* stats,
-                  void* ws, size_t ws_bytes, hipStream_t s);
-int mfma_conv_stats_rows(const n3d_conv_geom* g, bool data_grad, int flags);
-extern std::atomic<int64_t> g_fold_launches[5];
-// bf16-storage vox64 family (conv_bf16.hip)
-int vox16_layout(const n3d_conv_geom* g, bool data_grad, int flags);
-int vox16_stats_rows(const n3d_conv_geom* g, bool data_grad, int flags);
-int vox16_conv_try(const n3d_conv_geom* g, bool data_grad, const void* src, int64_t sld, const float* w, const float* bias, void* dst,
-                   int64_t dld, int flags, const float* in_gate, const void* relu_src, const float* out_gate, double* stats, void* ws,
-                   size_t ws_bytes, hipStream_t s);
-int mfma_pack_layout(const n3d_conv_geom* g, bool data_grad, int flags);  // 1 gemm16, 2 vox64, 0 none
-int vox_wgrad_try(const n3d_conv_geom* g, const float* x, int64_t xld, const float* dy, int64_t dyld, int flags, const float* in_gate,
-                  float* partial, size_t avail_floats, int* nchunks_out, hipStream_t s);
-int vox_wgrad_s2_try(const n3d_conv_geom* g, const float* x, int64_t xld, const float* dy, int64_t dyld, int flags, const float* in_gate,
-                     float* partial, size_t avail_floats, int* nchunks_out, hipStream_t s);
-struct Wg16Args;
-int wgrad_tile16_try(const n3d_conv_geom* g, const float* x, int64_t xld, const float* dy, int64_t dyld, int flags, const float* in_gate,
-                     float* partial, size_t avail_floats, int* nchunks_out, float** pbias_out, hipStream_t s);
-bool wgrad_tile16_plan(const n3d_conv_geom* g, int* chunks, int* tiles_per_wg, int* tw_out = nullptr);
-int mfma_wgrad_try(const n3d_conv_geom* g, const float* x, int64_t xld, const float* dy, int64_t dyld, int flags, const float* in_gate,
-                   float* partial, float* pbias, size_t avail_floats, int* nchunks_out, int* ntiles_out, hipStream_t s,
-                   Wg16Args* prepared = nullptr);
-struct DualArgs;
-int mfma_bwd_dual_try(const n3d_conv_geom* g, bool transposed, const float* dy, int64_t dyld, const float* wp_packed, float* dx,
-                      int64_t dxld, int flags_d, const float* relu_src, int64_t rld, const float* out_gate, const float* x, int64_t xld,
-                      int flags_w, const float* in_gate, float* partial, float* pbias, size_t avail_floats, int* nchunks_out,
-                      int* ntiles_out, hipStream_t s, DualArgs* prepared = nullptr, int* ksplit_out = nullptr);
-int mfma_bwd_quad_ok(const n3d_conv_geom* g0, bool t0, const n3d_conv_geom* g1, bool t1);
-struct BwdOne {  // one conv's backward operands for the quad launch (same layout as in conv_mfma.hip)
-  const n3d_conv_geom* g; bool transposed; const float* dy; int64_t dyld; const float* wp; float* dx; int64_t dxld; int flags_d;
-  const float* relu_src; int64_t rld; const float* out_gate; const float* x; int64_t xld; int flags_w; const float* in_gate;
-  float* partial; float* pbias; size_t avail; int nch, ntl;
-};
-int mfma_bwd_quad_try(BwdOne* c0, BwdOne* c1, hipStream_t s);
-int mfma_conv_multi_try(int n, const n3d_conv_geom* const* g, const bool* dg, const float* const* src, const int64_t* sld, const float* const* w,
-                        const float* const* bias, float* const* dst, const int64_t* dld, const int* flags, const float* const* gate,
-                        double* const* stats, void* const* ws, const size_t* wsb, hipStream_t s);
-struct VoxCall {  // one conv of a multi-conv launch of the vox family (same layout as in conv_mfma.hip)
-  const n3d_conv_geom* g; bool data_grad; const float* src; int64_t sld; const float* w; const float* bias; float* dst; int64_t dld; int flags;
-  const float* in_gate; const float* relu_src; const float* out_gate; double* stats; void* ws; size_t ws_bytes;
-};
-int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s);
-int mfma_vox_multi_folds(int n, const VoxCall* c);      // 1 = mfma_vox_multi_try would launch (the same decision code)
 // forward call -> gather operands (forward conv = gather with data_grad=false, transposed forward = data_grad=true: run_gather's convention)
-static VoxCall vox_call_fwd(const n3d_conv_fwd_call* c) {
-  return VoxCall{c->g, c->transposed != 0, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, nullptr, nullptr, c->stats, c->ws, c->ws_bytes};
+static ConvCall conv_call_fwd(const n3d_conv_fwd_call* c) {
+  return ConvCall{c->g, c->transposed != 0, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, nullptr, 0, nullptr, c->stats, c->ws, c->ws_bytes};
 }
 // data-gradient call -> gather operands (data gradient of a conv = gather with data_grad=true, of a transposed conv = data_grad=false)
-static VoxCall vox_call_bwd(const n3d_conv_bwd_call* c) {
-  return VoxCall{c->g, !c->transposed, c->dy, c->dyld, c->w, nullptr, c->dx, c->dxld, c->flags_data & ~N3D_RELU_IN, nullptr, c->relu_src,
-                 c->out_gate, nullptr, c->ws_data, c->ws_data_bytes};
-}
-int mfma_conv_pair_try(const n3d_conv_geom* g0, bool dg0, const float* src0, int64_t sld0, const float* w0, const float* bias0, float* dst0,
-                       int64_t dld0, int flags0, const float* gate0, double* stats0, void* ws0, size_t wsb0, const n3d_conv_geom* g1, bool dg1,
-                       const float* src1, int64_t sld1, const float* w1, const float* bias1, float* dst1, int64_t dld1, int flags1,
-                       const float* gate1, double* stats1, void* ws1, size_t wsb1, hipStream_t s, const PairExtras* x0, const PairExtras* x1);
-void mfma_pack16(const float* w, float* wp, int Co, int Ci, int taps, int data_grad, hipStream_t s);
+static ConvCall conv_call_bwd(const n3d_conv_bwd_call* c) {
+  return ConvCall{c->g, !c->transposed, c->dy, c->dyld, c->w, nullptr, c->dx, c->dxld, c->flags_data & ~N3D_RELU_IN, nullptr, c->relu_src, c->rld,
+                  c->out_gate, nullptr, c->ws_data, c->ws_data_bytes};
 }
 
 // request to fold the data gradient into the weight-gradient launch (n3d_conv_bwd_both)
@@ -2156,32 +2104,28 @@ static DwArgs dw_args(const n3d_conv_geom* g, bool data_grad, const float* src, 
                       int64_t dld, int flags) {
   DwArgs a;
   a.C = g->Ci; a.w = w; a.bias = bias; a.k = g->k; a.flags = flags;
-  if (!data_grad) { a.src = src; a.sld = sld; a.Ds = g->Di; a.Hs = g->Hi; a.Ws = g->Wi; a.dst = dst; a.dld = dld; a.Dd = g->Do; a.Hd = g->Ho; a.Wd = g->Wo;
-    a.sn = g->stride; a.off = -g->pad; a.dt = g->dil; a.den = 1; }
-  else { a.src = src; a.sld = sld; a.Ds = g->Do; a.Hs = g->Ho; a.Ws = g->Wo; a.dst = dst; a.dld = dld; a.Dd = g->Di; a.Hd = g->Hi; a.Wd = g->Wi;
-    a.sn = 1; a.off = g->pad; a.dt = -g->dil; a.den = g->stride; }
+  a.src = src; a.sld = sld; a.dst = dst; a.dld = dld;
+  const GatherGeom m = gather_geom(g, data_grad);
+  a.Ds = m.Ds; a.Hs = m.Hs; a.Ws = m.Ws; a.Dd = m.Dd; a.Hd = m.Hd; a.Wd = m.Wd; a.sn = m.sn; a.off = m.off; a.dt = m.dt; a.den = m.den;
   a.fcpb = FastDiv((uint32_t)(a.C / 4)); a.fWd = FastDiv((uint32_t)a.Wd); a.fHd = FastDiv((uint32_t)a.Hd);
   return a;
 }
 
-// extras of n3d_conv_k1_norm_fwd for the 1x1x1 streaming kernel (set around its run_gather call on the calling thread)
+// extras of n3d_conv_k1_norm_fwd for the 1x1x1 streaming kernel; run_gather sets `used` when that kernel took them
 struct K1Norm { const float* oscale; const float* oshift; bool nostore; bool used; };
-static thread_local K1Norm* g_k1_norm = nullptr;
 
 // a pointwise job held back by run_gather for a two-job launch (n3d_conv_fwd2 / n3d_conv_bwd_data2)
 // `before`: the held job of the pair's earlier call -- launched first if this call turns out to launch in place, so the pair keeps its order
 struct PointHold { PointJob job; int B; bool held; PointHold* before; };
 
-static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
-                      int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate,
-                      double* stats, void* ws, size_t ws_bytes, void* stream, PointHold* hold = nullptr) {
+static int run_gather(const ConvCall& c, hipStream_t s, K1Norm* k1n = nullptr, PointHold* hold = nullptr) {
   if (hold) hold->held = false;
-  hipStream_t s = (hipStream_t)stream;
-  const bool sb16 = flags & N3D_SRC_BF16, db16 = flags & N3D_DST_BF16;
+  const n3d_conv_geom* g = c.g;
+  const bool sb16 = c.flags & N3D_SRC_BF16, db16 = c.flags & N3D_DST_BF16;
   if (g->depthwise) {
-    N3D_CHECK_ARG(!in_gate && !relu_src && !out_gate && !stats && !(flags & N3D_RELU_IN), "depthwise conv: gate/relu/stats not supported");
-    N3D_CHECK_ARG(sld % 4 == 0 && dld % 4 == 0 && aligned_quad(src, sb16) && aligned_quad(dst, db16), "depthwise conv: needs quad-aligned pitched rows");
-    DwArgs a = dw_args(g, data_grad, src, sld, w, bias, dst, dld, flags);
+    N3D_CHECK_ARG(!c.in_gate && !c.relu_src && !c.out_gate && !c.stats && !(c.flags & N3D_RELU_IN), "depthwise conv: gate/relu/stats not supported");
+    N3D_CHECK_ARG(c.sld % 4 == 0 && c.dld % 4 == 0 && aligned_quad(c.src, sb16) && aligned_quad(c.dst, db16), "depthwise conv: needs quad-aligned pitched rows");
+    DwArgs a = dw_args(g, c.data_grad, c.src, c.sld, c.w, c.bias, c.dst, c.dld, c.flags);
     const int64_t Nd = (int64_t)a.Dd * a.Hd * a.Wd;
     const dim3 grid((unsigned)cdiv(Nd * (a.C / 4), 256), g->B);
     const size_t shm = (size_t)(a.C / 4) * 27 * sizeof(float4);
@@ -2194,77 +2138,74 @@ static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, 
     return N3D_OK;
   }
   // node-planar operands (a pitch smaller than the channel count; include/n3d.h): only the 1x1x1 streaming kernel reads / writes them
-  const int Cs_all = data_grad ? g->Co : g->Ci, Cd_all = data_grad ? g->Ci : g->Co;
-  const bool src_planar = sld > 0 && sld < Cs_all, dst_planar = dst && dld > 0 && dld < Cd_all;     // (dst NULL: the statistics-only pass of n3d_conv_k1_norm_fwd)
+  const int Cs_all = c.data_grad ? g->Co : g->Ci, Cd_all = c.data_grad ? g->Ci : g->Co;
+  const bool src_planar = c.sld > 0 && c.sld < Cs_all, dst_planar = c.dst && c.dld > 0 && c.dld < Cd_all;     // (dst NULL: the statistics-only pass of n3d_conv_k1_norm_fwd)
   if (src_planar || dst_planar) {
-    const bool ok = g->k == 1 && g->stride == 1 && sld >= 4 && dld >= 4 && sld % 4 == 0 && dld % 4 == 0 && Cs_all % sld == 0 && Cd_all % dld == 0 &&
-                    !in_gate && !out_gate && (!dst_planar || (data_grad && !bias && !stats && (!relu_src || rld == dld))) &&
-                    k1_dims_ok(g, data_grad, Cs_all, dst_planar ? (int)dld : Cd_all);
+    const bool ok = g->k == 1 && g->stride == 1 && c.sld >= 4 && c.dld >= 4 && c.sld % 4 == 0 && c.dld % 4 == 0 && Cs_all % c.sld == 0 && Cd_all % c.dld == 0 &&
+                    !c.in_gate && !c.out_gate && (!dst_planar || (c.data_grad && !c.bias && !c.stats && (!c.relu_src || c.rld == c.dld))) &&
+                    k1_dims_ok(g, c.data_grad, Cs_all, dst_planar ? (int)c.dld : Cd_all);
     if (!ok) N3D_UNSUPPORTED("conv: node-planar operands (pitch < channels) are taken by the 1x1x1 streaming kernel only (stride 1, no gates, "
                              "<= 24 source / <= 12 destination channels per launch, >= 32768 voxels)");
   }
-  if (!(flags & N3D_NO_MFMA) && !src_planar && !dst_planar) {
-    int r = mfma_conv_try(g, data_grad, src, sld, w, bias, dst, dld, flags, in_gate, relu_src, rld, out_gate, stats, ws, ws_bytes, s);
+  if (!(c.flags & N3D_NO_MFMA) && !src_planar && !dst_planar) {
+    int r = mfma_conv_try(c, s);
     if (r != 0) return r < 0 ? r : N3D_OK;
   }
   if (sb16 && db16 && !src_planar && !dst_planar) {
-    int r = vox16_conv_try(g, data_grad, src, sld, w, bias, dst, dld, flags, in_gate, relu_src, out_gate, stats, ws, ws_bytes, s);
+    int r = vox16_conv_try(c, s);
     if (r != 0) return r < 0 ? r : N3D_OK;
   }
   const int taps = g->k * g->k * g->k;
   GatherArgs a;
-  a.bias = bias; a.k = g->k; a.flags = flags; a.in_gate = in_gate; a.relu_src = relu_src; a.rld = rld; a.out_gate = out_gate; a.stats = stats;
-  a.src = src; a.sld = sld; a.dst = dst; a.dld = dld;
-  if (!data_grad) { a.Ds = g->Di; a.Hs = g->Hi; a.Ws = g->Wi; a.Cs = g->Ci; a.Dd = g->Do; a.Hd = g->Ho; a.Wd = g->Wo; a.Cd = g->Co;
-    a.sn = g->stride; a.off = -g->pad; a.dt = g->dil; a.den = 1; }
-  else { a.Ds = g->Do; a.Hs = g->Ho; a.Ws = g->Wo; a.Cs = g->Co; a.Dd = g->Di; a.Hd = g->Hi; a.Wd = g->Wi; a.Cd = g->Ci;
-    a.sn = 1; a.off = g->pad; a.dt = -g->dil; a.den = g->stride; }
+  a.bias = c.bias; a.k = g->k; a.flags = c.flags; a.in_gate = c.in_gate; a.relu_src = c.relu_src; a.rld = c.rld; a.out_gate = c.out_gate; a.stats = c.stats;
+  a.src = c.src; a.sld = c.sld; a.dst = c.dst; a.dld = c.dld;
+  set_gather_geom(a, gather_geom(g, c.data_grad));
   a.fWd = FastDiv((uint32_t)a.Wd); a.fHd = FastDiv((uint32_t)a.Hd);
   const int cot = pick_cot(a.Cd);
   a.Cdp = (int)align_up(a.Cd, cot);
   const size_t need = (size_t)taps * a.Cs * a.Cdp * 4;
-  if (!ws || ws_bytes < need) { set_error("conv: workspace too small (%zu < %zu)", ws_bytes, need); return N3D_ERR_WORKSPACE; }
-  float* wp = (float*)ws;
+  if (!c.ws || c.ws_bytes < need) { set_error("conv: workspace too small (%zu < %zu)", c.ws_bytes, need); return N3D_ERR_WORKSPACE; }
+  float* wp = (float*)c.ws;
   a.wp = wp;
   const int total = taps * a.Cs * a.Cdp;
-  if (!(flags & N3D_PREPACKED))
-    N3D_LAUNCH(pack_weights_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, g->Co, g->Ci, taps, a.Cdp, data_grad ? 1 : 0);
-  if (stats && gather_class_mode(a.den, a.k, a.Dd, a.Hd, a.Wd, a.Cs, true) && !((a.Cs % 4 == 0) && (a.sld % 4 == 0) && aligned_quad(a.src, sb16))) {
+  if (!(c.flags & N3D_PREPACKED))
+    N3D_LAUNCH(pack_weights_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, c.w, wp, g->Co, g->Ci, taps, a.Cdp, c.data_grad ? 1 : 0);
+  if (c.stats && gather_class_mode(a.den, a.k, a.Dd, a.Hd, a.Wd, a.Cs, true) && !((a.Cs % 4 == 0) && (a.sld % 4 == 0) && aligned_quad(a.src, sb16))) {
     set_error("conv: statistics on this shape need a 16-byte aligned source (n3d_conv_stats_rows assumed the parity-class kernel)");
     return N3D_ERR_UNSUPPORTED;
   }
-  const int cd_eff = dst_planar ? (int)dld : a.Cd;       // destination channels of one launch slice (blockIdx.z = node)
-  if (k1_dims_ok(g, data_grad, a.Cs, cd_eff)) {
-    const bool nostore = g_k1_norm && g_k1_norm->nostore;
-    const bool fits = !in_gate && !out_gate && sld % 4 == 0 && (nostore || (dld % 4 == 0 && aligned_quad(dst, db16))) && aligned_quad(src, sb16) && aligned16(a.wp) &&
-                      (!bias || aligned16(bias)) && (!relu_src || (rld % 4 == 0 && aligned_quad(relu_src, db16))) && a.Cdp % 4 == 0 &&
-                      !(a.den == 2 && (bias || stats));   // the zero-upsampling form carries neither
+  const int cd_eff = dst_planar ? (int)c.dld : a.Cd;       // destination channels of one launch slice (blockIdx.z = node)
+  if (k1_dims_ok(g, c.data_grad, a.Cs, cd_eff)) {
+    const bool nostore = k1n && k1n->nostore;
+    const bool fits = !c.in_gate && !c.out_gate && c.sld % 4 == 0 && (nostore || (c.dld % 4 == 0 && aligned_quad(c.dst, db16))) && aligned_quad(c.src, sb16) && aligned16(a.wp) &&
+                      (!c.bias || aligned16(c.bias)) && (!c.relu_src || (c.rld % 4 == 0 && aligned_quad(c.relu_src, db16))) && a.Cdp % 4 == 0 &&
+                      !(a.den == 2 && (c.bias || c.stats));   // the zero-upsampling form carries neither
     if (fits) {
       K1Args q;
-      q.src = src; q.sld = sld; q.dst = dst; q.dld = dld; q.wp = a.wp; q.Cdp = a.Cdp; q.bias = bias; q.flags = flags; q.relu_src = relu_src;
-      q.rld = rld; q.stats = stats; q.N = (int64_t)a.Dd * a.Hd * a.Wd;
+      q.src = c.src; q.sld = c.sld; q.dst = c.dst; q.dld = c.dld; q.wp = a.wp; q.Cdp = a.Cdp; q.bias = c.bias; q.flags = c.flags; q.relu_src = c.relu_src;
+      q.rld = c.rld; q.stats = c.stats; q.N = (int64_t)a.Dd * a.Hd * a.Wd;
       q.up = a.den == 2 ? 1 : 0; q.Wd = a.Wd; q.Hd = a.Hd; q.Ns = (int64_t)a.Ds * a.Hs * a.Ws; q.fWd = a.fWd; q.fHd = a.fHd;
       {
         constexpr bool noflat = false;
         const size_t esz = db16 ? 2 : 4;
         // fp32 destinations only: measured at 2 x 128^3, 12-channel writes 54.5 -> 42.5 us (fp32) but 31.1 -> 35.2 us (bf16: the 8-byte LDS
         // stores on a 24-byte pitch cost more than the partial-line stores they replace)
-        q.flat = (!noflat && !db16 && cd_eff >= 8 && dld == cd_eff && aligned16(dst) && ((size_t)q.N * cd_eff * esz) % 16 == 0) ? 1 : 0;
+        q.flat = (!noflat && !db16 && cd_eff >= 8 && c.dld == cd_eff && aligned16(c.dst) && ((size_t)q.N * cd_eff * esz) % 16 == 0) ? 1 : 0;
       }
       {
         constexpr bool nosparse = false;
         q.nostore = 0; q.oscale = q.oshift = nullptr;
-        if (g_k1_norm) { q.nostore = g_k1_norm->nostore ? 1 : 0; q.oscale = g_k1_norm->oscale; q.oshift = g_k1_norm->oshift; g_k1_norm->used = true; if (q.nostore) q.flat = 0; }
-        q.sparse = (q.up && (flags & N3D_ACCUMULATE) && !nosparse) ? 1 : 0;
+        if (k1n) { q.nostore = k1n->nostore ? 1 : 0; q.oscale = k1n->oscale; q.oshift = k1n->oshift; k1n->used = true; if (q.nostore) q.flat = 0; }
+        q.sparse = (q.up && (c.flags & N3D_ACCUMULATE) && !nosparse) ? 1 : 0;
         q.fWs = FastDiv((uint32_t)(a.Wd >> 1)); q.fHs = FastDiv((uint32_t)(a.Hd >> 1));
         if (q.sparse) q.flat = 0;
       }
-      const bool extra = (flags & N3D_ACCUMULATE) || relu_src || q.up;
-      N3D_CHECK_ARG(!(extra && (stats || q.oscale || q.nostore)), "conv(1x1x1): statistics / output coefficients together with accumulate / relu mask are not supported");
+      const bool extra = (c.flags & N3D_ACCUMULATE) || c.relu_src || q.up;
+      N3D_CHECK_ARG(!(extra && (c.stats || q.oscale || q.nostore)), "conv(1x1x1): statistics / output coefficients together with accumulate / relu mask are not supported");
       // node-planar operands: node k of a tensor starts k * (B * voxels * pitch) elements behind node 0
-      q.src_node_stride = src_planar ? (int64_t)g->B * q.N * sld : 0;
-      q.dst_node_stride = dst_planar ? (int64_t)g->B * q.N * dld : 0;
-      q.relu_node_stride = (dst_planar && relu_src) ? (int64_t)g->B * q.N * rld : 0;
+      q.src_node_stride = src_planar ? (int64_t)g->B * q.N * c.sld : 0;
+      q.dst_node_stride = dst_planar ? (int64_t)g->B * q.N * c.dld : 0;
+      q.relu_node_stride = (dst_planar && c.relu_src) ? (int64_t)g->B * q.N * c.rld : 0;
       const dim3 grid((unsigned)cdiv(q.sparse ? q.Ns : q.N, extra ? 512 : K1_VPB), (unsigned)g->B, (unsigned)(a.Cd / cd_eff));
       switch (a.Cs / 4) {
         case 1: launch_k1_c<1>(q, cd_eff, grid, s); break;
@@ -2277,7 +2218,7 @@ static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, 
       N3D_LAUNCH_CHECK();
       return N3D_OK;
     }
-    if (stats && g->stride == 1) {
+    if (c.stats && g->stride == 1) {
       set_error("conv: statistics on this 1x1x1 shape need the streaming kernel (no gates, 16-byte aligned rows): n3d_conv_stats_rows assumed it");
       return N3D_ERR_UNSUPPORTED;
     }
@@ -2285,7 +2226,7 @@ static int run_gather(const n3d_conv_geom* g, bool data_grad, const float* src, 
   {
     // small pointwise convs (conv_point_kernel): the weights are packed by now, the launch may be left to the caller (hold)
     PointJob pj;
-    if (!src_planar && !dst_planar && !g_k1_norm && point_job(a, g->B, &pj)) {
+    if (!src_planar && !dst_planar && !k1n && point_job(a, g->B, &pj)) {
       if (hold) { hold->job = pj; hold->B = g->B; hold->held = true; return N3D_OK; }
       launch_point(&pj, g->B, nullptr, 0, s);
       N3D_LAUNCH_CHECK();
@@ -2329,11 +2270,35 @@ static int point_pair_finish(PointHold* h, hipStream_t s) {
   return N3D_OK;
 }
 
+// one forward call as the single entry points run it (n3d_conv_fwd / n3d_convT_fwd, and the calls of n3d_conv_fwd2 / fwdN that do not fold)
+static int run_fwd_call(const n3d_conv_fwd_call* c, void* stream) {
+  const n3d_conv_geom* g = c->g;
+  if (c->transposed) {
+    if (int e = check_geom(g, "convT_fwd")) return e;
+    N3D_CHECK_ARG(c->x && c->w && c->y && c->xld >= g->Co && c->yld >= g->Ci, "convT_fwd: bad pointers/pitches");
+  } else {
+    if (int e = check_geom(g, "conv_fwd")) return e;
+    N3D_CHECK_ARG(c->x && c->w && c->y && (c->xld >= g->Ci || (c->xld >= 4 && g->Ci % c->xld == 0)) && c->yld >= g->Co, "conv_fwd: bad pointers/pitches");
+  }
+  return run_gather(conv_call_fwd(c), (hipStream_t)stream);
+}
+// the same for a data gradient (n3d_conv_bwd_data / n3d_convT_bwd_data, and the calls of n3d_conv_bwd_data2 that do not fold)
+static int run_bwd_data_call(const n3d_conv_bwd_call* c, void* stream) {
+  const n3d_conv_geom* g = c->g;
+  if (c->transposed) {
+    if (int e = check_geom(g, "convT_bwd_data")) return e;
+    N3D_CHECK_ARG(c->dy && c->w && c->dx && c->dyld >= g->Ci && c->dxld >= g->Co, "convT_bwd_data: bad pointers/pitches");
+  } else {
+    if (int e = check_geom(g, "conv_bwd_data")) return e;
+    N3D_CHECK_ARG(c->dy && c->w && c->dx && c->dyld >= g->Co && (c->dxld >= g->Ci || (c->dxld >= 4 && g->Ci % c->dxld == 0)), "conv_bwd_data: bad pointers/pitches");
+  }
+  return run_gather(conv_call_bwd(c), (hipStream_t)stream);
+}
+
 int n3d_conv_fwd(const n3d_conv_geom* g, const float* x, int64_t xld, const float* w, const float* bias, float* y, int64_t yld, int flags,
                  const float* in_gate, double* stats, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = check_geom(g, "conv_fwd")) return e;
-  N3D_CHECK_ARG(x && w && y && (xld >= g->Ci || (xld >= 4 && g->Ci % xld == 0)) && yld >= g->Co, "conv_fwd: bad pointers/pitches");
-  return run_gather(g, false, x, xld, w, bias, y, yld, flags, in_gate, nullptr, 0, nullptr, stats, ws, ws_bytes, stream);
+  const n3d_conv_fwd_call c = {g, 0, flags, x, xld, w, bias, y, yld, in_gate, stats, ws, ws_bytes};
+  return run_fwd_call(&c, stream);
 }
 
 static void fill_job(n3d_final_job* j, const float* partial, const float* pbias, float* dw, float* dbias, int nch, int ntl, int tci, int tco,
@@ -2349,10 +2314,8 @@ int n3d_conv_k1_norm_fwd(const n3d_conv_geom* g, const float* x, int64_t xld, co
   N3D_CHECK_ARG((oscale == nullptr) == (oshift == nullptr) && !(stats && oscale), "conv_k1_norm_fwd: oscale and oshift come together, without statistics");
   if (!n3d_conv_k1_norm_ok(g)) N3D_UNSUPPORTED("conv_k1_norm_fwd: 1x1x1 stride-1 convs with (Ci, Co) in {(4,4), (4,8), (4,12), (8,4)} on >= 32768 voxels");
   K1Norm nx = {oscale, oshift, y == nullptr, false};
-  g_k1_norm = &nx;
-  const int r = run_gather(g, false, x, xld, w, bias, y, yld, flags | N3D_NO_MFMA, nullptr, nullptr, 0, nullptr, stats, ws, ws_bytes, stream);
-  g_k1_norm = nullptr;
-  if (r) return r;
+  const ConvCall c = {g, false, x, xld, w, bias, y, yld, flags | N3D_NO_MFMA, nullptr, nullptr, 0, nullptr, stats, ws, ws_bytes};
+  if (int r = run_gather(c, (hipStream_t)stream, &nx)) return r;
   if (!nx.used) N3D_UNSUPPORTED("conv_k1_norm_fwd: the operands do not fit the 1x1x1 streaming kernel (alignment / pitches)");
   return N3D_OK;
 }
@@ -2396,24 +2359,23 @@ int n3d_conv_k1_norm_bwd_apply_wgrad(const n3d_conv_geom* g, const void* x, int6
 
 int n3d_conv_bwd_data(const n3d_conv_geom* g, const float* dy, int64_t dyld, const float* w, float* dx, int64_t dxld, int flags,
                       const float* relu_src, int64_t rld, const float* out_gate, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = check_geom(g, "conv_bwd_data")) return e;
-  N3D_CHECK_ARG(dy && w && dx && dyld >= g->Co && (dxld >= g->Ci || (dxld >= 4 && g->Ci % dxld == 0)), "conv_bwd_data: bad pointers/pitches");
-  return run_gather(g, true, dy, dyld, w, nullptr, dx, dxld, flags & ~N3D_RELU_IN, nullptr, relu_src, rld, out_gate, nullptr, ws, ws_bytes,
-                    stream);
+  n3d_conv_bwd_call c = {};
+  c.g = g; c.flags_data = flags; c.dy = dy; c.dyld = dyld; c.w = w; c.dx = dx; c.dxld = dxld; c.relu_src = relu_src; c.rld = rld; c.out_gate = out_gate;
+  c.ws_data = ws; c.ws_data_bytes = ws_bytes;
+  return run_bwd_data_call(&c, stream);
 }
 
 int n3d_convT_fwd(const n3d_conv_geom* g, const float* x, int64_t xld, const float* w, const float* bias, float* y, int64_t yld, int flags,
                   const float* in_gate, double* stats, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = check_geom(g, "convT_fwd")) return e;
-  N3D_CHECK_ARG(x && w && y && xld >= g->Co && yld >= g->Ci, "convT_fwd: bad pointers/pitches");
-  return run_gather(g, true, x, xld, w, bias, y, yld, flags, in_gate, nullptr, 0, nullptr, stats, ws, ws_bytes, stream);
+  const n3d_conv_fwd_call c = {g, 1, flags, x, xld, w, bias, y, yld, in_gate, stats, ws, ws_bytes};
+  return run_fwd_call(&c, stream);
 }
 
 int n3d_convT_bwd_data(const n3d_conv_geom* g, const float* dy, int64_t dyld, const float* w, float* dx, int64_t dxld, int flags, void* ws,
                        size_t ws_bytes, void* stream) {
-  if (int e = check_geom(g, "convT_bwd_data")) return e;
-  N3D_CHECK_ARG(dy && w && dx && dyld >= g->Ci && dxld >= g->Co, "convT_bwd_data: bad pointers/pitches");
-  return run_gather(g, false, dy, dyld, w, nullptr, dx, dxld, flags & ~N3D_RELU_IN, nullptr, nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
+  n3d_conv_bwd_call c = {};
+  c.g = g; c.transposed = 1; c.flags_data = flags; c.dy = dy; c.dyld = dyld; c.w = w; c.dx = dx; c.dxld = dxld; c.ws_data = ws; c.ws_data_bytes = ws_bytes;
+  return run_bwd_data_call(&c, stream);
 }
 
 static void fill_job(n3d_final_job* j, const float* partial, const float* pbias, float* dw, float* dbias, int nch, int ntl, int tci, int tco,
@@ -2551,11 +2513,11 @@ static int run_wgrad(const n3d_conv_geom* g, const float* x, int64_t xld, const 
         // run_wgrad's (x, dy) are kernel roles (i side, o side); a transposed conv's output gradient sits on the i side
         const float* true_dy = transposed ? x : dy; const int64_t true_dyld = transposed ? xld : dyld;
         const float* true_x = transposed ? dy : x; const int64_t true_xld = transposed ? dyld : xld;
-        handled = mfma_bwd_dual_try(g, transposed, true_dy, true_dyld, (const float*)dual->ws, dual->dx, dual->dxld, dual->flags,
-                                    dual->relu_src, dual->rld, dual->out_gate, true_x, true_xld, flags, in_gate, wsf, pb,
-                                    (N3D_WG16_SLABS + nt16) * 256, &nch, &ntl, s);
+        BwdOne b = {g, transposed, true_dy, true_dyld, (const float*)dual->ws, dual->dx, dual->dxld, dual->flags, dual->relu_src, dual->rld,
+                    dual->out_gate, true_x, true_xld, flags, in_gate, wsf, pb, (N3D_WG16_SLABS + nt16) * 256, 0, 0};
+        handled = mfma_bwd_dual_try(&b, s);
         if (handled < 0) return handled;
-        if (handled == 1) dual->done = true;
+        if (handled == 1) { dual->done = true; nch = b.nch; ntl = b.ntl; }
       }
       if (!handled) handled = mfma_wgrad_try(g, x, xld, dy, dyld, flags, in_gate, wsf, pb, (N3D_WG16_SLABS + nt16) * 256, &nch, &ntl, s);
     }
@@ -2642,8 +2604,8 @@ int n3d_conv_bwd_both(const n3d_conv_geom* g, const float* x, int64_t xld, const
   DualReq rq = {w, dx, dxld, flags_data & ~N3D_RELU_IN, relu_src, rld, out_gate, ws_data, ws_data_bytes, false};
   if (int e = run_wgrad(g, x, xld, dy, dyld, dw, dbias, flags_weight, in_gate, ws_weight, ws_weight_bytes, stream, false, deferred, &rq)) return e;
   if (rq.done) return N3D_OK;
-  return run_gather(g, true, dy, dyld, w, nullptr, dx, dxld, flags_data & ~N3D_RELU_IN, nullptr, relu_src, rld, out_gate, nullptr, ws_data,
-                    ws_data_bytes, stream);
+  return run_gather(ConvCall{g, true, dy, dyld, w, nullptr, dx, dxld, flags_data & ~N3D_RELU_IN, nullptr, relu_src, rld, out_gate, nullptr, ws_data,
+                             ws_data_bytes}, (hipStream_t)stream);
 }
 
 int n3d_convT_bwd_both(const n3d_conv_geom* g, const float* x, int64_t xld, const float* dy, int64_t dyld, const float* w, float* dx,
@@ -2656,8 +2618,8 @@ int n3d_convT_bwd_both(const n3d_conv_geom* g, const float* x, int64_t xld, cons
                         deferred, &rq))
     return e;
   if (rq.done) return N3D_OK;
-  return run_gather(g, false, dy, dyld, w, nullptr, dx, dxld, flags_data & ~N3D_RELU_IN, nullptr, nullptr, 0, nullptr, nullptr, ws_data,
-                    ws_data_bytes, stream);
+  return run_gather(ConvCall{g, false, dy, dyld, w, nullptr, dx, dxld, flags_data & ~N3D_RELU_IN, nullptr, nullptr, 0, nullptr, nullptr, ws_data,
+                             ws_data_bytes}, (hipStream_t)stream);
 }
 
 int n3d_dwconv_batch(const n3d_dw_job* jobs, int n, void* stream) {
@@ -2690,16 +2652,11 @@ int n3d_conv_fwd2(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1, void
     N3D_CHECK_ARG(cs[i]->x && cs[i]->w && cs[i]->y, "conv_fwd2: null pointers");
   }
   if (!((c0->flags | c1->flags) & N3D_NO_MFMA) && !c0->g->depthwise && !c1->g->depthwise) {
-    {
-      const VoxCall vc[2] = {vox_call_fwd(c0), vox_call_fwd(c1)};
-      const int r = mfma_vox_multi_try(2, vc, (hipStream_t)stream);
-      if (r < 0) return r;
-      if (r == 1) return N3D_OK;
-    }
-    // forward conv = gather with data_grad=false; transposed forward = gather with data_grad=true (run_gather convention)
-    const int r = mfma_conv_pair_try(c0->g, c0->transposed != 0, c0->x, c0->xld, c0->w, c0->bias, c0->y, c0->yld, c0->flags, c0->in_gate,
-                                     c0->stats, c0->ws, c0->ws_bytes, c1->g, c1->transposed != 0, c1->x, c1->xld, c1->w, c1->bias, c1->y,
-                                     c1->yld, c1->flags, c1->in_gate, c1->stats, c1->ws, c1->ws_bytes, (hipStream_t)stream, nullptr, nullptr);
+    const ConvCall cc[2] = {conv_call_fwd(c0), conv_call_fwd(c1)};
+    int r = mfma_vox_multi_try(2, cc, (hipStream_t)stream);
+    if (r < 0) return r;
+    if (r == 1) return N3D_OK;
+    r = mfma_conv_pair_try(cc[0], cc[1], (hipStream_t)stream);
     if (r < 0) return r;
     if (r == 1) return N3D_OK;
   }
@@ -2711,19 +2668,13 @@ int n3d_conv_fwd2(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1, void
     PointHold h[2] = {};
     h[1].before = &h[0];
     for (int i = 0; i < 2; ++i) {
-      const n3d_conv_fwd_call* c = cs[i];
-      const int e = run_gather(c->g, false, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, nullptr, 0, nullptr, c->stats, c->ws,
-                               c->ws_bytes, stream, &h[i]);
+      const int e = run_gather(conv_call_fwd(cs[i]), (hipStream_t)stream, nullptr, &h[i]);
       if (e) { point_pair_finish(h, (hipStream_t)stream); return e; }
     }
     return point_pair_finish(h, (hipStream_t)stream);
   }
-  for (int i = 0; i < 2; ++i) {
-    const n3d_conv_fwd_call* c = cs[i];
-    const int e = c->transposed ? n3d_convT_fwd(c->g, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, c->stats, c->ws, c->ws_bytes, stream)
-                                : n3d_conv_fwd(c->g, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, c->stats, c->ws, c->ws_bytes, stream);
-    if (e) return e;
-  }
+  for (int i = 0; i < 2; ++i)
+    if (int e = run_fwd_call(cs[i], stream)) return e;
   return N3D_OK;
 }
 
@@ -2731,31 +2682,27 @@ int n3d_conv_fwd2_folds(const n3d_conv_fwd_call* c0, const n3d_conv_fwd_call* c1
   if (!c0 || !c1 || !c0->g || !c1->g || !c0->x || !c1->x || !c0->w || !c1->w || !c0->y || !c1->y) return 0;
   if (check_geom(c0->g, "conv_fwd2_folds") || check_geom(c1->g, "conv_fwd2_folds")) return 0;
   if (((c0->flags | c1->flags) & N3D_NO_MFMA) || c0->g->depthwise || c1->g->depthwise) return 0;      // n3d_conv_fwd2's own conditions
-  const VoxCall vc[2] = {vox_call_fwd(c0), vox_call_fwd(c1)};
-  return mfma_vox_multi_folds(2, vc);
+  const ConvCall cc[2] = {conv_call_fwd(c0), conv_call_fwd(c1)};
+  return mfma_vox_multi_folds(2, cc);
 }
 
 int n3d_conv_fwdN(const n3d_conv_fwd_call* calls, int n, void* stream) {
   N3D_CHECK_ARG(calls && n >= 1 && n <= 4, "conv_fwdN: 1..4 calls");
   if (n >= 3) {
-    const n3d_conv_geom* g[4]; bool dg[4]; const float* src[4]; int64_t sld[4]; const float* w[4]; const float* bias[4]; float* dst[4];
-    int64_t dld[4]; int flags[4]; const float* gate[4]; double* stats[4]; void* ws[4]; size_t wsb[4];
+    ConvCall cc[4];
     bool mf = true;
     for (int i = 0; i < n; ++i) {
       const n3d_conv_fwd_call* c = &calls[i];
       N3D_CHECK_ARG(c->g && c->x && c->w && c->y, "conv_fwdN: null pointers");
       if (int e = check_geom(c->g, "conv_fwdN")) return e;
       mf = mf && !(c->flags & N3D_NO_MFMA) && !c->g->depthwise;
-      g[i] = c->g; dg[i] = c->transposed != 0; src[i] = c->x; sld[i] = c->xld; w[i] = c->w; bias[i] = c->bias; dst[i] = c->y; dld[i] = c->yld;
-      flags[i] = c->flags; gate[i] = c->in_gate; stats[i] = c->stats; ws[i] = c->ws; wsb[i] = c->ws_bytes;
+      cc[i] = conv_call_fwd(c);
     }
     if (mf) {
-      VoxCall vc[4];
-      for (int i = 0; i < n; ++i) vc[i] = vox_call_fwd(&calls[i]);
-      int r = mfma_vox_multi_try(n, vc, (hipStream_t)stream);
+      int r = mfma_vox_multi_try(n, cc, (hipStream_t)stream);
       if (r < 0) return r;
       if (r == 1) return N3D_OK;
-      r = mfma_conv_multi_try(n, g, dg, src, sld, w, bias, dst, dld, flags, gate, stats, ws, wsb, (hipStream_t)stream);
+      r = mfma_conv_multi_try(n, cc, (hipStream_t)stream);
       if (r < 0) return r;
       if (r == 1) return N3D_OK;
     }
@@ -2764,12 +2711,8 @@ int n3d_conv_fwdN(const n3d_conv_fwd_call* calls, int n, void* stream) {
   int i = 0;
   for (; i + 1 < n; i += 2)
     if (int e = n3d_conv_fwd2(&calls[i], &calls[i + 1], stream)) return e;
-  if (i < n) {
-    const n3d_conv_fwd_call* c = &calls[i];
-    const int e = c->transposed ? n3d_convT_fwd(c->g, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, c->stats, c->ws, c->ws_bytes, stream)
-                                : n3d_conv_fwd(c->g, c->x, c->xld, c->w, c->bias, c->y, c->yld, c->flags, c->in_gate, c->stats, c->ws, c->ws_bytes, stream);
-    if (e) return e;
-  }
+  if (i < n)
+    if (int e = run_fwd_call(&calls[i], stream)) return e;
   return N3D_OK;
 }
 
@@ -2785,18 +2728,11 @@ int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
     pair = pair && !(c->flags_data & N3D_NO_MFMA) && !c->g->depthwise;
   }
   if (pair) {
-    // data gradient of a conv = gather with data_grad=true, of a transposed conv = gather with data_grad=false (run_gather convention)
-    {
-      const VoxCall vc[2] = {vox_call_bwd(c0), vox_call_bwd(c1)};
-      const int r = mfma_vox_multi_try(2, vc, (hipStream_t)stream);
-      if (r < 0) return r;
-      if (r == 1) return N3D_OK;
-    }
-    const PairExtras x0{c0->relu_src, c0->rld, c0->out_gate}, x1{c1->relu_src, c1->rld, c1->out_gate};
-    const int r = mfma_conv_pair_try(c0->g, !c0->transposed, c0->dy, c0->dyld, c0->w, nullptr, c0->dx, c0->dxld, c0->flags_data & ~N3D_RELU_IN, nullptr,
-                                     nullptr, c0->ws_data, c0->ws_data_bytes, c1->g, !c1->transposed, c1->dy, c1->dyld, c1->w, nullptr, c1->dx,
-                                     c1->dxld, c1->flags_data & ~N3D_RELU_IN, nullptr, nullptr, c1->ws_data, c1->ws_data_bytes, (hipStream_t)stream,
-                                     &x0, &x1);
+    const ConvCall cc[2] = {conv_call_bwd(c0), conv_call_bwd(c1)};
+    int r = mfma_vox_multi_try(2, cc, (hipStream_t)stream);
+    if (r < 0) return r;
+    if (r == 1) return N3D_OK;
+    r = mfma_conv_pair_try(cc[0], cc[1], (hipStream_t)stream);
     if (r < 0) return r;
     if (r == 1) return N3D_OK;
   }
@@ -2810,20 +2746,13 @@ int n3d_conv_bwd_data2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1,
     PointHold h[2] = {};
     h[1].before = &h[0];
     for (int i = 0; i < 2; ++i) {
-      const n3d_conv_bwd_call* c = cs[i];
-      const int e = run_gather(c->g, true, c->dy, c->dyld, c->w, nullptr, c->dx, c->dxld, c->flags_data & ~N3D_RELU_IN, nullptr, c->relu_src, c->rld,
-                               c->out_gate, nullptr, c->ws_data, c->ws_data_bytes, stream, &h[i]);
+      const int e = run_gather(conv_call_bwd(cs[i]), (hipStream_t)stream, nullptr, &h[i]);
       if (e) { point_pair_finish(h, (hipStream_t)stream); return e; }
     }
     return point_pair_finish(h, (hipStream_t)stream);
   }
-  for (int i = 0; i < 2; ++i) {
-    const n3d_conv_bwd_call* c = cs[i];
-    const int e = c->transposed ? n3d_convT_bwd_data(c->g, c->dy, c->dyld, c->w, c->dx, c->dxld, c->flags_data, c->ws_data, c->ws_data_bytes, stream)
-                                : n3d_conv_bwd_data(c->g, c->dy, c->dyld, c->w, c->dx, c->dxld, c->flags_data, c->relu_src, c->rld, c->out_gate,
-                                                    c->ws_data, c->ws_data_bytes, stream);
-    if (e) return e;
-  }
+  for (int i = 0; i < 2; ++i)
+    if (int e = run_bwd_data_call(cs[i], stream)) return e;
   return N3D_OK;
 }
 
@@ -2837,8 +2766,8 @@ int n3d_conv_bwd_data2_folds(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_cal
     if ((c->flags_data & N3D_NO_MFMA) || c->g->depthwise) return 0;
   }
   if (c0->dx == c1->dx) return 0;
-  const VoxCall vc[2] = {vox_call_bwd(c0), vox_call_bwd(c1)};
-  return mfma_vox_multi_folds(2, vc);
+  const ConvCall cc[2] = {conv_call_bwd(c0), conv_call_bwd(c1)};
+  return mfma_vox_multi_folds(2, cc);
 }
 
 int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream) {

@@ -12,7 +12,7 @@
 // The same kernel is the data-gradient / transposed-conv kernel through the gather map
 //   src coordinate = (dst*sn + off + tap*dt) / den   (valid iff divisible and in range).
 #include <stdlib.h>
-#include "n3d_common.h"
+#include "conv_internal.h"
 #include <type_traits>
 #include <atomic>
 // cache policy of the weight-gradient kernels' LDS-DMA loads (cpol bits: 1 = sc0, 2 = nt, 16 = sc1).  These kernels run on the side
@@ -1485,14 +1485,8 @@ __global__ __launch_bounds__(64, 2) void conv_vox_multi_kernel(VoxMultiArgs q, E
   }
 }
 
-// one conv of a multi launch as the entry points hand it over (forward-type gather: data_grad as run_gather's)
-struct VoxCall {
-  const n3d_conv_geom* g; bool data_grad; const float* src; int64_t sld; const float* w; const float* bias; float* dst; int64_t dld; int flags;
-  const float* in_gate; const float* relu_src; const float* out_gate; double* stats; void* ws; size_t ws_bytes;
-};
-
 // kind of the job, -1 = this conv is not one the multi launch folds (pure function of geometry, flags and alignment)
-static int vox_multi_kind(const VoxCall& c, int* tiles, size_t* lds) {
+static int vox_multi_kind(const ConvCall& c, int* tiles, size_t* lds) {
   if (c.flags & (N3D_SRC_BF16 | N3D_DST_BF16 | N3D_NO_MFMA | N3D_RELU_IN)) return -1;
   if (c.in_gate || c.relu_src || c.out_gate || c.sld % 4 != 0 || c.dld % 4 != 0 || !aligned16(c.src) || !aligned16(c.dst)) return -1;
   const Vs2Plan v2 = vs2_plan(c.g, c.data_grad);
@@ -1514,7 +1508,7 @@ static int vox_multi_kind(const VoxCall& c, int* tiles, size_t* lds) {
 
 // THE decision whether n convs fold into one launch of conv_vox_multi_kernel (n3d_conv_fwd2_folds / n3d_conv_bwd_data2_folds ask it,
 // mfma_vox_multi_try launches by it): a pure function of geometry, flags, alignment and workspaces
-static bool vox_multi_plan(int n, const VoxCall* c, int* kind, int* tiles, size_t* lds_out) {
+static bool vox_multi_plan(int n, const ConvCall* c, int* kind, int* tiles, size_t* lds_out) {
   if (n < 2 || n > 4) return false;
   size_t lds = 0;
   int64_t total = 0;
@@ -1537,14 +1531,14 @@ static bool vox_multi_plan(int n, const VoxCall* c, int* kind, int* tiles, size_
   return true;
 }
 
-int mfma_vox_multi_folds(int n, const VoxCall* c) {
+int mfma_vox_multi_folds(int n, const ConvCall* c) {
   int kind[4], tiles[4];
   size_t lds = 0;
   return vox_multi_plan(n, c, kind, tiles, &lds) ? 1 : 0;
 }
 
 // n = 2..4 independent convs (distinct destinations) in one launch; 1 = launched, 0 = not foldable (nothing touched), < 0 error
-int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
+int mfma_vox_multi_try(int n, const ConvCall* c, hipStream_t s) {
   int kind[4], tiles[4];
   size_t lds = 0;
   if (!vox_multi_plan(n, c, kind, tiles, &lds)) return 0;
@@ -1555,7 +1549,7 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
   int at = 0;
   for (int i = 0; i < 4; ++i) {
     const int k = i < n ? i : n - 1;      // unused slots repeat the last job (never selected: their range is empty)
-    const VoxCall& cc = c[k];
+    const ConvCall& cc = c[k];
     const n3d_conv_geom* g = cc.g;
     float* wq = (float*)cc.ws;
     const bool up = kind[k] >= VOXK_UP_D1, s2 = !up && kind[k] >= VOXK_S2_D1;
@@ -1582,8 +1576,7 @@ int mfma_vox_multi_try(int n, const VoxCall* c, hipStream_t s) {
   if (C == 4) N3D_LAUNCH(conv_vox_multi_kernel<4>, dim3((unsigned)at), dim3(64), lds, s, q, es);
   else N3D_LAUNCH(conv_vox_multi_kernel<8>, dim3((unsigned)at), dim3(64), lds, s, q, es);
   g_fold_launches[0] += 1;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(vox multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(vox multi)");
   return 1;
 }
 
@@ -2191,8 +2184,7 @@ int vox_wgrad_s2_try(const n3d_conv_geom* g, const float* x, int64_t xld, const 
     if (g->dil == 1) N3D_LAUNCH((vox_wgrad_s2_kernel<8, 1>), grid, dim3(256), lds, s, a);
     else N3D_LAUNCH((vox_wgrad_s2_kernel<8, 2>), grid, dim3(256), lds, s, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(vox_wgrad_s2) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(vox_wgrad_s2)");
   *nchunks_out = nwg;
   return 1;
 }
@@ -2844,50 +2836,47 @@ void mfma_pack16(const float* w, float* wp, int Co, int Ci, int taps, int data_g
   N3D_LAUNCH(pack16_kernel, dim3((unsigned)cdiv((int64_t)taps * Co * Ci, 256)), dim3(256), 0, s, w, wp, Co, Ci, taps, data_grad);
 }
 
-int g16_prepare(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
-                int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate, double* stats,
-                void* ws, size_t ws_bytes, hipStream_t s, MfArgs* out, G16Plan* plan);
+int g16_prepare(const ConvCall& c, hipStream_t s, MfArgs* out, G16Plan* plan);
 
-int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
-                  int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate, double* stats,
-                  void* ws, size_t ws_bytes, hipStream_t s) {
-  if (flags & (N3D_SRC_BF16 | N3D_DST_BF16)) return 0;
+// What the three vox branches of mfma_conv_try do in front of their launch.  Extras or misalignment: 0, the call falls through to the
+// next family -- or N3D_ERR_UNSUPPORTED where statistics or pre-packed weights had committed it to this kernel.  Else the workspace is
+// checked, the weights are packed into it in pack mode `mode` (unless pre-packed), and 1 comes back.  `name`: the kernel, for messages
+static int vox_prologue(const ConvCall& c, int C, int mode, const char* name, hipStream_t s) {
+  if (c.in_gate || c.relu_src || c.out_gate || (c.flags & N3D_RELU_IN) || c.sld % 4 != 0 || c.dld % 4 != 0 || !aligned16(c.src) || !aligned16(c.dst)) {
+    if (c.stats || (c.flags & N3D_PREPACKED)) { set_error("conv(%s): gate / relu extras are not supported on this shape with statistics or pre-packed weights", name); return N3D_ERR_UNSUPPORTED; }
+    return 0;
+  }
+  const size_t need = (size_t)27 * C * C * 4;
+  if (!c.ws || c.ws_bytes < need) { set_error("conv(%s): workspace too small", name); return N3D_ERR_WORKSPACE; }
+  if (!(c.flags & N3D_PREPACKED))
+    N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * C * C, 256)), dim3(256), 0, s, c.w, (float*)c.ws, C, mode);
+  return 1;
+}
+
+int mfma_conv_try(const ConvCall& c, hipStream_t s) {
+  const n3d_conv_geom* g = c.g;
+  if (c.flags & (N3D_SRC_BF16 | N3D_DST_BF16)) return 0;
   {
-    Vs2Plan v2 = vs2_plan(g, data_grad);
+    Vs2Plan v2 = vs2_plan(g, c.data_grad);
     if (v2.ok) {
-      if (in_gate || relu_src || out_gate || (flags & N3D_RELU_IN) || sld % 4 != 0 || dld % 4 != 0 || !aligned16(src) || !aligned16(dst)) {
-        if (stats || (flags & N3D_PREPACKED)) { set_error("conv(vox_s2): gate / relu extras are not supported on this shape with statistics or pre-packed weights"); return N3D_ERR_UNSUPPORTED; }
-        return 0;
-      }
-      const size_t need = (size_t)27 * v2.C * v2.C * 4;
-      if (!ws || ws_bytes < need) { set_error("conv(vox_s2): workspace too small"); return N3D_ERR_WORKSPACE; }
-      float* wq = (float*)ws;
-      if (!(flags & N3D_PREPACKED))
-        N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * v2.C * v2.C, 256)), dim3(256), 0, s, w, wq, v2.C, 0);
+      const int r = vox_prologue(c, v2.C, 0, "vox_s2", s);
+      if (r <= 0) return r;
       Vs2Args a;
-      a.src = src; a.sld = sld; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.dst = dst; a.dld = dld; a.oD = g->Do; a.oH = g->Ho; a.oW = g->Wo;
-      a.wq = wq; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v2.tiles; a.tiles = v2.tiles; a.zero_page = zero_page_ptr();
+      a.src = c.src; a.sld = c.sld; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.dst = c.dst; a.dld = c.dld; a.oD = g->Do; a.oH = g->Ho; a.oW = g->Wo;
+      a.wq = (float*)c.ws; a.bias = c.bias; a.flags = c.flags; a.stats = c.stats; a.rows_per_sample = v2.tiles; a.tiles = v2.tiles; a.zero_page = zero_page_ptr();
       a.fT = FastDiv((uint32_t)v2.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
       if (!a.zero_page) { set_error("conv(vox_s2): zero page symbol unavailable"); return N3D_ERR_HIP; }
       launch_vs2(a, v2, g->B, s);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { set_error("conv(vox_s2) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+      N3D_LAUNCH_CHECK_AS("conv(vox_s2)");
       return 1;
     }
-    VupPlan v3 = vup_plan(g, data_grad);
+    VupPlan v3 = vup_plan(g, c.data_grad);
     if (v3.ok) {
-      if (in_gate || relu_src || out_gate || (flags & N3D_RELU_IN) || sld % 4 != 0 || dld % 4 != 0 || !aligned16(src) || !aligned16(dst)) {
-        if (stats || (flags & N3D_PREPACKED)) { set_error("conv(vox_up): gate / relu extras are not supported on this shape with statistics or pre-packed weights"); return N3D_ERR_UNSUPPORTED; }
-        return 0;
-      }
-      const size_t need = (size_t)27 * v3.C * v3.C * 4;
-      if (!ws || ws_bytes < need) { set_error("conv(vox_up): workspace too small"); return N3D_ERR_WORKSPACE; }
-      float* wq = (float*)ws;
-      if (!(flags & N3D_PREPACKED))
-        N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * v3.C * v3.C, 256)), dim3(256), 0, s, w, wq, v3.C, 2);
+      const int r = vox_prologue(c, v3.C, 2, "vox_up", s);
+      if (r <= 0) return r;
       VupArgs a;
-      a.src = src; a.sld = sld; a.D = g->Do; a.H = g->Ho; a.W = g->Wo; a.dst = dst; a.dld = dld;
-      a.wq = wq; a.bias = bias; a.flags = flags; a.stats = stats; a.rows_per_sample = v3.tiles; a.tiles = v3.tiles; a.zero_page = zero_page_ptr();
+      a.src = c.src; a.sld = c.sld; a.D = g->Do; a.H = g->Ho; a.W = g->Wo; a.dst = c.dst; a.dld = c.dld;
+      a.wq = (float*)c.ws; a.bias = c.bias; a.flags = c.flags; a.stats = c.stats; a.rows_per_sample = v3.tiles; a.tiles = v3.tiles; a.zero_page = zero_page_ptr();
       a.fT = FastDiv((uint32_t)v3.tiles); a.fTw = FastDiv((uint32_t)(g->Wo / 16)); a.fTh = FastDiv((uint32_t)(g->Ho / 4));
       if (!a.zero_page) { set_error("conv(vox_up): zero page symbol unavailable"); return N3D_ERR_HIP; }
       const EntrySignal es = entry_take(s);
@@ -2895,44 +2884,35 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
                        else N3D_LAUNCH((conv_vox_up_kernel<4, 2>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es); }
       else { if (v3.dil == 1) N3D_LAUNCH((conv_vox_up_kernel<8, 1>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es);
              else N3D_LAUNCH((conv_vox_up_kernel<8, 2>), dim3(v3.tiles * g->B), dim3(64), v3.lds, s, a, es); }
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { set_error("conv(vox_up) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+      N3D_LAUNCH_CHECK_AS("conv(vox_up)");
       return 1;
     }
     VxPlan v = vx_plan(g);
     if (v.ok) {
-      if (in_gate || relu_src || out_gate || (flags & N3D_RELU_IN) || sld % 4 != 0 || dld % 4 != 0 || !aligned16(src) || !aligned16(dst)) {
-        if (stats || (flags & N3D_PREPACKED)) { set_error("conv(vox64): gate / relu extras are not supported on this shape with statistics or pre-packed weights"); return N3D_ERR_UNSUPPORTED; }
-        return 0;
-      }
-      const size_t need = (size_t)27 * v.C * v.C * 4;
-      if (!ws || ws_bytes < need) { set_error("conv(vox64): workspace too small"); return N3D_ERR_WORKSPACE; }
-      float* wq = (float*)ws;
-      if (!(flags & N3D_PREPACKED))
-        N3D_LAUNCH(pack_vox_kernel, dim3((unsigned)cdiv(27 * v.C * v.C, 256)), dim3(256), 0, s, w, wq, v.C, data_grad ? 1 : 0);
+      const int r = vox_prologue(c, v.C, c.data_grad ? 1 : 0, "vox64", s);
+      if (r <= 0) return r;
       VxArgs a;
-      a.src = src; a.sld = sld; a.dst = dst; a.dld = dld; a.wq = wq; a.bias = bias; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.flags = flags;
-      a.stats = stats; a.rows_per_sample = v.tiles * v.nw;
+      a.src = c.src; a.sld = c.sld; a.dst = c.dst; a.dld = c.dld; a.wq = (float*)c.ws; a.bias = c.bias; a.D = g->Di; a.H = g->Hi; a.W = g->Wi; a.flags = c.flags;
+      a.stats = c.stats; a.rows_per_sample = v.tiles * v.nw;
       const int launched = v.C == 4 ? launch_vox_c<4>(a, v, g->B, s) : launch_vox_c<8>(a, v, g->B, s);
       if (!launched) { set_error("conv(vox64): zero page symbol unavailable"); return N3D_ERR_HIP; }
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) { set_error("conv(vox64) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+      N3D_LAUNCH_CHECK_AS("conv(vox64)");
       return 1;
     }
   }
   MfArgs a;
   G16Plan p;
   {
-    const int r = g16_prepare(g, data_grad, src, sld, w, bias, dst, dld, flags, in_gate, relu_src, rld, out_gate, stats, ws, ws_bytes, s, &a, &p);
+    const int r = g16_prepare(c, s, &a, &p);
     if (r <= 0) return r;
   }
   const int64_t M = (int64_t)g->B * a.Dd * a.Hd * a.Wd;
   if (p.ksplit == 1) {
-    const int tiles = tile16_up_tiles(g, data_grad);
+    const int tiles = tile16_up_tiles(g, c.data_grad);
     if (tiles) {
       const void* zp = zero_page_ptr();
       if (a.sld % 4 != 0 || !aligned16(a.src) || !aligned16(a.wp) || !zp) {
-        if (stats) { set_error("conv(tile16_up): misaligned source with statistics requested"); return N3D_ERR_UNSUPPORTED; }
+        if (c.stats) { set_error("conv(tile16_up): misaligned source with statistics requested"); return N3D_ERR_UNSUPPORTED; }
       } else {
         a.rows_per_sample = tiles;
         const int d = g->dil, lo = d == 2 ? 1 : 0;
@@ -2945,66 +2925,58 @@ int mfma_conv_try(const n3d_conv_geom* g, bool data_grad, const float* src, int6
                       else N3D_LAUNCH((conv_tile16_up_kernel<1, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); }
         else { if (bf) N3D_LAUNCH((conv_tile16_up_kernel<2, true>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh);
                else N3D_LAUNCH((conv_tile16_up_kernel<2, false>), grid, dim3(256), shm, s, a, zp, tiles, fT, fTw, fTh); }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("conv(tile16_up) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+        N3D_LAUNCH_CHECK_AS("conv(tile16_up)");
         return 1;
       }
     }
   }
   if (const int t32 = tile32_tiles(g)) {
     if (a.sn == 1 && a.den == 1 && a.Cs == 32 && a.Cd == 32) {
-      if (stats) a.rows_per_sample = t32;
+      if (c.stats) a.rows_per_sample = t32;
       if (launch_tile32(a, t32, s)) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("conv(tile32) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+        N3D_LAUNCH_CHECK_AS("conv(tile32)");
         return 1;
       }
-      if (stats) { set_error("conv(tile32): misaligned source with statistics requested"); return N3D_ERR_UNSUPPORTED; }
+      if (c.stats) { set_error("conv(tile32): misaligned source with statistics requested"); return N3D_ERR_UNSUPPORTED; }
     }
   }
   if (tile16_applies(a, p.ksplit) && launch_tile16(a, s)) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("conv(tile16) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+    N3D_LAUNCH_CHECK_AS("conv(tile16)");
     return 1;
   }
   if (p.ksplit == 16) launch_g16<1, 1, 16>(a, M, s);
   else if (p.ksplit == 4) launch_g16<1, 1, 4>(a, M, s);
   else if (p.nt == 2) launch_g16<2, 2, 1>(a, M, s);
   else launch_g16<2, 1, 1>(a, M, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(mfma) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(mfma)");
   return 1;
 }
 
 // fills the arguments of the gemm16 family for one conv (packing the weights unless pre-packed); 1 = ready, 0 = shape not
 // served by gemm16, < 0 error
-int g16_prepare(const n3d_conv_geom* g, bool data_grad, const float* src, int64_t sld, const float* w, const float* bias, float* dst,
-                int64_t dld, int flags, const float* in_gate, const float* relu_src, int64_t rld, const float* out_gate, double* stats,
-                void* ws, size_t ws_bytes, hipStream_t s, MfArgs* out, G16Plan* plan) {
+int g16_prepare(const ConvCall& c, hipStream_t s, MfArgs* out, G16Plan* plan) {
+  const n3d_conv_geom* g = c.g;
   if (vx_plan(g).ok) return 0;
-  G16Plan p = g16_plan(g, data_grad);
+  G16Plan p = g16_plan(g, c.data_grad);
   if (!p.ok) return 0;
-  if (sld % 4 != 0 || !aligned16(src)) {
-    if (flags & N3D_PREPACKED) { set_error("conv(gemm16): misaligned source with pre-packed weights"); return N3D_ERR_UNSUPPORTED; }
+  if (c.sld % 4 != 0 || !aligned16(c.src)) {
+    if (c.flags & N3D_PREPACKED) { set_error("conv(gemm16): misaligned source with pre-packed weights"); return N3D_ERR_UNSUPPORTED; }
     return 0;
   }
   const int taps = g->k * g->k * g->k;
   MfArgs a;
-  a.src = src; a.sld = sld; a.dst = dst; a.dld = dld; a.bias = bias; a.k = g->k; a.flags = flags; a.B = g->B;
-  a.in_gate = in_gate; a.relu_src = relu_src; a.rld = rld; a.out_gate = out_gate; a.stats = stats;
-  if (!data_grad) { a.Ds = g->Di; a.Hs = g->Hi; a.Ws = g->Wi; a.Cs = g->Ci; a.Dd = g->Do; a.Hd = g->Ho; a.Wd = g->Wo; a.Cd = g->Co;
-    a.sn = g->stride; a.off = -g->pad; a.dt = g->dil; a.den = 1; }
-  else { a.Ds = g->Do; a.Hs = g->Ho; a.Ws = g->Wo; a.Cs = g->Co; a.Dd = g->Di; a.Hd = g->Hi; a.Wd = g->Wi; a.Cd = g->Ci;
-    a.sn = 1; a.off = g->pad; a.dt = -g->dil; a.den = g->stride; }
+  a.src = c.src; a.sld = c.sld; a.dst = c.dst; a.dld = c.dld; a.bias = c.bias; a.k = g->k; a.flags = c.flags; a.B = g->B;
+  a.in_gate = c.in_gate; a.relu_src = c.relu_src; a.rld = c.rld; a.out_gate = c.out_gate; a.stats = c.stats;
+  set_gather_geom(a, gather_geom(g, c.data_grad));
   const int64_t Nd = (int64_t)a.Dd * a.Hd * a.Wd;
   if ((int64_t)g->B * Nd >= (1ll << 31)) return 0;  // 32-bit voxel indexing
   {
     // 31-bit byte offsets into the source (its voxel pitch may be that of a wider buffer)
-    const int64_t Ns = data_grad ? (int64_t)g->Do * g->Ho * g->Wo : (int64_t)g->Di * g->Hi * g->Wi;
-    if (((int64_t)g->B * Ns + 8 * ((int64_t)(data_grad ? g->Ho : g->Hi) + 1) * ((data_grad ? g->Wo : g->Wi) + 1)) * sld * 4 >= (1ll << 30)) return 0;
+    const int64_t Ns = c.data_grad ? (int64_t)g->Do * g->Ho * g->Wo : (int64_t)g->Di * g->Hi * g->Wi;
+    if (((int64_t)g->B * Ns + 8 * ((int64_t)(c.data_grad ? g->Ho : g->Hi) + 1) * ((c.data_grad ? g->Wo : g->Wi) + 1)) * c.sld * 4 >= (1ll << 30)) return 0;
   }
   a.fNd = FastDiv((uint32_t)Nd); a.fWd = FastDiv((uint32_t)a.Wd); a.fHd = FastDiv((uint32_t)a.Hd); a.fC16 = FastDiv((uint32_t)(a.Cs / 16));
-  if (stats) {
+  if (c.stats) {
     if (Nd * 2 == p.rows_per_block && p.ksplit > 1) a.rows_per_sample = 1;
     else {
       if (Nd % p.rows_per_block != 0) { set_error("conv(mfma): statistics requested for a shape whose n3d_conv_stats_rows() is -1"); return N3D_ERR_INVALID; }
@@ -3012,40 +2984,34 @@ int g16_prepare(const n3d_conv_geom* g, bool data_grad, const float* src, int64_
     }
   } else a.rows_per_sample = 0;
   const size_t need = (size_t)taps * a.Cs * a.Cd * 4;
-  if (!ws || ws_bytes < need) { set_error("conv(mfma): workspace too small (%zu < %zu)", ws_bytes, need); return N3D_ERR_WORKSPACE; }
-  float* wp = (float*)ws;
+  if (!c.ws || c.ws_bytes < need) { set_error("conv(mfma): workspace too small (%zu < %zu)", c.ws_bytes, need); return N3D_ERR_WORKSPACE; }
+  float* wp = (float*)c.ws;
   a.wp = wp;
   const int total = taps * a.Cs * a.Cd;
-  if (!(flags & N3D_PREPACKED))
-    N3D_LAUNCH(pack16_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, g->Co, g->Ci, taps, data_grad ? 1 : 0);
+  if (!(c.flags & N3D_PREPACKED))
+    N3D_LAUNCH(pack16_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, c.w, wp, g->Co, g->Ci, taps, c.data_grad ? 1 : 0);
   *out = a; *plan = p;
   return 1;
 }
 
-// two forward-type convs (forward, or transposed forward) of the K-split gemm16 family in one launch; 1 = launched,
-// 0 = not applicable (nothing launched, nothing packed), < 0 error
-int mfma_conv_pair_try(const n3d_conv_geom* g0, bool dg0, const float* src0, int64_t sld0, const float* w0, const float* bias0, float* dst0,
-                       int64_t dld0, int flags0, const float* gate0, double* stats0, void* ws0, size_t wsb0, const n3d_conv_geom* g1, bool dg1,
-                       const float* src1, int64_t sld1, const float* w1, const float* bias1, float* dst1, int64_t dld1, int flags1,
-                       const float* gate1, double* stats1, void* ws1, size_t wsb1, hipStream_t s, const PairExtras* x0, const PairExtras* x1) {
+// two convs in gather form (forward, transposed forward, or data gradients with their extras) of the K-split gemm16 family in one
+// launch; 1 = launched, 0 = not applicable (nothing launched, nothing packed), < 0 error
+int mfma_conv_pair_try(const ConvCall& c0, const ConvCall& c1, hipStream_t s) {
   // decide before touching anything (g16_prepare packs weights)
-  if ((flags0 | flags1) & (N3D_SRC_BF16 | N3D_DST_BF16)) return 0;
-  if (vx_plan(g0).ok || vx_plan(g1).ok) return 0;
-  if (tile32_tiles(g0) || tile32_tiles(g1)) return 0;      // the LDS-tile kernel takes these one at a time (two launches beat the K-split pair)
-  const G16Plan p0 = g16_plan(g0, dg0), p1 = g16_plan(g1, dg1);
+  if ((c0.flags | c1.flags) & (N3D_SRC_BF16 | N3D_DST_BF16)) return 0;
+  if (vx_plan(c0.g).ok || vx_plan(c1.g).ok) return 0;
+  if (tile32_tiles(c0.g) || tile32_tiles(c1.g)) return 0;      // the LDS-tile kernel takes these one at a time (two launches beat the K-split pair)
+  const G16Plan p0 = g16_plan(c0.g, c0.data_grad), p1 = g16_plan(c1.g, c1.data_grad);
   if (!p0.ok || !p1.ok || p0.ksplit != p1.ksplit || p0.ksplit == 1) return 0;
-  if (sld0 % 4 != 0 || !aligned16(src0) || sld1 % 4 != 0 || !aligned16(src1)) return 0;
-  if (ws0 == ws1 && !((flags0 & flags1) & N3D_PREPACKED)) return 0;   // one kernel reads both packed copies: they must not share a workspace
+  if (c0.sld % 4 != 0 || !aligned16(c0.src) || c1.sld % 4 != 0 || !aligned16(c1.src)) return 0;
+  if (c0.ws == c1.ws && !((c0.flags & c1.flags) & N3D_PREPACKED)) return 0;   // one kernel reads both packed copies: they must not share a workspace
   PairArgs q;
   G16Plan t0, t1;
-  // x0 / x1: the data-gradient extras of a conv (ReLU mask source of the input, per-(b,c) output gate); NULL for a forward conv
-  int r = g16_prepare(g0, dg0, src0, sld0, w0, bias0, dst0, dld0, flags0, gate0, x0 ? x0->relu_src : nullptr, x0 ? x0->rld : 0,
-                      x0 ? x0->out_gate : nullptr, stats0, ws0, wsb0, s, &q.a0, &t0);
+  int r = g16_prepare(c0, s, &q.a0, &t0);
   if (r <= 0) return r < 0 ? r : N3D_ERR_INVALID;
-  r = g16_prepare(g1, dg1, src1, sld1, w1, bias1, dst1, dld1, flags1, gate1, x1 ? x1->relu_src : nullptr, x1 ? x1->rld : 0,
-                  x1 ? x1->out_gate : nullptr, stats1, ws1, wsb1, s, &q.a1, &t1);
+  r = g16_prepare(c1, s, &q.a1, &t1);
   if (r <= 0) return r < 0 ? r : N3D_ERR_INVALID;
-  const int64_t M0 = (int64_t)g0->B * q.a0.Dd * q.a0.Hd * q.a0.Wd, M1 = (int64_t)g1->B * q.a1.Dd * q.a1.Hd * q.a1.Wd;
+  const int64_t M0 = (int64_t)c0.g->B * q.a0.Dd * q.a0.Hd * q.a0.Wd, M1 = (int64_t)c1.g->B * q.a1.Dd * q.a1.Hd * q.a1.Wd;
   q.gx0 = (int)cdiv(M0, 16); q.gx1 = (int)cdiv(M1, 16);
   q.n0 = q.gx0 * (q.a0.Cd / 16);
   const int n1 = q.gx1 * (q.a1.Cd / 16);
@@ -3054,34 +3020,30 @@ int mfma_conv_pair_try(const n3d_conv_geom* g0, bool dg0, const float* src0, int
   if (p0.ksplit == 16) N3D_LAUNCH(conv_gemm16_pair_kernel<16>, dim3((unsigned)(q.n0 + n1)), dim3(1024), shm, s, q, es);
   else N3D_LAUNCH(conv_gemm16_pair_kernel<4>, dim3((unsigned)(q.n0 + n1)), dim3(256), shm, s, q, es);
   g_fold_launches[1] += 1;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(pair) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(pair)");
   return 1;
 }
 
 // n = 3 or 4 forward-type convs (no data-gradient extras) in one launch; 1 = launched, 0 = not foldable (nothing touched)
-int mfma_conv_multi_try(int n, const n3d_conv_geom* const* g, const bool* dg, const float* const* src, const int64_t* sld, const float* const* w,
-                        const float* const* bias, float* const* dst, const int64_t* dld, const int* flags, const float* const* gate,
-                        double* const* stats, void* const* ws, const size_t* wsb, hipStream_t s) {
+int mfma_conv_multi_try(int n, const ConvCall* c, hipStream_t s) {
   if (n < 3 || n > 4) return 0;
   int ksplit = 0;
   for (int i = 0; i < n; ++i) {
-    if (vx_plan(g[i]).ok || tile32_tiles(g[i])) return 0;
-    const G16Plan p = g16_plan(g[i], dg[i]);
+    if (vx_plan(c[i].g).ok || tile32_tiles(c[i].g)) return 0;
+    const G16Plan p = g16_plan(c[i].g, c[i].data_grad);
     if (!p.ok || p.ksplit == 1 || (i > 0 && p.ksplit != ksplit)) return 0;
     ksplit = p.ksplit;
-    if (sld[i] % 4 != 0 || !aligned16(src[i])) return 0;
-    for (int j = 0; j < i; ++j) if (ws[j] == ws[i] && !((flags[j] & flags[i]) & N3D_PREPACKED)) return 0;   // (as mfma_conv_pair_try)
+    if (c[i].sld % 4 != 0 || !aligned16(c[i].src)) return 0;
+    for (int j = 0; j < i; ++j) if (c[j].ws == c[i].ws && !((c[j].flags & c[i].flags) & N3D_PREPACKED)) return 0;   // (as mfma_conv_pair_try)
   }
   MultiArgs q;
   int total = 0;
   for (int i = 0; i < 4; ++i) {
     if (i < n) {
       G16Plan t;
-      const int r = g16_prepare(g[i], dg[i], src[i], sld[i], w[i], bias[i], dst[i], dld[i], flags[i], gate[i], nullptr, 0, nullptr, stats[i],
-                                ws[i], wsb[i], s, &q.a[i], &t);
+      const int r = g16_prepare(c[i], s, &q.a[i], &t);
       if (r <= 0) return r < 0 ? r : N3D_ERR_INVALID;
-      const int64_t M = (int64_t)g[i]->B * q.a[i].Dd * q.a[i].Hd * q.a[i].Wd;
+      const int64_t M = (int64_t)c[i].g->B * q.a[i].Dd * q.a[i].Hd * q.a[i].Wd;
       q.gx[i] = (int)cdiv(M, 16);
       q.start[i] = total;
       total += q.gx[i] * (q.a[i].Cd / 16);
@@ -3094,8 +3056,7 @@ int mfma_conv_multi_try(int n, const n3d_conv_geom* const* g, const bool* dg, co
   if (ksplit == 16) N3D_LAUNCH(conv_gemm16_multi_kernel<16>, dim3((unsigned)total), dim3(1024), shm, s, q);
   else N3D_LAUNCH(conv_gemm16_multi_kernel<4>, dim3((unsigned)total), dim3(256), shm, s, q);
   g_fold_launches[2] += 1;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(multi) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(multi)");
   return 1;
 }
 
@@ -3331,38 +3292,33 @@ int wgrad_tile16_try(const n3d_conv_geom* g, const float* x, int64_t xld, const 
 
 // Data gradient + weight gradient of a non-transposed conv whose channel counts are multiples of 16 and whose data
 // gradient is a tiny GEMM (K-split plan), in one launch.  Returns 1 if launched, 0 if the shape does not qualify.
-int mfma_bwd_dual_try(const n3d_conv_geom* g, bool transposed, const float* dy, int64_t dyld, const float* wp_packed, float* dx,
-                      int64_t dxld, int flags_d, const float* relu_src, int64_t rld, const float* out_gate, const float* x, int64_t xld,
-                      int flags_w, const float* in_gate, float* partial, float* pbias, size_t avail_floats, int* nchunks_out,
-                      int* ntiles_out, hipStream_t s, DualArgs* prepared, int* ksplit_out) {
+int mfma_bwd_dual_try(BwdOne* c, hipStream_t s, DualArgs* prepared, int* ksplit_out) {
+  const n3d_conv_geom* g = c->g;
   // transposed conv: its data gradient is the FORWARD gather of the geometry (dy lives on the i side), and the weight
   // gradient kernel sees dy as its i-side operand and x as its o-side operand (roles swapped by the caller's convention)
-  const bool dgrad_is_data_grad = !transposed;
+  const bool dgrad_is_data_grad = !c->transposed;
   if (vx_plan(g).ok) return 0;
   const G16Plan p = g16_plan(g, dgrad_is_data_grad);
   if (!p.ok || p.ksplit == 1) return 0;
-  if (dyld % 4 != 0 || !aligned16(dy)) return 0;
+  if (c->dyld % 4 != 0 || !aligned16(c->dy)) return 0;
   MfArgs a;
-  a.src = dy; a.sld = dyld; a.dst = dx; a.dld = dxld; a.bias = nullptr; a.k = g->k; a.flags = flags_d; a.B = g->B;
-  a.in_gate = nullptr; a.relu_src = relu_src; a.rld = rld; a.out_gate = out_gate; a.stats = nullptr; a.rows_per_sample = 0;
-  if (!dgrad_is_data_grad) { a.Ds = g->Di; a.Hs = g->Hi; a.Ws = g->Wi; a.Cs = g->Ci; a.Dd = g->Do; a.Hd = g->Ho; a.Wd = g->Wo; a.Cd = g->Co;
-    a.sn = g->stride; a.off = -g->pad; a.dt = g->dil; a.den = 1; }
-  else { a.Ds = g->Do; a.Hs = g->Ho; a.Ws = g->Wo; a.Cs = g->Co; a.Dd = g->Di; a.Hd = g->Hi; a.Wd = g->Wi; a.Cd = g->Ci;
-    a.sn = 1; a.off = g->pad; a.dt = -g->dil; a.den = g->stride; }
+  a.src = c->dy; a.sld = c->dyld; a.dst = c->dx; a.dld = c->dxld; a.bias = nullptr; a.k = g->k; a.flags = c->flags_d; a.B = g->B;
+  a.in_gate = nullptr; a.relu_src = c->relu_src; a.rld = c->rld; a.out_gate = c->out_gate; a.stats = nullptr; a.rows_per_sample = 0;
+  set_gather_geom(a, gather_geom(g, dgrad_is_data_grad));
   const int64_t Nd = (int64_t)a.Dd * a.Hd * a.Wd;
   if ((int64_t)g->B * Nd >= (1ll << 31)) return 0;
   a.fNd = FastDiv((uint32_t)Nd); a.fWd = FastDiv((uint32_t)a.Wd); a.fHd = FastDiv((uint32_t)a.Hd); a.fC16 = FastDiv((uint32_t)(a.Cs / 16));
-  a.wp = wp_packed;
+  a.wp = c->wp;
   DualArgs q;
   q.d = a;
-  const int wok = transposed ? mfma_wgrad_try(g, dy, dyld, x, xld, flags_w, in_gate, partial, pbias, avail_floats, nchunks_out, ntiles_out, s, &q.w)
-                             : mfma_wgrad_try(g, x, xld, dy, dyld, flags_w, in_gate, partial, pbias, avail_floats, nchunks_out, ntiles_out, s, &q.w);
+  const int wok = c->transposed ? mfma_wgrad_try(g, c->dy, c->dyld, c->x, c->xld, c->flags_w, c->in_gate, c->partial, c->pbias, c->avail, &c->nch, &c->ntl, s, &q.w)
+                                : mfma_wgrad_try(g, c->x, c->xld, c->dy, c->dyld, c->flags_w, c->in_gate, c->partial, c->pbias, c->avail, &c->nch, &c->ntl, s, &q.w);
   if (!wok) return 0;
   const int64_t M = (int64_t)g->B * Nd;
   q.gxA = (int)cdiv(M, 16);
   q.nA = q.gxA * (a.Cd / 16);
-  q.ntilesB = *ntiles_out;
-  q.nB = *ntiles_out * *nchunks_out;
+  q.ntilesB = c->ntl;
+  q.nB = c->ntl * c->nch;
   if (prepared) { *prepared = q; *ksplit_out = p.ksplit; return 1; }
   const int units = p.ksplit == 16 ? 4 : 1;
   const size_t shm_a = (size_t)(p.ksplit - 1) * 256 * sizeof(float) + (size_t)16 * 16 * 2 * sizeof(double);
@@ -3372,8 +3328,7 @@ int mfma_bwd_dual_try(const n3d_conv_geom* g, bool transposed, const float* dy, 
   if (p.ksplit == 16) N3D_LAUNCH(conv_bwd16_dual_kernel<16>, grid, dim3(1024), shm, s, q);
   else N3D_LAUNCH(conv_bwd16_dual_kernel<4>, grid, dim3(256), shm, s, q);
   g_fold_launches[3] += 1;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(bwd dual) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(bwd dual)");
   return 1;
 }
 
@@ -3389,12 +3344,6 @@ int mfma_bwd_quad_ok(const n3d_conv_geom* g0, bool t0, const n3d_conv_geom* g1, 
   return p0.ok && p1.ok && p0.ksplit == p1.ksplit && p0.ksplit != 1;
 }
 
-struct BwdOne {  // one conv's backward operands for the quad launch
-  const n3d_conv_geom* g; bool transposed; const float* dy; int64_t dyld; const float* wp; float* dx; int64_t dxld; int flags_d;
-  const float* relu_src; int64_t rld; const float* out_gate; const float* x; int64_t xld; int flags_w; const float* in_gate;
-  float* partial; float* pbias; size_t avail; int nch, ntl;
-};
-
 int mfma_bwd_quad_try(BwdOne* c0, BwdOne* c1, hipStream_t s) {
   QuadArgs z;
   int k0 = 0, k1 = 0;
@@ -3402,9 +3351,7 @@ int mfma_bwd_quad_try(BwdOne* c0, BwdOne* c1, hipStream_t s) {
   DualArgs* qs[2] = {&z.q0, &z.q1};
   int* ks[2] = {&k0, &k1};
   for (int i = 0; i < 2; ++i) {
-    BwdOne* c = cs[i];
-    const int r = mfma_bwd_dual_try(c->g, c->transposed, c->dy, c->dyld, c->wp, c->dx, c->dxld, c->flags_d, c->relu_src, c->rld, c->out_gate,
-                                    c->x, c->xld, c->flags_w, c->in_gate, c->partial, c->pbias, c->avail, &c->nch, &c->ntl, s, qs[i], ks[i]);
+    const int r = mfma_bwd_dual_try(cs[i], s, qs[i], ks[i]);
     if (r != 1) return r;
   }
   if (k0 != k1) return 0;
@@ -3417,8 +3364,7 @@ int mfma_bwd_quad_try(BwdOne* c0, BwdOne* c1, hipStream_t s) {
   if (k0 == 16) N3D_LAUNCH(conv_bwd16_quad_kernel<16>, dim3((unsigned)(z.n0 + n1)), dim3(1024), shm, s, z);
   else N3D_LAUNCH(conv_bwd16_quad_kernel<4>, dim3((unsigned)(z.n0 + n1)), dim3(256), shm, s, z);
   g_fold_launches[4] += 1;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("conv(bwd quad) launch: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  N3D_LAUNCH_CHECK_AS("conv(bwd quad)");
   return 1;
 }
 

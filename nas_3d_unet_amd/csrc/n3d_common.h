@@ -37,6 +37,16 @@ void set_error(const char* fmt, ...);
     }                                                                          \
   } while (0)
 
+// the same for the launchers of a kernel family, whose messages name the family ("conv(vox64)") and not a line
+#define N3D_LAUNCH_CHECK_AS(family_)                                           \
+  do {                                                                         \
+    hipError_t e__ = hipGetLastError();                                        \
+    if (e__ != hipSuccess) {                                                   \
+      n3d::set_error(family_ " launch: %s", hipGetErrorString(e__));           \
+      return N3D_ERR_HIP;                                                      \
+    }                                                                          \
+  } while (0)
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- entry signals (include/n3d.h, "Entry signals"): a stream hand-off signal carried in the entry of the next kernel of its stream.
@@ -376,9 +386,5 @@ __device__ __forceinline__ float wave_sum_strided_f(float v, int cpb) {
 __device__ __forceinline__ float wave_sum_f(float v) { return wave_classsum_f(v, 1); }
 __device__ __forceinline__ double wave_sum_d(double v) { return wave_classsum_d(v, 1); }
 #endif
-
-// data-gradient extras of one conv in a paired MFMA launch (conv_mfma.hip, mfma_conv_pair_try): ReLU mask source of the
-// conv input (and its pitch), per-(b,c) gate applied to the result
-struct PairExtras { const float* relu_src; int64_t rld; const float* out_gate; };
 
 }  // namespace n3d
