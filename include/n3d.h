@@ -674,6 +674,57 @@ int n3d_image_finish(const float* y, int64_t sc, int64_t sv, int C, const int32_
                      const double* sum, int K, double* probs, uint8_t* labels, double threshold, int inclusive, const float* mask_box, int Cv,
                      int bx, int by, int bz, const int32_t* origin, void* stream);
 
+/* ---- Segmentation metrics: a predicted label volume scored against the truth per region -- the four columns plot.py:151-173
+ * draws (Dice, Sensitivity, Specificity, Hausdorff95 of ET / WT / TC).  The reference has no code for them; the definitions are
+ * the BraTS portal's and medpy.metric.binary.hd95's, at unit voxel spacing.
+ *   labels: uint8 {0, 1, 2, 4}.  Regions, in tr.eval_result()'s order: 0 WT = label != 0, 1 TC = label in {1, 4}, 2 ET = label == 4.
+ *   pred: DEVICE uint8 (FX, FY, FZ), the full image.  truth: DEVICE uint8 (BX, BY, BZ), the box at `origin` inside the image; the
+ *     truth is zero outside its box.  full / box / origin: HOST int32[3] each.  FX * FY * FZ < 2^31.
+ *   counts: TP, FP, FN per region over the full image (TN = FX * FY * FZ - TP - FP - FN is the host's).
+ *   surface of a mask: a mask voxel with a 6-neighbour that is unset or outside the image
+ *     (mask & ~binary_erosion(mask, generate_binary_structure(3, 1), border_value=0)).
+ *   d2_B(v): squared Euclidean distance from voxel v to the nearest voxel of surface B: an integer.  Per region the multiset D =
+ *     {d2_T(v): v on the prediction's surface} + {d2_P(v): v on the truth's surface}; HD95 is numpy's linear-interpolation
+ *     percentile 95 of sqrt(D).  From the device come only n = |D|, the order statistics D[k] and D[min(k + 1, n - 1)] of the
+ *     sorted D with k = floor((n - 1) * 0.95) (one fp64 product, as numpy forms it) and max D; the host interpolates.  D is
+ *     empty (n = 0) when either mask of the region is.
+ * Everything is integer work with integer atomics (add / min / max commute exactly): the same inputs give the same bits.
+ *
+ * rec: DEVICE int64[N3D_SEG_REC_WORDS], 8-byte aligned; the subject's one device -> host copy.  Words 0..8: counts[region][TP, FP,
+ * FN]; 9..20: order[region][n, D[k], D[k + 1], max D]; 21..29 hold int32 bbox[region][lo x, y, z, hi x, y, z], the bounding box
+ * (inclusive) of the union of both surfaces of the region.  Before n3d_seg_regions the caller fills counts and order with 0 and
+ * every bbox with {INT32_MAX x 3, -1 x 3}, which is also what a region without surface keeps.
+ * flags: DEVICE uint8 (FX, FY, FZ): bits 0..2 the prediction's surface of WT / TC / ET, bits 3..5 the truth's.
+ * dist: DEVICE int32 [njobs][FX * FY * FZ]; hist: DEVICE uint32 [3][hist_len], zeroed by the caller per subject.
+ * n3d_seg_workspace_bytes: bytes of one allocation holding rec, flags, dist (6 jobs) and hist for an image shape, 0 on a bad shape;
+ * offsets (HOST int64[5], may be NULL) receives the byte offsets of rec, flags, dist, hist and hist_len itself. */
+#define N3D_SEG_REGIONS 3
+#define N3D_SEG_REC_WORDS 30
+#define N3D_SEG_REC_ORDER 9      /* first word of order[][] */
+#define N3D_SEG_REC_BBOX 21      /* first word of bbox[][] (int32 view: word * 2) */
+#define N3D_SEG_INF (1 << 29)    /* "no source": INF + 1023^2 stays below 2^31 */
+#define N3D_SEG_MAX_AXIS 1024
+size_t n3d_seg_workspace_bytes(int FX, int FY, int FZ, int64_t* offsets);
+/* ONE launch: every voxel's labels are read once (the six neighbours again, through the cache); writes flags, adds the counts
+ * (per wave, then one atomic per workgroup and nonzero counter) and combines the bounding boxes (atomic min / max). */
+int n3d_seg_regions(const uint8_t* pred, const uint8_t* truth, const int32_t* full, const int32_t* box, const int32_t* origin,
+                    uint8_t* flags, int64_t* rec, void* stream);
+/* Exact squared distance transform, separable: out[i] = min_j (f[j] + (i - j)^2) along z, then y, then x (three launches), brute
+ * force over the line held in LDS.  Job j (0 <= j < njobs <= 6) takes bit j of flags as its sources (f = 0 there, N3D_SEG_INF
+ * elsewhere) and writes dist[j]; it works inside bbox[j % nreg] only (bbox: DEVICE int32 [nreg][6] as in rec, read on the device
+ * and clipped to the image; the workgroups walk the box's tiles; an empty box does nothing) -- voxels of dist[j] outside the box are left
+ * untouched.  A box without a source voxel gives N3D_SEG_INF throughout.  Each pass after the first works in place (a workgroup
+ * owns whole lines and holds them in LDS before it writes).  An axis longer than N3D_SEG_MAX_AXIS: N3D_ERR_UNSUPPORTED. */
+int n3d_seg_edt(const uint8_t* flags, int njobs, int nreg, const int32_t* full, const int32_t* bbox, int32_t* dist, void* stream);
+/* ONE launch: every prediction-surface voxel of region r adds 1 to hist[r][dist[3 + r][v]], every truth-surface voxel to
+ * hist[r][dist[r][v]] (dist as n3d_seg_edt with njobs = 6, nreg = 3 wrote it from the same flags and bbox); only the box around
+ * bbox's three boxes is walked (every surface voxel lies in it).  A distance >= hist_len (N3D_SEG_INF: the other surface is empty)
+ * is not counted. */
+int n3d_seg_sample(const uint8_t* flags, const int32_t* full, const int32_t* bbox, const int32_t* dist, uint32_t* hist, int64_t hist_len,
+                   void* stream);
+/* ONE launch of three workgroups: scans hist[r] up to the squared diagonal of bbox[r] and writes order[r] into rec. */
+int n3d_seg_order(const uint32_t* hist, int64_t hist_len, int64_t* rec, void* stream);
+
 /* ---- RCCL exchange step of data-parallel training (no reference counterpart: config.yml:54 `multi_gpus` is never read;
  * SURVEY 8(e)).  One process per GPU; the hot path's only exchange is a SUM all-reduce of the flat fp32 gradient buffer, in
  * place, stream-ordered on `stream` (a side HIP stream lets it run under the backward kernels of the next bucket).

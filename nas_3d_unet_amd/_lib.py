@@ -236,6 +236,11 @@ PROTOTYPES = {
     "n3d_image_embed": (_i, [_p, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i64, _p]),
     "n3d_image_add": (_i, [_p, _i64, _i64, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i, _p]),
     "n3d_image_finish": (_i, [_p, _i64, _i64, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i, _p, _p, C.c_double, _i, _p, _i, _i, _i, _i, C.POINTER(C.c_int32), _p]),
+    "n3d_seg_workspace_bytes": (_sz, [_i, _i, _i, C.POINTER(C.c_int64)]),
+    "n3d_seg_regions": (_i, [_p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _p, _p]),
+    "n3d_seg_edt": (_i, [_p, _i, _i, C.POINTER(C.c_int32), _p, _p, _p]),
+    "n3d_seg_sample": (_i, [_p, C.POINTER(C.c_int32), _p, _p, _p, _i64, _p]),
+    "n3d_seg_order": (_i, [_p, _i64, _p, _p]),
     "n3d_comm_available": (_i, []),
     "n3d_comm_unique_id": (_i, [_p]),
     "n3d_comm_init": (_i, [_p, _i, _i, C.POINTER(C.c_void_p)]),
