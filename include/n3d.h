@@ -725,6 +725,60 @@ int n3d_seg_sample(const uint8_t* flags, const int32_t* full, const int32_t* bbo
 /* ONE launch of three workgroups: scans hist[r] up to the squared diagonal of bbox[r] and writes order[r] into rec. */
 int n3d_seg_order(const uint32_t* hist, int64_t hist_len, int64_t* rec, void* stream);
 
+/* ---- Label clean-up: the step between prediction and scoring -- connected components of a predicted label volume's foreground and
+ * the two rules BraTS submissions apply to them.  The reference has no code for it; the definitions are scipy.ndimage.label's.
+ *   labels / mask: DEVICE uint8 (FX, FY, FZ); any nonzero byte is foreground.  full: HOST int32[3].  FX * FY * FZ < 2^31.
+ *   connectivity: 6, 18 or 26 -- scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3).  Neighbours are neighbours by coordinate:
+ *     (x, y, FZ - 1) and (x, y + 1, 0) are not.
+ *   id of a component: the smallest linear index (x * FY + y) * FZ + z of its voxels -- whatever order the work runs in; scipy's
+ *     labels map onto it by "minimum linear index per label".  comp: DEVICE int32 (FX, FY, FZ), the id per voxel, -1 on background.
+ *   Step A: a component is kept iff size >= min_voxels and (not keep_largest or it is the largest; equal sizes: the smallest id);
+ *     voxels of the others become 0.  If the largest is smaller than min_voxels nothing is kept.
+ *   Step B: e = label-4 voxels in kept components; if 0 < e < et_min_voxels they become 1 (e == et_min_voxels changes nothing).
+ *   With every rule off (0, 0, 0) out equals labels and the record is still filled.
+ * Union-find on the int32 parent array (parent[v] <= v, -1 on background): a workgroup labels an 8 x 8 x 32 tile in LDS, the
+ * voxels on tile faces unite across tiles with atomicMin, a flatten pass writes comp from parent and counts the sizes.  Integer
+ * atomics only (min, add, max): the same inputs give the same bits.  No kernel waits on another workgroup.
+ *
+ * rec: DEVICE int64[N3D_CC_REC_WORDS], 8-byte aligned, in the workspace at the offset the query reports; n3d_cc_clean clears and
+ * fills it.  Words: 0 components, 1 components kept, 2 foreground voxels, 3 voxels kept, 4 size of the largest component, 5 its id
+ * (-1 without a component), 6 label-4 voxels, 7 label-4 voxels in kept components, 8 whether step B relabelled them (0 / 1),
+ * 9 scratch: max over components of (size << 32) | (0xFFFFFFFF - id).
+ * n3d_cc_workspace_bytes: bytes of one allocation holding parent, comp, the per-root sizes and label-4 counts (int32 per voxel
+ * each), the per-root verdicts (a byte per voxel) and rec -- 17 bytes per voxel; 0 on a bad shape.  offsets (HOST int64[6], may be
+ * NULL) receives the byte offsets of those six, in that order. */
+#define N3D_CC_REC_WORDS 10
+#define N3D_CC_REC_COMPONENTS 0
+#define N3D_CC_REC_KEPT 1
+#define N3D_CC_REC_VOXELS_IN 2
+#define N3D_CC_REC_VOXELS_KEPT 3
+#define N3D_CC_REC_LARGEST_SIZE 4
+#define N3D_CC_REC_LARGEST_ID 5
+#define N3D_CC_REC_ET_IN 6
+#define N3D_CC_REC_ET_KEPT 7
+#define N3D_CC_REC_ET_RELABELLED 8
+#define N3D_CC_REC_PACKED 9
+size_t n3d_cc_workspace_bytes(int FX, int FY, int FZ, int64_t* offsets);
+/* THREE launches (local, merge, flatten): comp = the component ids of mask; parent (DEVICE int32 (FX, FY, FZ), 4-byte aligned, not
+ * comp) is scratch.  A connectivity other than 6 / 18 / 26, a NULL pointer or a bad shape: N3D_ERR_INVALID. */
+int n3d_cc_label(const uint8_t* mask, const int32_t* full, int connectivity, int32_t* parent, int32_t* comp, void* stream);
+/* SIX launches (local, merge, flatten with the size counts, two decide launches -- the verdicts need the maximum, the surviving
+ * label-4 count needs the verdicts --, apply): out (DEVICE uint8 (FX, FY, FZ), not labels) = labels cleaned by steps A and B.
+ * workspace: n3d_cc_workspace_bytes(FX, FY, FZ) bytes, 8-byte aligned; nothing in it has to be cleared.  Errors as n3d_cc_label;
+ * negative thresholds: N3D_ERR_INVALID. */
+int n3d_cc_clean(const uint8_t* labels, const int32_t* full, int connectivity, int64_t min_voxels, int keep_largest, int64_t et_min_voxels,
+                 void* workspace, uint8_t* out, void* stream);
+/* The launches first .. last (0 local, 1 merge, 2 flatten, 3 decide: maximum, 4 decide: verdicts, 5 apply) of n3d_cc_clean, for
+ * measuring them one by one: a launch expects the workspace as the launches before it leave it, and 0 .. k repeats (launch 0
+ * clears what the later ones add to).  n3d_cc_clean is variant N3D_CC_TILED, launches 0 .. 5.  N3D_CC_GLOBAL_ONLY is the design
+ * without the LDS tile phase -- launch 0 only makes every foreground voxel its own root, launch 1 unites every voxel with all its
+ * forward neighbours in memory -- kept so that the two can be timed against each other; same results. */
+#define N3D_CC_PHASES 6
+#define N3D_CC_TILED 0
+#define N3D_CC_GLOBAL_ONLY 1
+int n3d_cc_phases(int variant, int first, int last, const uint8_t* labels, const int32_t* full, int connectivity, int64_t min_voxels,
+                  int keep_largest, int64_t et_min_voxels, void* workspace, uint8_t* out, void* stream);
+
 /* ---- RCCL exchange step of data-parallel training (no reference counterpart: config.yml:54 `multi_gpus` is never read;
  * SURVEY 8(e)).  One process per GPU; the hot path's only exchange is a SUM all-reduce of the flat fp32 gradient buffer, in
  * place, stream-ordered on `stream` (a side HIP stream lets it run under the backward kernels of the next bucket).

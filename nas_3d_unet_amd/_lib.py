@@ -241,6 +241,10 @@ PROTOTYPES = {
     "n3d_seg_edt": (_i, [_p, _i, _i, C.POINTER(C.c_int32), _p, _p, _p]),
     "n3d_seg_sample": (_i, [_p, C.POINTER(C.c_int32), _p, _p, _p, _i64, _p]),
     "n3d_seg_order": (_i, [_p, _i64, _p, _p]),
+    "n3d_cc_workspace_bytes": (_sz, [_i, _i, _i, C.POINTER(C.c_int64)]),
+    "n3d_cc_label": (_i, [_p, C.POINTER(C.c_int32), _i, _p, _p, _p]),
+    "n3d_cc_clean": (_i, [_p, C.POINTER(C.c_int32), _i, _i64, _i, _i64, _p, _p, _p]),
+    "n3d_cc_phases": (_i, [_i, _i, _i, _p, C.POINTER(C.c_int32), _i, _i64, _i, _i64, _p, _p, _p]),
     "n3d_comm_available": (_i, []),
     "n3d_comm_unique_id": (_i, [_p]),
     "n3d_comm_init": (_i, [_p, _i, _i, C.POINTER(C.c_void_p)]),
