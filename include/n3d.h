@@ -522,6 +522,37 @@ int n3d_head_bwd(const n3d_head* h, const float* dp, int64_t dsb, int64_t dsc, i
 int n3d_head_eval(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t psv, const void* t, int64_t tsb, int64_t tsc, int64_t tsv,
                   float smooth, float thr, double* partial, double* hpartial, double* sums, float* loss, double* acc, void* stream);
 
+/* ---- Tversky / focal / cross-entropy loss in the head's passes and on probabilities.  For a (b, c) pair with A = sum p*t, P = sum p,
+ * T = sum t over the sample's N voxels, logit z and p = sigmoid(z):
+ *   TI = (A + smooth) / (A + alpha (P - A) + beta (T - A) + smooth),   u = max(1 - TI, 0),
+ *   loss = mean_bc u^gamma + bce_weight * mean_bcv [max(z, 0) - z t + log1p(exp(-|z|))].
+ * A pair with u == 0 contributes 0 and a zero gradient for every gamma.  alpha, beta >= 0, alpha + beta > 0, gamma > 0,
+ * bce_weight >= 0, smooth > 0, otherwise N3D_ERR_INVALID.  alpha = beta = 0.5, gamma = 1, bce_weight = 0, smooth = s / 2 is the Dice
+ * loss of n3d_head_fwd with smooth = s.
+ * n3d_head_loss_fwd / _eval / _bwd: n3d_head_fwd / n3d_head_eval / n3d_head_bwd (same operands, layouts and scratch) with this loss.
+ *   bce_weight == 0: every head shape of the Dice mode, records of S = 3 doubles.  bce_weight > 0: Co = 3 only (N3D_ERR_UNSUPPORTED
+ *   otherwise), and the records hold S = 4 doubles, the fourth being the cross-entropy sum:
+ *   partial: double[B][Co][n3d_head_rows(N)][S], sums: double[B][Co][S].
+ *   coef: float[2 * B * Co + 1] written by n3d_head_loss_fwd and read by n3d_head_loss_bwd: per pair (k2, k0) with
+ *   d loss / d p = k2 t + k0 for the Tversky term, then kb = bce_weight / (B Co N); d loss / d z = (k2 t + k0) p (1 - p) + kb (p - t).
+ *   n3d_head_loss_eval adds the configured loss into acc[0]; the region counts are those of n3d_head_eval.
+ * n3d_tversky_fwd / _bwd: the loss on probabilities (n3d_dice_fwd / n3d_dice_bwd operands; partial: double[B][C][n3d_dice_rows(N)][3],
+ *   sums: double[B][C][3], coef: float[2 * B * C]).  The cross-entropy term is formed from logits and exists in the head only:
+ *   bce_weight > 0 is N3D_ERR_UNSUPPORTED here. */
+typedef struct n3d_loss { float alpha, beta, gamma, bce_weight, smooth; } n3d_loss;
+int n3d_head_loss_fwd(const n3d_head* h, const n3d_loss* l, float* p, int64_t psb, int64_t psc, int64_t psv, float* logits, const void* t,
+                      int64_t tsb, int64_t tsc, int64_t tsv, double* partial, double* sums, float* coef, float* loss, void* stream);
+int n3d_head_loss_eval(const n3d_head* h, const n3d_loss* l, float* p, int64_t psb, int64_t psc, int64_t psv, const void* t, int64_t tsb,
+                       int64_t tsc, int64_t tsv, float thr, double* partial, double* hpartial, double* sums, float* loss, double* acc,
+                       void* stream);
+int n3d_head_loss_bwd(const n3d_head* h, const void* t, int64_t tsb, int64_t tsc, int64_t tsv, const float* coef, const float* dloss, void* dx,
+                      int64_t dxld, int dx_dtype, int flags, float* dw, float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred,
+                      void* stream);
+int n3d_tversky_fwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const float* t, int64_t tsb, int64_t tsc, int64_t tsv, int B, int C,
+                    int64_t N, const n3d_loss* l, double* partial, double* sums, float* coef, float* loss, void* stream);
+int n3d_tversky_bwd(const float* t, int64_t tsb, int64_t tsc, int64_t tsv, int B, int C, int64_t N, const float* coef, const float* dloss,
+                    float* dp, int64_t dsb, int64_t dsc, int64_t dsv, void* stream);
+
 /* ---- layout: NCDHW <-> NDHWC (caller tensors arrive NCDHW: train.py:118-119) ---------------------- */
 int n3d_ncdhw_to_ndhwc(const float* src, float* dst, int64_t dld, int B, int C, int64_t N, void* stream);
 int n3d_ndhwc_to_ncdhw(const float* src, int64_t sld, float* dst, int B, int C, int64_t N, void* stream);

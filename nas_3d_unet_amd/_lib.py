@@ -95,6 +95,11 @@ class Head(C.Structure):
                 ("x_node_stride", C.c_int64), ("dx_node_stride", C.c_int64), ("node_c", C.c_int32), ("t_dtype", C.c_int32)]
 
 
+class Loss(C.Structure):
+    """n3d_loss (include/n3d.h)"""
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("gamma", C.c_float), ("bce_weight", C.c_float), ("smooth", C.c_float)]
+
+
 class PatchDesc(C.Structure):
     """n3d_patch_desc (include/n3d.h)"""
     _fields_ = [("corner", C.c_int32 * 3), ("perm", C.c_int32 * 3), ("flip", C.c_int32 * 3)]
@@ -218,6 +223,11 @@ PROTOTYPES = {
     "n3d_head_bwd": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _sz,
                           C.POINTER(FinalJob), _p]),
     "n3d_head_eval": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f, _f, _p, _p, _p, _p, _p, _p]),
+    "n3d_head_loss_fwd": (_i, [C.POINTER(Head), C.POINTER(Loss), _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    "n3d_head_loss_eval": (_i, [C.POINTER(Head), C.POINTER(Loss), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f, _p, _p, _p, _p, _p, _p]),
+    "n3d_head_loss_bwd": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _sz, C.POINTER(FinalJob), _p]),
+    "n3d_tversky_fwd": (_i, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i, _i, _i64, C.POINTER(Loss), _p, _p, _p, _p, _p]),
+    "n3d_tversky_bwd": (_i, [_p, _i64, _i64, _i64, _i, _i, _i64, _p, _p, _p, _i64, _i64, _i64, _p]),
     "n3d_ncdhw_to_ndhwc": (_i, [_p, _p, _i64, _i, _i, _i64, _p]),
     "n3d_ndhwc_to_ncdhw": (_i, [_p, _i64, _p, _i, _i, _i64, _p]),
     "n3d_patch_batch": (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(PatchDesc), _i, _i, _i, _p, _i64, _p, _p]),

@@ -2226,6 +2226,47 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
   }
 }
 
+// Tversky / focal loss on probabilities (n3d_tversky_fwd / _bwd): the partial rows of dice_reduce_kernel, a finalize of its own
+// (one wave per (b, c) pair, as dice_finalize_kernel) that forms the loss and the pairs' gradient coefficients, and the affine gradient
+__global__ __launch_bounds__(256) void tversky_finalize_kernel(const double* __restrict__ partial, int rows, int BC, TverskySpec tv,
+                                                               double* __restrict__ sums /*[BC][3]*/, float* __restrict__ coef /*[BC][2]*/,
+                                                               float* __restrict__ loss) {
+  __shared__ double term[4];
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  double acc = 0;
+  for (int i = wave; i < BC; i += 4) {
+    double s[3] = {0, 0, 0};
+    for (int r = lane; r < rows; r += 64)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s[k] += partial[((int64_t)i * rows + r) * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = wave_sum_d(s[k]);
+    if (lane == 0) {
+      sums[i * 3] = s[0]; sums[i * 3 + 1] = s[1]; sums[i * 3 + 2] = s[2];
+      acc += tversky_term(s[0], s[1], s[2], tv, BC, coef + 2 * i);
+    }
+  }
+  if (lane == 0) term[wave] = acc;
+  __syncthreads();
+  if (t == 0) *loss = (float)((term[0] + term[1] + term[2] + term[3]) / BC);
+}
+
+__global__ __launch_bounds__(256) void tversky_bwd_kernel(const float* __restrict__ t, int64_t tsb, int64_t tsc, int64_t tsv, int64_t N,
+                                                          const float* __restrict__ coef, const float* __restrict__ dloss,
+                                                          float* __restrict__ dp, int64_t dsb, int64_t dsc, int64_t dsv) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int i = b * gridDim.y + c;
+  const float gl = dloss ? *dloss : 1.0f;
+  const float k2 = coef[2 * i] * gl, k0 = coef[2 * i + 1] * gl;
+  const float* tp = t + b * tsb + c * tsc;
+  float* op = dp + b * dsb + c * dsc;
+  const int64_t v0 = (int64_t)blockIdx.x * DICE_CHUNK;
+  for (int j = threadIdx.x; j < DICE_CHUNK; j += 256) {
+    const int64_t v = v0 + j;
+    if (v < N) op[v * dsv] = fmaf(k2, tp[v * tsv], k0);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // layout
 // ------------------------------------------------------------------------------------------------
@@ -3254,6 +3295,28 @@ int n3d_dice_bwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const fl
   const int rows = (int)cdiv(N, DICE_CHUNK);
   N3D_LAUNCH(dice_bwd_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, p, psb, psc, psv, t, tsb, tsc, tsv, N, B * C,
                      (double)smooth, sums, dloss, dp, dsb, dsc, dsv);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_tversky_fwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const float* t, int64_t tsb, int64_t tsc, int64_t tsv, int B, int C,
+                    int64_t N, const n3d_loss* l, double* partial, double* sums, float* coef, float* loss, void* stream) {
+  N3D_CHECK_ARG(p && t && partial && sums && coef && loss && B > 0 && C > 0 && N > 0, "tversky_fwd: bad args");
+  if (int e = check_loss(l, "tversky_fwd")) return e;
+  if (l->bce_weight > 0.f)
+    N3D_UNSUPPORTED("tversky_fwd: the cross-entropy term is formed from logits and exists in the fused head only (bce_weight=%g)", l->bce_weight);
+  const int rows = (int)cdiv(N, DICE_CHUNK);
+  N3D_LAUNCH(dice_reduce_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, p, psb, psc, psv, t, tsb, tsc, tsv, N, partial);
+  N3D_LAUNCH(tversky_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, rows, B * C, tversky_spec(l), sums, coef, loss);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_tversky_bwd(const float* t, int64_t tsb, int64_t tsc, int64_t tsv, int B, int C, int64_t N, const float* coef, const float* dloss,
+                    float* dp, int64_t dsb, int64_t dsc, int64_t dsv, void* stream) {
+  N3D_CHECK_ARG(t && coef && dp && B > 0 && C > 0 && N > 0, "tversky_bwd: bad args");
+  const int rows = (int)cdiv(N, DICE_CHUNK);
+  N3D_LAUNCH(tversky_bwd_kernel, dim3(rows, C, B), dim3(256), 0, (hipStream_t)stream, t, tsb, tsc, tsv, N, coef, dloss, dp, dsb, dsc, dsv);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }

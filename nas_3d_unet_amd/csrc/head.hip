@@ -59,6 +59,17 @@ __device__ __forceinline__ void head_target_quads_take(const uint32_t (&q)[NCO],
     for (int co = 0; co < NCO; ++co) tv[k][co] = (float)((lds[co][(tid >> 2) + 64 * k] >> (8 * (tid & 3))) & 0xffu);
 }
 
+// Binary cross-entropy of a voxel from its logit, max(z, 0) - z t + log1p(exp(-|z|)), given en = exp(-z) (the sigmoid's): exp(-|z|) is en
+// for z >= 0 and 1 / en below (en = inf gives 0), and log1p(e) on [0, 1] is log(u) e / (u - 1) with u = 1 + e, which cancels the rounding
+// of u (e where u == 1).  The hardware logarithm and reciprocal: about 4 ulp per voxel.  With the library's expf and log1pf here the
+// forward pass became ALU-bound: 68.8 instead of 46.5 us at (2, 12, 128^3) (profiles/loss_probe.log).
+__device__ __forceinline__ float head_bce_voxel(float z, float en, float t) {
+  const float e = z >= 0.f ? en : __fdividef(1.0f, en);
+  const float u = 1.0f + e;
+  const float l1p = u == 1.0f ? e : __logf(u) * __fdividef(e, u - 1.0f);
+  return fmaxf(z, 0.f) - z * t + l1p;
+}
+
 struct HeadFwdArgs {
   const void* x; int64_t xld; int64_t N; int64_t xns; int qn;   // xns / qn: node stride and quads per node (qn == 0: pitched layout)
   const float* w; const float* bias; const float* gate;
@@ -76,13 +87,16 @@ struct HeadFwdArgs {
 // target bytes, the same sums bit for bit
 // EVAL: the evaluation form (n3d_head_eval) -- the same conv, sigmoid and soft sums, plus the two hard sums of the thresholded
 // prediction (prediction.py:157-164: p >= thr) per row; two compares and two adds per voxel and channel on an HBM-bound pass
-template <typename TX, int CIQ, int NCO, typename TT = float, bool EVAL = false>
+// BCE: the cross-entropy form (n3d_head_loss_fwd / _eval with bce_weight > 0) -- a FOURTH sum per row, the voxels' binary cross-entropy
+// from the logit, max(z, 0) - z t + log1p(exp(-|z|)); the partial records then hold S = 4 doubles
+template <typename TX, int CIQ, int NCO, typename TT = float, bool EVAL = false, bool BCE = false>
 __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
   N3D_CHAIN_PRIO();
   constexpr int CI = CIQ * 4;
+  constexpr int S = BCE ? 4 : 3;              // sums per (b, c, row) record
   constexpr bool ALL = NCO != HEAD_COMAX;     // every computed channel is a real one
   __shared__ float wsm[HEAD_COMAX][CI];
-  __shared__ double red[HEAD_COMAX * 3][4];
+  __shared__ double red[HEAD_COMAX * S][4];
   const int b = blockIdx.y, tid = threadIdx.x;
   for (int i = tid; i < HEAD_COMAX * CI; i += 256) {
     const int co = i / CI, ci = i - co * CI;
@@ -102,6 +116,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
   float shi[HEAD_COMAX], shp[HEAD_COMAX];     // EVAL: hard intersection and predicted voxels (integers, exact in fp32 per lane)
 #pragma unroll
   for (int co = 0; co < HEAD_COMAX; ++co) shi[co] = shp[co] = 0.f;
+  float sce[HEAD_COMAX] = {0.f, 0.f, 0.f, 0.f};     // BCE: cross-entropy
   const int64_t v0 = (int64_t)blockIdx.x * HEAD_CHUNK;
   // every operand of the workgroup's four voxel rounds is requested before the first use (predicated, no early exit: a `break` in
   // the loop kept each round's loads behind the previous round's stores -- 2.6 TB/s on a 37 MB pass)
@@ -146,7 +161,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
 #pragma unroll
     for (int co = 0; co < NCO; ++co) {
       if (ALL || co < a.Co) {
-        const float pr = 1.0f / (1.0f + expf(-z[co]));
+        const float en = expf(-z[co]);
+        const float pr = 1.0f / (1.0f + en);
         if (a.p) a.p[b * a.psb + co * a.psc + v * a.psv] = pr;
         if (a.logits) a.logits[b * a.psb + co * a.psc + v * a.psv] = z[co];
         spt[co] = fmaf(pr, tv[co], spt[co]); sp[co] += pr; st[co] += tv[co];
@@ -154,6 +170,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
           const float hard = pr >= a.thr ? 1.f : 0.f;
           shi[co] = fmaf(hard, tv[co], shi[co]); shp[co] += hard;
         }
+        if constexpr (BCE) sce[co] += head_bce_voxel(z[co], en, tv[co]);
       }
     }
   }
@@ -165,7 +182,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
     const double d0 = wave_sum4_d(spt[0], spt[1], spt[2], spt[3]), d1 = wave_sum4_d(sp[0], sp[1], sp[2], sp[3]),
                  d2 = wave_sum4_d(st[0], st[1], st[2], st[3]);
     const int co = classsum4_sel(lane);
-    if ((lane & 15) == 0) { red[co * 3][wave] = d0; red[co * 3 + 1][wave] = d1; red[co * 3 + 2][wave] = d2; }
+    if ((lane & 15) == 0) { red[co * S][wave] = d0; red[co * S + 1][wave] = d1; red[co * S + 2][wave] = d2; }
+    if constexpr (BCE) {
+      const double d3 = wave_sum4_d(sce[0], sce[1], sce[2], sce[3]);
+      if ((lane & 15) == 0) red[co * S + 3][wave] = d3;
+    }
   }
   __shared__ double hred[EVAL ? HEAD_COMAX * 2 : 1][4];
   if constexpr (EVAL) {
@@ -174,9 +195,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
     if ((lane & 15) == 0) { hred[co * 2][wave] = d3; hred[co * 2 + 1][wave] = d4; }
   }
   __syncthreads();
-  if (tid < a.Co * 3) {
-    const int co = tid / 3, k = tid - co * 3;
-    a.partial[(((int64_t)b * a.Co + co) * a.rows + blockIdx.x) * 3 + k] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+  if (tid < a.Co * S) {
+    const int co = tid / S, k = tid - co * S;
+    a.partial[(((int64_t)b * a.Co + co) * a.rows + blockIdx.x) * S + k] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
   }
   if constexpr (EVAL) {
     if (tid < a.Co * 2) {
@@ -204,6 +225,7 @@ __device__ __forceinline__ void head_eval_hard_walk(const HeadEvalAcc& ev, int r
 }
 
 // thread 0, behind a barrier that orders the hs / sums / loss stores of the finalize
+template <int S = 3>     // doubles per sums record
 __device__ __forceinline__ void head_eval_add(const HeadEvalAcc& ev, int BC, const double (*hs)[2], const double* sums, const float* loss) {
   const int Co = ev.Co, B = BC / Co;
   double* acc = ev.acc;
@@ -214,7 +236,7 @@ __device__ __forceinline__ void head_eval_add(const HeadEvalAcc& ev, int BC, con
     double* ac = acc + 4 + 4 * c;
     for (int b = 0; b < B; ++b) {
       const int i = b * Co + c;
-      const double I = hs[i][0], P = hs[i][1], T = sums[i * 3 + 2];
+      const double I = hs[i][0], P = hs[i][1], T = sums[i * S + 2];
       ac[0] += I; ac[1] += P; ac[2] += T;
       ac[3] += (P + T == 0.0) ? 1.0 : 2.0 * I / (P + T);
     }
@@ -228,28 +250,48 @@ __device__ __forceinline__ void head_eval_add(const HeadEvalAcc& ev, int BC, con
 // 4.6 us at 64^3, between the head's forward and backward passes.
 // EVAL: the flat walk also reduces the hard sums of n3d_head_eval (same record index, [BC][rows][2]), and the batch is then added
 // into the evaluation accumulator (head_eval_add); the loss is formed by the same code.
-template <bool EVAL = false>
+// TV: the Tversky / focal / cross-entropy loss of n3d_head_loss_fwd / _eval instead of Dice: records of S doubles (S = 4: the fourth
+// is the cross-entropy sum), a pair's term is u^gamma + bce_weight * CE / N (tversky_term, n3d_common.h), the loss is the mean of the
+// terms, and the coefficients of the backward pass go to lf.coef: (k2, k0) per pair, then kb = bce_weight / (BC N)
+struct HeadLossFin { TverskySpec tv; double w, inv_n; float* coef; };
+
+template <int S, bool TV>
+__device__ __forceinline__ double head_pair_term(const double* q, double smooth, const HeadLossFin& lf, int i, int BC) {
+  if constexpr (TV) {
+    const double term = tversky_term(q[0], q[1], q[2], lf.tv, BC, lf.coef ? lf.coef + 2 * i : nullptr);
+    if constexpr (S == 4) return term + lf.w * q[3] * lf.inv_n;
+    return term;
+  } else {
+    return (2.0 * q[0] + smooth) / (q[1] + q[2] + smooth);
+  }
+}
+
+template <bool EVAL = false, int S = 3, bool TV = false>
 __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* __restrict__ partial, int rows, int BC, double smooth,
-                                                                 double* __restrict__ sums, float* __restrict__ loss, HeadEvalAcc ev) {
+                                                                 double* __restrict__ sums, float* __restrict__ loss, HeadEvalAcc ev,
+                                                                 HeadLossFin lf) {
   __shared__ double ratio[256];
-  __shared__ double red[64][3][4];
+  __shared__ double red[64][S][4];
+  if constexpr (TV) {
+    if (threadIdx.x == 0 && lf.coef) lf.coef[2 * BC] = (float)(lf.w * lf.inv_n / BC);
+  }
   __shared__ double hred[EVAL ? 64 : 1][2][4];
   __shared__ double hs[EVAL ? 256 : 1][2];
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   if ((rows & 255) == 0 && BC <= 64) {
     const int per = rows >> 8, M = BC * per;
-    double s[3] = {0, 0, 0};
+    double s[S] = {};
     double h[2] = {0, 0};
     int left = per, pair = 0;
     for (int m0 = 0; m0 < M; m0 += 8) {
-      double v[8][3];
+      double v[8][S];
       double hv[EVAL ? 8 : 1][2];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const bool ok = m0 + u < M;
-        const double* rec = partial + ((int64_t)(ok ? m0 + u : 0) * 256 + t) * 3;
+        const double* rec = partial + ((int64_t)(ok ? m0 + u : 0) * 256 + t) * S;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) v[u][k] = rec[k];
+        for (int k = 0; k < S; ++k) v[u][k] = rec[k];
         if constexpr (EVAL) {
           const double* hrec = ev.hpartial + ((int64_t)(ok ? m0 + u : 0) * 256 + t) * 2;
           hv[u][0] = hrec[0]; hv[u][1] = hrec[1];
@@ -259,11 +301,11 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
       for (int u = 0; u < 8; ++u) {
         if (m0 + u >= M) break;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += v[u][k];
+        for (int k = 0; k < S; ++k) s[k] += v[u][k];
         if constexpr (EVAL) { h[0] += hv[u][0]; h[1] += hv[u][1]; }
         if (--left == 0) {
 #pragma unroll
-          for (int k = 0; k < 3; ++k) {
+          for (int k = 0; k < S; ++k) {
             const double w = wave_sum_d(s[k]);
             if (lane == 0) red[pair][k][wave] = w;
             s[k] = 0;
@@ -283,10 +325,10 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
     __syncthreads();
     double r = 0;
     if (t < BC) {
-      double q[3];
+      double q[S];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { q[k] = (red[t][k][0] + red[t][k][1]) + (red[t][k][2] + red[t][k][3]); sums[t * 3 + k] = q[k]; }
-      r = (2.0 * q[0] + smooth) / (q[1] + q[2] + smooth);
+      for (int k = 0; k < S; ++k) { q[k] = (red[t][k][0] + red[t][k][1]) + (red[t][k][2] + red[t][k][3]); sums[t * S + k] = q[k]; }
+      r = head_pair_term<S, TV>(q, smooth, lf, t, BC);
       if constexpr (EVAL) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) hs[t][k] = (hred[t][k][0] + hred[t][k][1]) + (hred[t][k][2] + hred[t][k][3]);
@@ -297,23 +339,24 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
     if (t == 0) {
       double a = 0;
       for (int i = 0; i < BC; ++i) a += ratio[i];
-      *loss = (float)(1.0 - a / BC);
-      if constexpr (EVAL) head_eval_add(ev, BC, hs, sums, loss);
+      *loss = TV ? (float)(a / BC) : (float)(1.0 - a / BC);
+      if constexpr (EVAL) head_eval_add<S>(ev, BC, hs, sums, loss);
     }
     return;
   }
   if constexpr (EVAL) head_eval_hard_walk(ev, rows, BC, hs);
   double acc = 0;
   for (int i = wave; i < BC; i += 4) {
-    double s[3] = {0, 0, 0};
+    double s[S] = {};
     for (int r = lane; r < rows; r += 64)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) s[k] += partial[((int64_t)i * rows + r) * 3 + k];
+      for (int k = 0; k < S; ++k) s[k] += partial[((int64_t)i * rows + r) * S + k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] = wave_sum_d(s[k]);
+    for (int k = 0; k < S; ++k) s[k] = wave_sum_d(s[k]);
     if (lane == 0) {
-      sums[i * 3] = s[0]; sums[i * 3 + 1] = s[1]; sums[i * 3 + 2] = s[2];
-      acc += (2.0 * s[0] + smooth) / (s[1] + s[2] + smooth);
+#pragma unroll
+      for (int k = 0; k < S; ++k) sums[i * S + k] = s[k];
+      acc += head_pair_term<S, TV>(s, smooth, lf, i, BC);
     }
   }
   ratio[t] = acc;
@@ -322,8 +365,8 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
     // (only lane 0 of each wave holds a value: the four adds below are the 256-entry sum without its zeros, bit for bit)
     double s = 0;
     for (int i = 0; i < 256; i += 64) s += ratio[i];
-    *loss = (float)(1.0 - s / BC);
-    if constexpr (EVAL) head_eval_add(ev, BC, hs, sums, loss);
+    *loss = TV ? (float)(s / BC) : (float)(1.0 - s / BC);
+    if constexpr (EVAL) head_eval_add<S>(ev, BC, hs, sums, loss);
   }
 }
 
@@ -335,11 +378,14 @@ struct HeadBwdArgs {
   const double* sums; const float* dloss; double smooth; int BC;
   void* dx; int64_t dxld; int accumulate;
   float* partial; float* pbias; int chunks_per_sample; int Ci, Co;
+  const float* coef;     // COEF: float[2 BC + 1] of the loss finalize (HeadLossFin)
 };
 
 // thread = voxel.  d logit = dp * p * (1 - p) with p recomputed from x (no saved activations are read);
 // dx[ci] = gate[ci] * sum_co W[co][ci] * dlogit[co];  dW[co][ci] = gate[ci] * sum_v dlogit[co] * x[ci];  dbias[co] = sum_v dlogit[co]
-template <typename TX, typename TD, int CIQ, int NCO, typename TT = float>     // NCO, TT: as head_fwd_kernel
+// COEF (n3d_head_loss_bwd): d loss / d p = k2 t + k0 with the pair's (k2, k0) as the loss finalize left them, and, when the
+// cross-entropy coefficient kb is not 0, d logit += kb (p - t); targets are given, dp and sums are not
+template <typename TX, typename TD, int CIQ, int NCO, typename TT = float, bool COEF = false>     // NCO, TT: as head_fwd_kernel
 __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
   N3D_CHAIN_PRIO();
   constexpr int CI = CIQ * 4, NV = HEAD_COMAX * CI + HEAD_COMAX;
@@ -354,12 +400,21 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
   }
   if (tid < CI) gsm[tid] = a.gate ? a.gate[b * CI + tid] : 1.f;
   __syncthreads();
-  float bias[NCO], k2[NCO], k0[NCO];
+  const bool fusedloss = COEF || a.sums;     // (uniform) the loss gradient is formed here from the targets
+  float bias[NCO], k2[NCO], k0[NCO], kb = 0.f;
+  if constexpr (COEF) kb = a.coef[2 * a.BC] * (a.dloss ? *a.dloss : 1.f);
 #pragma unroll
   for (int co = 0; co < NCO; ++co) {
     bias[co] = (ALL || co < a.Co) ? a.bias[co] : 0.f;
     k2[co] = k0[co] = 0.f;
-    if (a.sums && (ALL || co < a.Co)) {
+    if constexpr (COEF) {
+      if (ALL || co < a.Co) {
+        const int i = b * a.Co + co;
+        const float gl = a.dloss ? *a.dloss : 1.f;
+        k2[co] = a.coef[2 * i] * gl;
+        k0[co] = a.coef[2 * i + 1] * gl;
+      }
+    } else if (a.sums && (ALL || co < a.Co)) {
       // d loss / d p = -(1/BC) * (2 t den - num) / den^2   (loss.py:13-14), as n3d_dice_bwd
       const int i = b * a.Co + co;
       const double num = 2.0 * a.sums[i * 3] + a.smooth, den = a.sums[i * 3 + 1] + a.sums[i * 3 + 2] + a.smooth;
@@ -385,7 +440,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
   constexpr int NK = HEAD_CHUNK / 256;
   constexpr bool TU8 = sizeof(TT) == 1;
   __shared__ uint32_t tql[TU8 ? NCO : 1][256];
-  const bool tquad = TU8 && a.t_quad && a.sums;     // (uniform)
+  const bool tquad = TU8 && a.t_quad && fusedloss;     // (uniform)
   float4 xqs[NK][CIQ];
   float gin[NK][NCO];
   uint32_t tq[NCO];
@@ -401,7 +456,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
       for (int co = 0; co < NCO; ++co) {
         gin[k][co] = 0.f;
         if (ALL || co < a.Co)
-          gin[k][co] = a.sums ? (float)reinterpret_cast<const TT*>(a.t)[b * a.tsb + co * a.tsc + vc * a.tsv] : a.dp[b * a.dsb + co * a.dsc + vc * a.dsv];
+          gin[k][co] = fusedloss ? (float)reinterpret_cast<const TT*>(a.t)[b * a.tsb + co * a.tsc + vc * a.tsv] : a.dp[b * a.dsb + co * a.dsc + vc * a.dsv];
       }
     }
   }
@@ -415,7 +470,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
 #pragma unroll
     for (int co = 0; co < NCO; ++co) {
       gp[co] = 0.f;
-      if (ALL || co < a.Co) gp[co] = a.sums ? fmaf(k2[co], gin[k][co], k0[co]) : gin[k][co];
+      if (ALL || co < a.Co) gp[co] = fusedloss ? fmaf(k2[co], gin[k][co], k0[co]) : gin[k][co];
     }
     float4 prevq[CIQ];
     if (a.accumulate) {
@@ -433,6 +488,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
       }
       const float pr = 1.0f / (1.0f + expf(-s));
       dl[co] = gp[co] * pr * (1.0f - pr);
+      if constexpr (COEF) {
+        if (kb != 0.f && (ALL || co < a.Co)) dl[co] = fmaf(kb, pr - gin[k][co], dl[co]);
+      }
       accb[co] += dl[co];
     }
 #pragma unroll
@@ -486,15 +544,16 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
 }
 
 // (byte targets: the three-channel form only -- the reference's out_channels, the generator's three boolean maps)
-template <typename TX, bool EVAL = false>
+// (the cross-entropy form, BCE: the three-channel head only)
+template <typename TX, bool EVAL = false, bool BCE = false>
 static bool launch_head_fwd(const HeadFwdArgs& a, int B, bool t_u8, hipStream_t s) {
   const dim3 grid((unsigned)a.rows, (unsigned)B), blk(256);
   const bool three = a.Co == 3;
-  if (t_u8 && !three) return false;
+  if ((t_u8 || BCE) && !three) return false;
 #define N3D_HEAD_FWD(Q_)                                                                                                     \
-  case Q_: if (t_u8) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, uint8_t, EVAL>), grid, blk, 0, s, a);                     \
-           else if (three) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, float, EVAL>), grid, blk, 0, s, a);                 \
-           else N3D_LAUNCH((head_fwd_kernel<TX, Q_, HEAD_COMAX, float, EVAL>), grid, blk, 0, s, a);                   \
+  case Q_: if (t_u8) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, uint8_t, EVAL, BCE>), grid, blk, 0, s, a);                \
+           else if (three) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, float, EVAL, BCE>), grid, blk, 0, s, a);            \
+           else if constexpr (!BCE) N3D_LAUNCH((head_fwd_kernel<TX, Q_, HEAD_COMAX, float, EVAL>), grid, blk, 0, s, a); \
            break;
   switch (a.Ci / 4) {
     N3D_HEAD_FWD(1) N3D_HEAD_FWD(2) N3D_HEAD_FWD(3) N3D_HEAD_FWD(4) N3D_HEAD_FWD(6) N3D_HEAD_FWD(8)
@@ -504,15 +563,15 @@ static bool launch_head_fwd(const HeadFwdArgs& a, int B, bool t_u8, hipStream_t 
   return true;
 }
 
-template <typename TX, typename TD>
+template <typename TX, typename TD, bool COEF = false>
 static bool launch_head_bwd(const HeadBwdArgs& a, int B, bool t_u8, hipStream_t s) {
   const dim3 grid((unsigned)a.chunks_per_sample, (unsigned)B), blk(256);
   const bool three = a.Co == 3;
   if (t_u8 && !three) return false;
 #define N3D_HEAD_BWD(Q_)                                                                                                     \
-  case Q_: if (t_u8) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3, uint8_t>), grid, blk, 0, s, a);                       \
-           else if (three) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3>), grid, blk, 0, s, a);                          \
-           else N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, HEAD_COMAX>), grid, blk, 0, s, a);                            \
+  case Q_: if (t_u8) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3, uint8_t, COEF>), grid, blk, 0, s, a);                 \
+           else if (three) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3, float, COEF>), grid, blk, 0, s, a);             \
+           else N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, HEAD_COMAX, float, COEF>), grid, blk, 0, s, a);               \
            break;
   switch (a.Ci / 4) {
     N3D_HEAD_BWD(1) N3D_HEAD_BWD(2) N3D_HEAD_BWD(3) N3D_HEAD_BWD(4) N3D_HEAD_BWD(6) N3D_HEAD_BWD(8)
@@ -539,6 +598,68 @@ static int check_head(const n3d_head* h, const char* what) {
   }
   N3D_CHECK_ARG(h->xld >= h->Ci && h->xld % 4 == 0 && (reinterpret_cast<uintptr_t>(h->x) % (4 * esz)) == 0, "%s: x needs ld %% 4 == 0 and quad alignment", what);
   return 0;
+}
+
+// arguments of the forward pass (partial == nullptr: no sums; hpartial / thr: the evaluation form)
+static HeadFwdArgs head_fwd_args(const n3d_head* h, const float* gate, float* p, int64_t psb, int64_t psc, int64_t psv, float* logits, const void* t,
+                                 int64_t tsb, int64_t tsc, int64_t tsv, double* partial, double* hpartial, float thr) {
+  HeadFwdArgs a;
+  a.x = h->x; a.xld = h->xld; a.N = h->N; a.w = h->w; a.bias = h->bias; a.gate = gate;
+  a.qn = h->node_c / 4; a.xns = h->x_node_stride;
+  a.p = p; a.psb = psb; a.psc = psc; a.psv = psv; a.logits = logits;
+  a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv; a.partial = partial; a.rows = (int)cdiv(h->N, HEAD_CHUNK);
+  a.Ci = h->Ci; a.Co = h->Co; a.hpartial = hpartial; a.thr = thr;
+  const bool u8 = t && h->t_dtype == N3D_U8;
+  a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
+  return a;
+}
+
+static HeadLossFin head_loss_fin(const n3d_loss* l, int64_t N, float* coef) {
+  return HeadLossFin{tversky_spec(l), (double)l->bce_weight, 1.0 / (double)N, coef};
+}
+
+// what n3d_head_bwd (dp, or t and sums) and n3d_head_loss_bwd (t and coef) share: the one backward launch and the weight-gradient job
+static int head_bwd_run(const n3d_head* h, const char* what, const float* dp, int64_t dsb, int64_t dsc, int64_t dsv, const void* t, int64_t tsb,
+                        int64_t tsc, int64_t tsv, float smooth, const double* sums, const float* coef, const float* dloss, void* dx,
+                        int64_t dxld, int dx_dtype, int flags, float* dw, float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred,
+                        void* stream) {
+  N3D_CHECK_ARG(dx && dxld >= (h->node_c ? h->node_c : h->Ci) && dxld % 4 == 0 && (!h->node_c || h->dx_node_stride % 4 == 0), "%s: bad dx", what);
+  N3D_CHECK_ARG(dx_dtype == N3D_F32 || dx_dtype == N3D_BF16, "%s: unknown dx dtype", what);
+  const bool want_w = dw || dbias;
+  const int cps = (int)cdiv(h->N, HEAD_CHUNK);
+  const size_t need = n3d_head_workspace_bytes(h);
+  if (want_w && (!ws || ws_bytes < need)) { set_error("%s: workspace too small (%zu < %zu)", what, ws_bytes, need); return N3D_ERR_WORKSPACE; }
+  HeadBwdArgs a;
+  a.x = h->x; a.xld = h->xld; a.N = h->N; a.w = h->w; a.bias = h->bias; a.gate = h->gate;
+  a.qn = h->node_c / 4; a.xns = h->x_node_stride; a.dxns = h->dx_node_stride;
+  a.dp = dp; a.dsb = dsb; a.dsc = dsc; a.dsv = dsv; a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv;
+  a.sums = dp ? nullptr : sums; a.dloss = dloss; a.smooth = (double)smooth; a.BC = h->B * h->Co;
+  a.dx = dx; a.dxld = dxld; a.accumulate = (flags & N3D_ACCUMULATE) ? 1 : 0;
+  const int nchunks = h->B * cps;
+  a.partial = want_w ? (float*)ws : nullptr;
+  a.pbias = want_w ? (float*)ws + (size_t)nchunks * h->Ci * h->Co : nullptr;
+  a.chunks_per_sample = cps; a.Ci = h->Ci; a.Co = h->Co; a.coef = coef;
+  hipStream_t s = (hipStream_t)stream;
+  bool ok;
+  const bool u8 = !dp && h->t_dtype == N3D_U8;
+  a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
+  const bool xb = h->x_dtype == N3D_BF16, db = dx_dtype == N3D_BF16;
+  if (coef) {
+    if (xb) ok = db ? launch_head_bwd<bf16_t, bf16_t, true>(a, h->B, u8, s) : launch_head_bwd<bf16_t, float, true>(a, h->B, u8, s);
+    else ok = db ? launch_head_bwd<float, bf16_t, true>(a, h->B, u8, s) : launch_head_bwd<float, float, true>(a, h->B, u8, s);
+  } else if (xb) ok = db ? launch_head_bwd<bf16_t, bf16_t>(a, h->B, u8, s) : launch_head_bwd<bf16_t, float>(a, h->B, u8, s);
+  else ok = db ? launch_head_bwd<float, bf16_t>(a, h->B, u8, s) : launch_head_bwd<float, float>(a, h->B, u8, s);
+  if (!ok) N3D_UNSUPPORTED("%s: Ci=%d", what, h->Ci);
+  N3D_LAUNCH_CHECK();
+  if (want_w) {
+    // one "tile" holding the whole [Ci][Co] slab per chunk (layout of n3d_final_job: position = ci * co_t + co)
+    n3d_final_job job;
+    job.partial = a.partial; job.pbias = a.pbias; job.dw = dw; job.dbias = dbias; job.nchunks = nchunks; job.ntiles = 1; job.tci = 1; job.tco = 1;
+    job.ci_t = h->Ci; job.co_t = h->Co; job.Co = h->Co; job.Ci = h->Ci; job.taps = 1; job.pad_ = 0;
+    if (deferred) *deferred = job;
+    else if (int e = n3d_wgrad_finalize_batch(&job, 1, stream)) return e;
+  }
+  return N3D_OK;
 }
 
 }  // namespace n3d
@@ -568,19 +689,13 @@ int n3d_head_fwd(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t 
   if (int e = check_head(h, "head_fwd")) return e;
   N3D_CHECK_ARG(p || t, "head_fwd: no output (p may be NULL only in the Dice mode: the trainers' step needs the loss alone)");
   N3D_CHECK_ARG(!t || (partial && sums && loss), "head_fwd: the Dice mode needs partial / sums / loss");
-  HeadFwdArgs a;
-  a.x = h->x; a.xld = h->xld; a.N = h->N; a.w = h->w; a.bias = h->bias; a.gate = h->gate;
-  a.qn = h->node_c / 4; a.xns = h->x_node_stride;
-  a.p = p; a.psb = psb; a.psc = psc; a.psv = psv; a.logits = logits;
-  a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv; a.partial = t ? partial : nullptr; a.rows = (int)cdiv(h->N, HEAD_CHUNK);
-  a.Ci = h->Ci; a.Co = h->Co; a.hpartial = nullptr; a.thr = 0.f;
+  HeadFwdArgs a = head_fwd_args(h, h->gate, p, psb, psc, psv, logits, t, tsb, tsc, tsv, t ? partial : nullptr, nullptr, 0.f);
   hipStream_t s = (hipStream_t)stream;
   const bool u8 = t && h->t_dtype == N3D_U8;
-  a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
   const bool ok = h->x_dtype == N3D_BF16 ? launch_head_fwd<bf16_t>(a, h->B, u8, s) : launch_head_fwd<float>(a, h->B, u8, s);
   if (!ok) N3D_UNSUPPORTED("head_fwd: Ci=%d", h->Ci);
   if (t) N3D_LAUNCH(head_dice_finalize_kernel<>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
-                           HeadEvalAcc{});
+                           HeadEvalAcc{}, HeadLossFin{});
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -591,19 +706,66 @@ int n3d_head_eval(const n3d_head* h, float* p, int64_t psb, int64_t psc, int64_t
   N3D_CHECK_ARG(!h->gate, "head_eval: the evaluation head has no Dropout3d gate (eval mode)");
   N3D_CHECK_ARG(t && partial && hpartial && sums && loss && acc, "head_eval: needs t, partial, hpartial, sums, loss and acc");
   N3D_CHECK_ARG(h->B * h->Co <= 256, "head_eval: B * Co <= 256 (B=%d Co=%d)", h->B, h->Co);
-  HeadFwdArgs a;
-  a.x = h->x; a.xld = h->xld; a.N = h->N; a.w = h->w; a.bias = h->bias; a.gate = nullptr;
-  a.qn = h->node_c / 4; a.xns = h->x_node_stride;
-  a.p = p; a.psb = psb; a.psc = psc; a.psv = psv; a.logits = nullptr;
-  a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv; a.partial = partial; a.rows = (int)cdiv(h->N, HEAD_CHUNK);
-  a.Ci = h->Ci; a.Co = h->Co; a.hpartial = hpartial; a.thr = thr;
+  HeadFwdArgs a = head_fwd_args(h, nullptr, p, psb, psc, psv, nullptr, t, tsb, tsc, tsv, partial, hpartial, thr);
   hipStream_t s = (hipStream_t)stream;
   const bool u8 = h->t_dtype == N3D_U8;
-  a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
   const bool ok = h->x_dtype == N3D_BF16 ? launch_head_fwd<bf16_t, true>(a, h->B, u8, s) : launch_head_fwd<float, true>(a, h->B, u8, s);
   if (!ok) N3D_UNSUPPORTED("head_eval: Ci=%d", h->Ci);
   N3D_LAUNCH(head_dice_finalize_kernel<true>, dim3(1), dim3(256), 0, s, partial, a.rows, h->B * h->Co, (double)smooth, sums, loss,
-                     HeadEvalAcc{hpartial, h->Co, acc});
+                     HeadEvalAcc{hpartial, h->Co, acc}, HeadLossFin{});
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_head_loss_fwd(const n3d_head* h, const n3d_loss* l, float* p, int64_t psb, int64_t psc, int64_t psv, float* logits, const void* t,
+                      int64_t tsb, int64_t tsc, int64_t tsv, double* partial, double* sums, float* coef, float* loss, void* stream) {
+  if (int e = check_head(h, "head_loss_fwd")) return e;
+  if (int e = check_loss(l, "head_loss_fwd")) return e;
+  N3D_CHECK_ARG(t && partial && sums && coef && loss, "head_loss_fwd: needs t, partial, sums, coef and loss");
+  const bool bce = l->bce_weight > 0.f;
+  if (bce && h->Co != 3) N3D_UNSUPPORTED("head_loss_fwd: the cross-entropy term is built for Co = 3 (Co=%d bce_weight=%g)", h->Co, l->bce_weight);
+  HeadFwdArgs a = head_fwd_args(h, h->gate, p, psb, psc, psv, logits, t, tsb, tsc, tsv, partial, nullptr, 0.f);
+  hipStream_t s = (hipStream_t)stream;
+  const bool u8 = h->t_dtype == N3D_U8, xb = h->x_dtype == N3D_BF16;
+  const HeadLossFin lf = head_loss_fin(l, h->N, coef);
+  const int BC = h->B * h->Co;
+  if (bce) {
+    if (!(xb ? launch_head_fwd<bf16_t, false, true>(a, h->B, u8, s) : launch_head_fwd<float, false, true>(a, h->B, u8, s)))
+      N3D_UNSUPPORTED("head_loss_fwd: Ci=%d", h->Ci);
+    N3D_LAUNCH((head_dice_finalize_kernel<false, 4, true>), dim3(1), dim3(256), 0, s, partial, a.rows, BC, lf.tv.smooth, sums, loss, HeadEvalAcc{}, lf);
+  } else {
+    if (!(xb ? launch_head_fwd<bf16_t>(a, h->B, u8, s) : launch_head_fwd<float>(a, h->B, u8, s))) N3D_UNSUPPORTED("head_loss_fwd: Ci=%d", h->Ci);
+    N3D_LAUNCH((head_dice_finalize_kernel<false, 3, true>), dim3(1), dim3(256), 0, s, partial, a.rows, BC, lf.tv.smooth, sums, loss, HeadEvalAcc{}, lf);
+  }
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_head_loss_eval(const n3d_head* h, const n3d_loss* l, float* p, int64_t psb, int64_t psc, int64_t psv, const void* t, int64_t tsb,
+                       int64_t tsc, int64_t tsv, float thr, double* partial, double* hpartial, double* sums, float* loss, double* acc,
+                       void* stream) {
+  if (int e = check_head(h, "head_loss_eval")) return e;
+  if (int e = check_loss(l, "head_loss_eval")) return e;
+  N3D_CHECK_ARG(!h->gate, "head_loss_eval: the evaluation head has no Dropout3d gate (eval mode)");
+  N3D_CHECK_ARG(t && partial && hpartial && sums && loss && acc, "head_loss_eval: needs t, partial, hpartial, sums, loss and acc");
+  N3D_CHECK_ARG(h->B * h->Co <= 256, "head_loss_eval: B * Co <= 256 (B=%d Co=%d)", h->B, h->Co);
+  const bool bce = l->bce_weight > 0.f;
+  if (bce && h->Co != 3) N3D_UNSUPPORTED("head_loss_eval: the cross-entropy term is built for Co = 3 (Co=%d bce_weight=%g)", h->Co, l->bce_weight);
+  HeadFwdArgs a = head_fwd_args(h, nullptr, p, psb, psc, psv, nullptr, t, tsb, tsc, tsv, partial, hpartial, thr);
+  hipStream_t s = (hipStream_t)stream;
+  const bool u8 = h->t_dtype == N3D_U8, xb = h->x_dtype == N3D_BF16;
+  const HeadLossFin lf = head_loss_fin(l, h->N, nullptr);
+  const HeadEvalAcc ev{hpartial, h->Co, acc};
+  const int BC = h->B * h->Co;
+  if (bce) {
+    if (!(xb ? launch_head_fwd<bf16_t, true, true>(a, h->B, u8, s) : launch_head_fwd<float, true, true>(a, h->B, u8, s)))
+      N3D_UNSUPPORTED("head_loss_eval: Ci=%d", h->Ci);
+    N3D_LAUNCH((head_dice_finalize_kernel<true, 4, true>), dim3(1), dim3(256), 0, s, partial, a.rows, BC, lf.tv.smooth, sums, loss, ev, lf);
+  } else {
+    if (!(xb ? launch_head_fwd<bf16_t, true>(a, h->B, u8, s) : launch_head_fwd<float, true>(a, h->B, u8, s)))
+      N3D_UNSUPPORTED("head_loss_eval: Ci=%d", h->Ci);
+    N3D_LAUNCH((head_dice_finalize_kernel<true, 3, true>), dim3(1), dim3(256), 0, s, partial, a.rows, BC, lf.tv.smooth, sums, loss, ev, lf);
+  }
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }
@@ -613,40 +775,19 @@ int n3d_head_bwd(const n3d_head* h, const float* dp, int64_t dsb, int64_t dsc, i
                  float* dw, float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred, void* stream) {
   if (deferred) deferred->nchunks = 0;
   if (int e = check_head(h, "head_bwd")) return e;
-  N3D_CHECK_ARG(dx && dxld >= (h->node_c ? h->node_c : h->Ci) && dxld % 4 == 0 && (!h->node_c || h->dx_node_stride % 4 == 0), "head_bwd: bad dx");
   N3D_CHECK_ARG((dp != nullptr) != (t != nullptr && sums != nullptr), "head_bwd: give either dp or (t, sums)");
-  N3D_CHECK_ARG(dx_dtype == N3D_F32 || dx_dtype == N3D_BF16, "head_bwd: unknown dx dtype");
-  const bool want_w = dw || dbias;
-  const int cps = (int)cdiv(h->N, HEAD_CHUNK);
-  const size_t need = n3d_head_workspace_bytes(h);
-  if (want_w && (!ws || ws_bytes < need)) { set_error("head_bwd: workspace too small (%zu < %zu)", ws_bytes, need); return N3D_ERR_WORKSPACE; }
-  HeadBwdArgs a;
-  a.x = h->x; a.xld = h->xld; a.N = h->N; a.w = h->w; a.bias = h->bias; a.gate = h->gate;
-  a.qn = h->node_c / 4; a.xns = h->x_node_stride; a.dxns = h->dx_node_stride;
-  a.dp = dp; a.dsb = dsb; a.dsc = dsc; a.dsv = dsv; a.t = t; a.tsb = tsb; a.tsc = tsc; a.tsv = tsv;
-  a.sums = dp ? nullptr : sums; a.dloss = dloss; a.smooth = (double)smooth; a.BC = h->B * h->Co;
-  a.dx = dx; a.dxld = dxld; a.accumulate = (flags & N3D_ACCUMULATE) ? 1 : 0;
-  const int nchunks = h->B * cps;
-  a.partial = want_w ? (float*)ws : nullptr;
-  a.pbias = want_w ? (float*)ws + (size_t)nchunks * h->Ci * h->Co : nullptr;
-  a.chunks_per_sample = cps; a.Ci = h->Ci; a.Co = h->Co;
-  hipStream_t s = (hipStream_t)stream;
-  bool ok;
-  const bool u8 = !dp && h->t_dtype == N3D_U8;
-  a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
-  if (h->x_dtype == N3D_BF16) ok = dx_dtype == N3D_BF16 ? launch_head_bwd<bf16_t, bf16_t>(a, h->B, u8, s) : launch_head_bwd<bf16_t, float>(a, h->B, u8, s);
-  else ok = dx_dtype == N3D_BF16 ? launch_head_bwd<float, bf16_t>(a, h->B, u8, s) : launch_head_bwd<float, float>(a, h->B, u8, s);
-  if (!ok) N3D_UNSUPPORTED("head_bwd: Ci=%d", h->Ci);
-  N3D_LAUNCH_CHECK();
-  if (want_w) {
-    // one "tile" holding the whole [Ci][Co] slab per chunk (layout of n3d_final_job: position = ci * co_t + co)
-    n3d_final_job job;
-    job.partial = a.partial; job.pbias = a.pbias; job.dw = dw; job.dbias = dbias; job.nchunks = nchunks; job.ntiles = 1; job.tci = 1; job.tco = 1;
-    job.ci_t = h->Ci; job.co_t = h->Co; job.Co = h->Co; job.Ci = h->Ci; job.taps = 1; job.pad_ = 0;
-    if (deferred) *deferred = job;
-    else if (int e = n3d_wgrad_finalize_batch(&job, 1, stream)) return e;
-  }
-  return N3D_OK;
+  return head_bwd_run(h, "head_bwd", dp, dsb, dsc, dsv, t, tsb, tsc, tsv, smooth, sums, nullptr, dloss, dx, dxld, dx_dtype, flags, dw, dbias, ws,
+                      ws_bytes, deferred, stream);
+}
+
+int n3d_head_loss_bwd(const n3d_head* h, const void* t, int64_t tsb, int64_t tsc, int64_t tsv, const float* coef, const float* dloss, void* dx,
+                      int64_t dxld, int dx_dtype, int flags, float* dw, float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred,
+                      void* stream) {
+  if (deferred) deferred->nchunks = 0;
+  if (int e = check_head(h, "head_loss_bwd")) return e;
+  N3D_CHECK_ARG(t && coef, "head_loss_bwd: needs the targets and the coefficients of n3d_head_loss_fwd");
+  return head_bwd_run(h, "head_loss_bwd", nullptr, 0, 0, 0, t, tsb, tsc, tsv, 0.f, nullptr, coef, dloss, dx, dxld, dx_dtype, flags, dw, dbias, ws,
+                      ws_bytes, deferred, stream);
 }
 
 }  // extern "C"

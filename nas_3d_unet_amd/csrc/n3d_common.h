@@ -385,6 +385,32 @@ __device__ __forceinline__ float wave_sum_strided_f(float v, int cpb) {
 }
 __device__ __forceinline__ float wave_sum_f(float v) { return wave_classsum_f(v, 1); }
 __device__ __forceinline__ double wave_sum_d(double v) { return wave_classsum_d(v, 1); }
+
+// Tversky / focal term of a (b, c) pair from its sums A = sum p*t, P = sum p, T = sum t (include/n3d.h, n3d_loss):
+//   TI = (A + s) / (A + alpha (P - A) + beta (T - A) + s),  u = max(1 - TI, 0),  term = u^gamma
+// and the coefficients of its gradient d mean_bc(term) / d p = k2 * t + k0, written to k[0..1] when k is given.  u == 0: the pair
+// contributes 0 and a zero gradient for every gamma (pow's derivative is infinite there for gamma < 1).
+struct TverskySpec { double alpha, beta, gamma, smooth; };
+inline int check_loss(const n3d_loss* l, const char* what) {
+  N3D_CHECK_ARG(l && l->alpha >= 0.f && l->beta >= 0.f && l->alpha + l->beta > 0.f && l->gamma > 0.f && l->bce_weight >= 0.f && l->smooth > 0.f,
+                "%s: a loss needs alpha, beta >= 0, alpha + beta > 0, gamma > 0, bce_weight >= 0 and smooth > 0", what);
+  return 0;
+}
+inline TverskySpec tversky_spec(const n3d_loss* l) { return TverskySpec{(double)l->alpha, (double)l->beta, (double)l->gamma, (double)l->smooth}; }
+__device__ __forceinline__ double tversky_term(double A, double P, double T, const TverskySpec& l, int BC, float* k) {
+  const double num = A + l.smooth, den = A + l.alpha * (P - A) + l.beta * (T - A) + l.smooth;
+  const double u = 1.0 - num / den;
+  double term = 0, f = 0;
+  if (u > 0) {
+    term = l.gamma == 1.0 ? u : pow(u, l.gamma);
+    f = (l.gamma == 1.0 ? 1.0 : l.gamma * pow(u, l.gamma - 1.0)) / BC;
+  }
+  if (k) {
+    k[0] = (float)(-f * (den - num * (1.0 - l.alpha - l.beta)) / (den * den));
+    k[1] = (float)(f * num * l.alpha / (den * den));
+  }
+  return term;
+}
 #endif
 
 }  // namespace n3d

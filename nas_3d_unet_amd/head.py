@@ -4,6 +4,7 @@ dropout_rate=p, ops_order='weight'), nn.Sigmoid())`, and loss.py:12-14 behind it
 `run(head, x)` = Dropout3d -> 1x1x1 conv -> sigmoid in ONE kernel (n3d_head_fwd) with a one-pass backward (n3d_head_bwd);
 `run_loss(head, x, t, smooth)` additionally forms the Dice sums in the forward pass and the Dice gradient inside the
 backward pass, so the trainers' step has no separate sigmoid / Dice passes over (B, n_out, D, H, W).
+`run_loss(..., loss=TverskyBCELoss(...))` forms the Tversky / focal / cross-entropy loss in the same two passes (n3d_head_loss_fwd / _bwd).
 `run_eval(head, x, t, acc)` is the evaluation form (n3d_head_eval, no autograd): eval-mode head, Dice loss and the region counts of
 the thresholded prediction in one pass, added into a device accumulator that `eval_figures` turns into an `EvalResult`.
 The modules (and their state-dict names `last_conv.0.conv.*`) stay the reference's; only what runs underneath differs.
@@ -103,6 +104,59 @@ class HeadDiceFn(torch.autograd.Function):
         return None, None, dx.t, None, None if inplace else dw, None if inplace else db
 
 
+class HeadLossFn(torch.autograd.Function):
+    """HeadDiceFn for a loss.TverskyBCELoss `spec` (n3d_head_loss_fwd / n3d_head_loss_bwd): the same `skip_p` contract"""
+
+    @staticmethod
+    def forward(ctx, gate, spec, x, t, w, b):
+        global last_logits
+        xv = _feat_view(x)
+        if K._bcv_strides(t) is None:
+            t = t.contiguous()
+        want_p = KEEP_LOGITS or not getattr(ctx, "skip_p", False)
+        p, logits, _, coef, loss = K.head_loss_fwd(xv, w, b, gate, t, spec, want_logits=KEEP_LOGITS, want_p=want_p)
+        if KEEP_LOGITS:
+            last_logits = logits
+        ctx.xv, ctx.gate, ctx.w, ctx.b, ctx.t, ctx.coef = xv, gate, w, b, t, coef
+        if p is not None:
+            ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, dloss, _dp):
+        xv, w, b = ctx.xv, ctx.w, ctx.b
+        dx = _feat_like(xv)
+        dw, db = K.grad_target(w), K.grad_target(b)
+        K.head_loss_bwd(xv, w, b, ctx.gate, dx, dw, db, ctx.t, ctx.coef, dloss=dloss.contiguous())
+        inplace = getattr(w, "_n3d_grad", None) is not None
+        ctx.xv = ctx.t = None
+        return None, None, dx.t, None, None if inplace else dw, None if inplace else db
+
+
+def _dice_like(loss):
+    """is `loss` (None, a loss.WeightedDiceLoss or a loss.TverskyBCELoss) the Dice loss of the existing entry points?"""
+    from .loss import TverskyBCELoss, WeightedDiceLoss
+    if loss is None or isinstance(loss, WeightedDiceLoss):
+        return True
+    if not isinstance(loss, TverskyBCELoss):
+        raise K.N3DError("head: loss must be a WeightedDiceLoss or a TverskyBCELoss (got %s)" % type(loss).__name__)
+    return False
+
+
+def check_loss_head(head, loss):
+    """raise unless the head can form `loss`: a cross-entropy term (bce_weight > 0) is built inside the fused three-channel head only"""
+    if _dice_like(loss) or not loss.bce_weight > 0:
+        return
+    op = head[0]
+    ci, co = op.conv.weight.shape[1], op.conv.weight.shape[0]
+    if not fusable(head, torch.empty((1, ci, 1, 1, 1), device="meta")):
+        raise K.N3DError("TverskyBCELoss(bce_weight=%g): the cross-entropy term is formed from logits inside the fused head, and this "
+                         "head is not one it takes (1x1x1 conv of 4..32 channels to <= 4, sigmoid; %d -> %d here)" % (loss.bce_weight, ci, co))
+    if co != 3:
+        raise K.N3DError("TverskyBCELoss(bce_weight=%g): the cross-entropy kernels are built for a three-channel head (out_channels=%d)"
+                         % (loss.bce_weight, co))
+
+
 def run(head, x):
     """probabilities of the head on features x"""
     if not fusable(head, x):
@@ -111,17 +165,26 @@ def run(head, x):
     return HeadFn.apply(_gate(op, x), x, op.conv.weight, op.conv.bias)
 
 
-def run_loss(head, x, t, smooth=1e-6):
-    """(Dice loss, probabilities) of the head on features x against the target t.  The probabilities are returned for
-    inspection only and carry NO gradient on either path (the fused kernels form the Dice gradient inside the head's backward
+def run_loss(head, x, t, smooth=1e-6, loss=None):
+    """(loss, probabilities) of the head on features x against the target t.  loss: None or a WeightedDiceLoss -- the Dice loss with
+    `smooth` -- or a TverskyBCELoss, which carries its own smooth.  The probabilities are returned for
+    inspection only and carry NO gradient on either path (the fused kernels form the loss gradient inside the head's backward
     pass): a caller who wants another loss on them uses run() and differentiates through that."""
     fused = fusable(head, x)
     byte_ok = fused and t.dtype == torch.uint8 and head[0].conv.weight.shape[0] == 3      # {0, 1} bytes: the three-channel head kernels read them as they are
+    dice = _dice_like(loss)
+    if not dice:
+        check_loss_head(head, loss)
     if not fused or not (t.dtype == torch.float32 or byte_ok):
         from .loss import WeightedDiceLoss
+        if not dice and loss.bce_weight > 0:
+            raise K.N3DError("TverskyBCELoss(bce_weight=%g): targets are float32, or uint8 {0, 1} bytes (got %s)" % (loss.bce_weight, t.dtype))
         p = head(x)
-        return WeightedDiceLoss(smooth=smooth)(p, t if t.dtype == torch.float32 else t.to(torch.float32)), p.detach()
+        fn = WeightedDiceLoss(smooth=smooth) if dice else loss
+        return fn(p, t if t.dtype == torch.float32 else t.to(torch.float32)), p.detach()
     op = head[0]
+    if not dice:
+        return HeadLossFn.apply(_gate(op, x), loss, x, t, op.conv.weight, op.conv.bias)
     return HeadDiceFn.apply(_gate(op, x), float(smooth), x, t, op.conv.weight, op.conv.bias)
 
 
@@ -152,10 +215,10 @@ def eval_figures(acc):
     return EvalResult(float(a[0] / nb), dsum / ns, glob, int(round(nb)), int(round(ns)))
 
 
-def run_eval(head, x, t, acc, smooth=1e-6, thr=0.5):
-    """eval-mode head on features x (no Dropout3d, no autograd): the Dice loss against t -- bit for bit run_loss's in eval mode --
-    with the region counts of p >= thr, both added into acc (kernels.eval_acc).  Returns the batch loss (0-d device tensor).
-    Only the fused head kernel takes this path: another head shape is an error."""
+def run_eval(head, x, t, acc, smooth=1e-6, thr=0.5, loss=None):
+    """eval-mode head on features x (no Dropout3d, no autograd): the loss against t -- bit for bit run_loss's in eval mode, Dice or
+    the TverskyBCELoss `loss` -- with the region counts of p >= thr, both added into acc (kernels.eval_acc).  Returns the batch loss
+    (0-d device tensor).  Only the fused head kernel takes this path: another head shape is an error."""
     op = head[0]
     if not fusable(head, x):
         raise K.N3DError("evaluate: the head is not one the fused evaluation kernel takes (1x1x1 conv of 4..32 channels to <= 4, sigmoid)")
@@ -163,4 +226,7 @@ def run_eval(head, x, t, acc, smooth=1e-6, thr=0.5):
         raise K.N3DError("evaluate: targets are float32, or uint8 {0, 1} bytes for a three-channel head (got %s)" % t.dtype)
     if K._bcv_strides(t) is None:
         t = t.contiguous()
+    if not _dice_like(loss):
+        check_loss_head(head, loss)
+        return K.head_loss_eval(_feat_view(x), op.conv.weight, op.conv.bias, t, acc, loss, thr)[0]
     return K.head_eval(_feat_view(x), op.conv.weight, op.conv.bias, t, acc, smooth, thr)[0]

@@ -1828,6 +1828,105 @@ def head_bwd(x, w, bias, gate, dx, dw, dbias, dp=None, t=None, sums=None, dloss=
         _ctx.keep.append(ws)
 
 
+def loss_record(spec):
+    """n3d_loss of a loss.TverskyBCELoss (anything with alpha, beta, gamma, bce_weight and smooth)"""
+    return _lib.Loss(float(spec.alpha), float(spec.beta), float(spec.gamma), float(spec.bce_weight), float(spec.smooth))
+
+
+def _loss_sums(spec):
+    """doubles per record of the partial rows and the sums: 4 with the cross-entropy term (its sum is the fourth), else 3"""
+    return 4 if spec.bce_weight > 0 else 3
+
+
+def head_loss_fwd(x, w, bias, gate, t, spec, want_logits=False, want_p=True):
+    """head_fwd with the Tversky / focal / cross-entropy loss `spec` (n3d_head_loss_fwd).
+    Returns (p | None, logits | None, sums (B, Co, S), coef (2 B Co + 1 floats for head_loss_bwd), loss)."""
+    lib = _lib.load()
+    h = _head_desc(x, w, bias, gate, t=t)
+    dev = x.t.device
+    Co, S = int(w.shape[0]), _loss_sums(spec)
+    if want_logits and not want_p:
+        raise N3DError("head_loss_fwd: the logits are stored next to the probabilities")
+    p = torch.empty((x.B, Co, x.D, x.H, x.W), dtype=torch.float32, device=dev) if want_p else None
+    logits = torch.empty_like(p) if want_logits else None
+    ts = _bcv_strides(t)
+    partial = torch.empty((x.B, Co, int(lib.n3d_head_rows(x.N)), S), dtype=torch.float64, device=dev)
+    sums = torch.empty((x.B, Co, S), dtype=torch.float64, device=dev)
+    coef = torch.empty(2 * x.B * Co + 1, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    l = loss_record(spec)
+    check(lib.n3d_head_loss_fwd(C.byref(h), C.byref(l), ptr(p), Co * x.N, x.N, 1, ptr(logits), ptr(t), ts[0], ts[1], ts[2], ptr(partial),
+                                ptr(sums), ptr(coef), ptr(loss), stream_ptr()), "n3d_head_loss_fwd")
+    return p, logits, sums, coef, loss
+
+
+def head_loss_eval(x, w, bias, t, acc, spec, thr=0.5, want_p=False):
+    """head_eval with the loss `spec` (n3d_head_loss_eval): acc[0] accumulates the configured loss, the region counts are head_eval's.
+    Returns (loss 0-d device tensor, p | None)."""
+    lib = _lib.load()
+    h = _head_desc(x, w, bias, None, t=t)
+    dev = x.t.device
+    Co, S = int(w.shape[0]), _loss_sums(spec)
+    if acc.dtype != torch.float64 or acc.numel() != eval_acc_len(Co) or not acc.is_contiguous():
+        raise N3DError("head_loss_eval: the accumulator must be a contiguous float64 tensor of %d elements" % eval_acc_len(Co))
+    p = torch.empty((x.B, Co, x.D, x.H, x.W), dtype=torch.float32, device=dev) if want_p else None
+    ts = _bcv_strides(t)
+    rows = int(lib.n3d_head_rows(x.N))
+    partial = torch.empty((x.B, Co, rows, S), dtype=torch.float64, device=dev)
+    hpartial = torch.empty((x.B, Co, rows, 2), dtype=torch.float64, device=dev)
+    sums = torch.empty((x.B, Co, S), dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    l = loss_record(spec)
+    check(lib.n3d_head_loss_eval(C.byref(h), C.byref(l), ptr(p), Co * x.N, x.N, 1, ptr(t), ts[0], ts[1], ts[2], float(thr), ptr(partial),
+                                 ptr(hpartial), ptr(sums), ptr(loss), ptr(acc), stream_ptr()), "n3d_head_loss_eval")
+    return loss, p
+
+
+def head_loss_bwd(x, w, bias, gate, dx, dw, dbias, t, coef, dloss=None, accumulate=False):
+    """backward of head_loss_fwd in one pass (n3d_head_loss_bwd): dx (+)=, dw, dbias from the targets and the forward's coefficients"""
+    lib = _lib.load()
+    h = _head_desc(x, w, bias, gate, dx if isinstance(x, Planar) else None, t=t)
+    ws = None
+    n = 0
+    job = None
+    if dw is not None or dbias is not None:
+        n = int(lib.n3d_head_workspace_bytes(C.byref(h)))
+        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=x.t.device)
+        job = FinalJob() if _ctx is not None else None
+    ts = _bcv_strides(t)
+    check(lib.n3d_head_loss_bwd(C.byref(h), ptr(t), ts[0], ts[1], ts[2], ptr(coef), ptr(dloss),
+                                dx.nodes[0].p if isinstance(dx, Planar) else dx.p, dx.cn if isinstance(dx, Planar) else dx.ld, dx.dt,
+                                ACCUMULATE if accumulate else 0, ptr(dw), ptr(dbias), ptr(ws), n,
+                                C.byref(job) if job is not None else None, stream_ptr()), "n3d_head_loss_bwd")
+    if job is not None and job.nchunks > 0:
+        _ctx.final.append(job)
+        _ctx.keep.append(ws)
+
+
+def tversky_fwd(p, t, spec):
+    """Tversky / focal loss on probabilities (n3d_tversky_fwd): (loss, sums (B, C, 3), coef (2 B C floats for tversky_bwd))"""
+    lib = _lib.load()
+    B, Cc = p.shape[0], p.shape[1]
+    N = p.shape[2] * p.shape[3] * p.shape[4]
+    ps, ts = _bcv_strides(p), _bcv_strides(t)
+    partial = torch.empty((B, Cc, int(lib.n3d_dice_rows(N)), 3), dtype=torch.float64, device=p.device)
+    sums = torch.empty((B, Cc, 3), dtype=torch.float64, device=p.device)
+    coef = torch.empty(2 * B * Cc, dtype=torch.float32, device=p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    l = loss_record(spec)
+    check(lib.n3d_tversky_fwd(ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], B, Cc, N, C.byref(l), ptr(partial), ptr(sums),
+                              ptr(coef), ptr(loss), stream_ptr()), "n3d_tversky_fwd")
+    return loss, sums, coef
+
+
+def tversky_bwd(t, coef, dloss, dp):
+    B, Cc = t.shape[0], t.shape[1]
+    N = t.shape[2] * t.shape[3] * t.shape[4]
+    ts, ds = _bcv_strides(t), _bcv_strides(dp)
+    check(_lib.load().n3d_tversky_bwd(ptr(t), ts[0], ts[1], ts[2], B, Cc, N, ptr(coef), ptr(dloss), ptr(dp), ds[0], ds[1], ds[2],
+                                      stream_ptr()), "n3d_tversky_bwd")
+
+
 def ncdhw_to_ndhwc(src):
     """(B,C,D,H,W) contiguous NCDHW -> dense NDHWC (logical shape unchanged)."""
     B, Cc, D, H, W = src.shape

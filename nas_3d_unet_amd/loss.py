@@ -32,6 +32,56 @@ class _DiceFn(torch.autograd.Function):
         return dp, None, None
 
 
+class _TverskyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, spec):
+        if not p.is_cuda:
+            raise N3DError("TverskyBCELoss: predictions are on %s; no CPU fallback" % p.device)
+        if p.dtype != torch.float32 or t.dtype != torch.float32:
+            raise N3DError("TverskyBCELoss: fp32 tensors expected")
+        if K._bcv_strides(p) is None:
+            p = p.contiguous()
+        if K._bcv_strides(t) is None:
+            t = t.contiguous()
+        loss, _, coef = K.tversky_fwd(p, t, spec)
+        ctx.save_for_backward(p, t, coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        p, t, coef = ctx.saved_tensors
+        dp = torch.empty_like(p)  # preserves p's (NDHWC) strides
+        if K._bcv_strides(dp) is None:
+            dp = torch.empty(p.shape, device=p.device, dtype=p.dtype)
+        K.tversky_bwd(t, coef, dloss.contiguous(), dp)
+        return dp, None, None
+
+
+class TverskyBCELoss(nn.Module):
+    """mean_{b,c} u^gamma + bce_weight * mean_{b,c,v} BCE-with-logits(z, t), with u = max(1 - TI, 0) and the Tversky index
+    TI = (A + s) / (A + alpha (P - A) + beta (T - A) + s) of A = sum(p*t), P = sum(p), T = sum(t) over the last three dims.
+    alpha weighs false positives, beta false negatives; gamma != 1 is the focal form.  A pair with u == 0 contributes 0 and a ZERO
+    gradient for every gamma (torch.pow's derivative is infinite there for gamma < 1).  alpha = beta = 0.5, gamma = 1, smooth = s / 2
+    is WeightedDiceLoss(smooth=s).
+
+    The trainers and `forward_loss(..., loss=...)` form the loss inside the fused head, from the logits.  Called as a module on
+    probabilities -- the reference's training-loop form -- it takes the Tversky / focal term only: the cross-entropy term is formed
+    from logits and exists in the fused head only, so bce_weight > 0 raises N3DError here."""
+
+    def __init__(self, alpha=0.5, beta=0.5, gamma=1.0, bce_weight=0.0, smooth=1e-6):
+        super().__init__()
+        if not (alpha >= 0 and beta >= 0 and alpha + beta > 0 and gamma > 0 and bce_weight >= 0 and smooth > 0):
+            raise ValueError("TverskyBCELoss: alpha, beta >= 0, alpha + beta > 0, gamma > 0, bce_weight >= 0 and smooth > 0 are required "
+                             "(alpha=%r beta=%r gamma=%r bce_weight=%r smooth=%r)" % (alpha, beta, gamma, bce_weight, smooth))
+        self.alpha, self.beta, self.gamma, self.bce_weight, self.smooth = float(alpha), float(beta), float(gamma), float(bce_weight), float(smooth)
+
+    def forward(self, y_pred, y_truth):
+        if self.bce_weight > 0:
+            raise N3DError("TverskyBCELoss: the cross-entropy term is formed from logits and exists in the fused head only "
+                           "(bce_weight=%g): train through Trainer(loss=...) or forward_loss(..., loss=...)" % self.bce_weight)
+        return _TverskyFn.apply(y_pred, y_truth, self)
+
+
 class WeightedDiceLoss(nn.Module):
     """1 - mean_{b,c} (2*sum(p*t)+eps) / (sum(p)+sum(t)+eps), sums over the last three dims."""
 

@@ -35,10 +35,10 @@ class KernelNet(nn.Module):
             return unet.run_padded(self, x, (alpha1_down, alpha1_up, alpha2_down, alpha2_up))
         return unet.run(self, x, (alpha1_down, alpha1_up, alpha2_down, alpha2_up))
 
-    def forward_loss(self, x, t, alpha1_down, alpha1_up, alpha2_down, alpha2_up, smooth=1e-6):
+    def forward_loss(self, x, t, alpha1_down, alpha1_up, alpha2_down, alpha2_up, smooth=1e-6, *, loss=None):
         if self._n3d_padded:
-            return unet.run_padded(self, x, (alpha1_down, alpha1_up, alpha2_down, alpha2_up), t, smooth)
-        return unet.run_loss(self, x, t, (alpha1_down, alpha1_up, alpha2_down, alpha2_up), smooth)
+            return unet.run_padded(self, x, (alpha1_down, alpha1_up, alpha2_down, alpha2_up), t, smooth, loss=loss)
+        return unet.run_loss(self, x, t, (alpha1_down, alpha1_up, alpha2_down, alpha2_up), smooth, loss=loss)
 
 
 class ShellNet(nn.Module):
@@ -64,9 +64,10 @@ class ShellNet(nn.Module):
     def forward(self, x):
         return self.kernel(x, *self._soft())
 
-    def forward_loss(self, x, t, smooth=1e-6):
-        """(Dice loss, probabilities) with the loss formed inside the head's launches (search.py:224-226,233-235)"""
-        return self.kernel.forward_loss(x, t, *self._soft(), smooth=smooth)
+    def forward_loss(self, x, t, smooth=1e-6, *, loss=None):
+        """(Dice loss, probabilities) with the loss formed inside the head's launches (search.py:224-226,233-235);
+        loss: a loss.TverskyBCELoss to form that loss there instead"""
+        return self.kernel.forward_loss(x, t, *self._soft(), smooth=smooth, loss=loss)
 
     def get_gene(self):
         a1d, a1u, a2d, a2u = (a.detach().cpu().numpy() for a in self._soft())

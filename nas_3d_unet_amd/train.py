@@ -28,15 +28,34 @@ import torch.distributed as dist
 from . import comm as _comm
 from . import fused as _fused
 from . import kernels as K
-from .loss import WeightedDiceLoss
+from .loss import TverskyBCELoss, WeightedDiceLoss
 
 
 def _loss_of(model, loss_fn, x, t):
-    """Dice loss of the model on (x, t): through the model's fused head + loss path when it has one"""
+    """loss of the model on (x, t): through the model's fused head + loss path when it has one"""
     fl = getattr(model, "forward_loss", None)
     if fl is not None and isinstance(loss_fn, WeightedDiceLoss):
         return fl(x, t, loss_fn.smooth)[0]
+    if fl is not None and isinstance(loss_fn, TverskyBCELoss):
+        return fl(x, t, loss=loss_fn)[0]
     return loss_fn(model(x), t)
+
+
+def _trainer_loss(loss, kernel):
+    """the loss a trainer trains `kernel` with: WeightedDiceLoss() by default, or the caller's WeightedDiceLoss / TverskyBCELoss -- whose
+    cross-entropy term needs the fused three-channel head (head.check_loss_head raises with the reason)"""
+    if loss is None:
+        return WeightedDiceLoss()
+    if not isinstance(loss, (WeightedDiceLoss, TverskyBCELoss)):
+        raise TypeError("loss must be a WeightedDiceLoss or a TverskyBCELoss (got %s)" % type(loss).__name__)
+    from . import head as _head
+    head = getattr(kernel, "last_conv", None)
+    if head is not None:
+        _head.check_loss_head(head, loss)
+    elif isinstance(loss, TverskyBCELoss) and loss.bce_weight > 0:
+        raise K.N3DError("TverskyBCELoss(bce_weight=%g): the cross-entropy term is formed inside the fused head, and this model has no "
+                         "`last_conv` head" % loss.bce_weight)
+    return loss
 
 
 GRAD_HEADER = 4   # floats in front of a flat gradient buffer (FlatParams.grad_full)
@@ -926,9 +945,9 @@ class _TwinShell:
     def __init__(self, shell, twin):
         self.shell, self.kernel = shell, twin
 
-    def forward_loss(self, x, t, smooth=1e-6):
+    def forward_loss(self, x, t, smooth=1e-6, *, loss=None):
         from . import unet as _unet
-        return _unet.run_loss(self.kernel, x, t, tuple(self.shell._soft()), smooth)
+        return _unet.run_loss(self.kernel, x, t, tuple(self.shell._soft()), smooth, loss=loss)
 
     def modules(self):
         return self.kernel.modules()
@@ -954,8 +973,10 @@ class _GraphTrainer:
     N_INPUTS = 2        # tensors step() takes
     TIMING = (2, 6)     # (warm-up, timed) replays of each schedule in _choose_schedule
 
-    def __init__(self, model, kernel, lr, betas, eps, graph, process_group, side_wgrad):
-        """kernel: the module whose parameters the trainer trains (the model itself, or a shell's kernel net)"""
+    def __init__(self, model, kernel, lr, betas, eps, graph, process_group, side_wgrad, loss=None):
+        """kernel: the module whose parameters the trainer trains (the model itself, or a shell's kernel net)
+        loss: None (WeightedDiceLoss()), a WeightedDiceLoss or a TverskyBCELoss -- a constructor argument, as in the reference, and
+        like there no part of a checkpoint"""
         self.model = model
         # channel counts that are not multiples of 4: the trainer trains the kernel module's zero-padded TWIN (unet.PaddedTwin; padded
         # entries have exactly-zero gradients, so Adam never moves them) and cuts the parameters back into it at the host-visible
@@ -987,7 +1008,7 @@ class _GraphTrainer:
         # N3D_FORCE_DP=1: take the multi-GPU code path (all-reduce + eager Adam after the graph) even in a 1-rank group --
         # lets a single-GPU box exercise exactly what N > 1 runs
         self.dp_path = self.world > 1 or (dist.is_initialized() and os.environ.get("N3D_FORCE_DP") == "1")
-        self.loss_fn = WeightedDiceLoss()
+        self.loss_fn = _trainer_loss(loss, kernel if self._twin is None else self._twin.twin)
         self.lr, self.betas, self.eps = lr, betas, eps
         self.device = next(model.parameters()).device
         # evaluation pass (evaluate / eval_result): its accumulator, weight packing, and captured graph with its input buffers
@@ -1216,7 +1237,7 @@ class _GraphTrainer:
                 # (the input layout of the head as unet.run_loss chooses it: node-planar for float targets)
                 planar = _unet._head_takes_planar(net) and t.dtype == torch.float32
                 body = _unet.body(net, x, alphas() if alphas is not None else None, planar=planar)
-                loss = _head.run_eval(net.last_conv, body, t, self._eval_acc, self.loss_fn.smooth, self.EVAL_THRESHOLD)
+                loss = _head.run_eval(net.last_conv, body, t, self._eval_acc, self.loss_fn.smooth, self.EVAL_THRESHOLD, loss=self.loss_fn)
             if not self._eval_ctx.frozen:
                 self._eval_ctx.freeze()
         finally:
@@ -1344,14 +1365,14 @@ class Trainer(_GraphTrainer):
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None,
                  n_buckets=None, params=None, comm=None, storage=None, side_wgrad=None, optimizer="adam", optim_args=None,
-                 grad_clip=None):
+                 grad_clip=None, loss=None):
         self.optim = OptimSpec(optimizer, lr, betas, eps, optim_args)
-        super().__init__(model, model, lr, betas, eps, graph, process_group, side_wgrad)
+        super().__init__(model, model, lr, betas, eps, graph, process_group, side_wgrad, loss)
         self.net = model      # the module whose kernels run (the model itself, or its padded twin)
         if self._twin is not None:
             from . import unet as _unet
             tw = self.net = self._twin.twin
-            tw.forward_loss = lambda x, t, smooth=1e-6, _tw=tw: _unet.run_loss(_tw, x, t, None, smooth)
+            tw.forward_loss = lambda x, t, smooth=1e-6, _tw=tw, loss=None: _unet.run_loss(_tw, x, t, None, smooth, loss=loss)
         # side_wgrad: the weight-gradient kernels of the C in {4, 8} levels -- nothing on the backward chain waits for them -- are
         # queued during the backward walk and launched on a SIDE HIP stream at a few cut points (cell boundaries), as separately
         # launched graphs tied to the main chain by events; the streams join once, in front of the slab reduction + Adam.  (Round 3:
@@ -1464,7 +1485,7 @@ class Trainer(_GraphTrainer):
         return loss.detach()
 
     def _pipeline(self, x, t, cell_hook):
-        """forward + Dice + backward WITHOUT autograd: fused.NetFn and head.HeadDiceFn are called directly, so the backward walk
+        """forward + loss + backward WITHOUT autograd: fused.NetFn and head.HeadDiceFn / HeadLossFn are called directly, so the backward walk
         is one Python function on this thread and can hand over work on the way: cell_hook(k) is called when the backward of cell k
         (-1: the stems, i.e. the end) has been launched."""
         from . import head as _head, programs as _P
@@ -1481,8 +1502,12 @@ class Trainer(_GraphTrainer):
             gate = _P.draw_gate(op.dropout, op.training, *_head.feat_shape(body), body.device)
             hctx = _Ctx((False, False, True, False, True, True))
             hctx.skip_p = True        # the step returns the loss only: the head does not write the probabilities
-            loss, _ = _head.HeadDiceFn.forward(hctx, gate, float(self.loss_fn.smooth), body, t, op.conv.weight, op.conv.bias)
-            dbody = _head.HeadDiceFn.backward(hctx, self._one, None)[2]
+            if isinstance(self.loss_fn, TverskyBCELoss):
+                loss, _ = _head.HeadLossFn.forward(hctx, gate, self.loss_fn, body, t, op.conv.weight, op.conv.bias)
+                dbody = _head.HeadLossFn.backward(hctx, self._one, None)[2]
+            else:
+                loss, _ = _head.HeadDiceFn.forward(hctx, gate, float(self.loss_fn.smooth), body, t, op.conv.weight, op.conv.bias)
+                dbody = _head.HeadDiceFn.backward(hctx, self._one, None)[2]
             with _fused.switched(REUSE_GRAD_OUTPUT=True, CELL_DONE_HOOK=cell_hook):
                 _fused.NetFn.backward(nctx, dbody)
         if not self.ctx.frozen:
@@ -1490,10 +1515,10 @@ class Trainer(_GraphTrainer):
         return loss
 
     def _direct_ok(self):
-        """can the step run as the autograd-free pipeline (a stems / cells / fusable-head net with the Dice loss)?"""
+        """can the step run as the autograd-free pipeline (a stems / cells / fusable-head net with a loss the head forms)?"""
         from . import head as _head
         m = self.net
-        return (_fused.WHOLE_NET and isinstance(self.loss_fn, WeightedDiceLoss) and not hasattr(m, "kernel")
+        return (_fused.WHOLE_NET and isinstance(self.loss_fn, (WeightedDiceLoss, TverskyBCELoss)) and not hasattr(m, "kernel")
                 and all(hasattr(m, a) for a in ("stem0", "stem1", "down_cells", "up_cells", "last_conv"))
                 and _head.fusable(m.last_conv, torch.empty((1, m.last_conv[0].conv.weight.shape[1], 1, 1, 1), device="meta")))
 
@@ -1716,11 +1741,12 @@ class SearchTrainer(_GraphTrainer):
     TIMING = (1, 3)
 
     def __init__(self, shell, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None, comm=None, side_wgrad=None,
-                 optimizer="adam", optim_args=None, grad_clip=None):
+                 optimizer="adam", optim_args=None, grad_clip=None, loss=None):
+        # loss: both passes, the architecture pass and the weight pass (search.py:224-226,233-235 call one loss function)
         # optimizer / optim_args / grad_clip: the weight pass (search.py:236-238: the commented clip line sits in front of
         # optim_kernel.step()); the alphas stay on Adam (search.py:103)
         self.optim = OptimSpec(optimizer, lr, betas, eps, optim_args)
-        super().__init__(shell, shell.kernel, lr, betas, eps, graph, process_group, side_wgrad)
+        super().__init__(shell, shell.kernel, lr, betas, eps, graph, process_group, side_wgrad, loss)
         # a kernel net with channel counts that are not multiples of 4: the shell's own alphas around its zero-padded twin
         self.net = shell if self._twin is None else _TwinShell(shell, self._twin.twin)
         # the weight pass queues its weight-gradient kernels for the side stream (SideSchedule); the architecture pass has none

@@ -170,10 +170,11 @@ def _padded_net_fn():
     import torch
 
     class PaddedNetFn(torch.autograd.Function):
-        """inputs: (net, twin, need_grad, loss target | None, smooth, number of alphas, x, *alphas, *the net's parameters in twin.names order)"""
+        """inputs: (net, twin, need_grad, loss target | None, (smooth, loss), number of alphas, x, *alphas, *the net's parameters in
+        twin.names order)"""
 
         @staticmethod
-        def forward(ctx, net, tw, need_grad, loss_target, smooth, n_al, xin, *rest):
+        def forward(ctx, net, tw, need_grad, loss_target, loss_spec, n_al, xin, *rest):
             al = rest[:n_al]
             tw.embed(net)
             with fused.padded_switches(), torch.set_grad_enabled(need_grad):
@@ -182,7 +183,7 @@ def _padded_net_fn():
                 if loss_target is None:
                     out = (run(tw.twin, xi, ali if n_al else None),)
                 else:
-                    out = run_loss(tw.twin, xi, loss_target, ali if n_al else None, smooth)
+                    out = run_loss(tw.twin, xi, loss_target, ali if n_al else None, loss_spec[0], loss=loss_spec[1])
             if need_grad:
                 ctx.saved = (tw, xi, ali, out)
             return tuple(o.detach() for o in out)
@@ -210,8 +211,9 @@ def _padded_net_fn():
 _PaddedNetFn = None
 
 
-def run_padded(net, x, alphas=None, loss_target=None, smooth=1e-6):
-    """forward (probabilities, or (Dice loss, probabilities) with loss_target) of a net with odd channel counts through its padded twin"""
+def run_padded(net, x, alphas=None, loss_target=None, smooth=1e-6, loss=None):
+    """forward (probabilities, or (loss, probabilities) with loss_target; loss as in run_loss) of a net with odd channel counts
+    through its padded twin"""
     import torch
     tw = net.__dict__.get("_n3d_twin")
     if tw is None or next(net.parameters()).device != next(tw.twin.parameters()).device:
@@ -221,7 +223,7 @@ def run_padded(net, x, alphas=None, loss_target=None, smooth=1e-6):
     als = tuple(alphas) if alphas is not None else ()
     # inference (no_grad / nothing requires a gradient): the twin runs under no_grad too -- no autograd graph, no saved activations
     need_grad = torch.is_grad_enabled() and (x.requires_grad or any(r.requires_grad for r in reals) or any(a.requires_grad for a in als))
-    res = _padded_net_fn().apply(net, tw, need_grad, loss_target, smooth, len(als), x, *als, *reals)
+    res = _padded_net_fn().apply(net, tw, need_grad, loss_target, (smooth, loss), len(als), x, *als, *reals)
     return res[0] if loss_target is None else res
 
 
@@ -270,10 +272,11 @@ def run(net, x, alphas=None):
     return _head.run(net.last_conv, body(net, x, alphas, planar=_head_takes_planar(net)))
 
 
-def run_loss(net, x, t, alphas=None, smooth=1e-6):
-    """(Dice loss, probabilities): forward with the loss of loss.py:12-14 formed inside the head's passes (the trainers' path)"""
+def run_loss(net, x, t, alphas=None, smooth=1e-6, loss=None):
+    """(loss, probabilities): forward with the loss formed inside the head's passes (the trainers' path) -- the Dice loss of
+    loss.py:12-14, or the loss.TverskyBCELoss `loss`"""
     import torch
-    return _head.run_loss(net.last_conv, body(net, x, alphas, planar=_head_takes_planar(net) and t.dtype == torch.float32), t, smooth)
+    return _head.run_loss(net.last_conv, body(net, x, alphas, planar=_head_takes_planar(net) and t.dtype == torch.float32), t, smooth, loss=loss)
 
 
 def _head_takes_planar(net):
