@@ -623,6 +623,47 @@ typedef struct n3d_patch_adesc { n3d_patch_gdesc g; int32_t aflip[3]; int32_t id
 int n3d_patch_gather_aug(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_adesc* descs, int B, int P, int flags,
                          float* x_out, int64_t xld, void* t_out, void* stream);
 
+/* n3d_patch_gather_aug with a full 3x4 resampling map (a small rotation composed with the scale), linear interpolation of the
+ * DATA (the truth stays nearest neighbour) and a per-channel intensity scale and shift of the nonzero voxels, in the same single
+ * launch.  For output voxel i of patch b, with j = the patch index the isometry of g.d gives (as n3d_patch_gather) and k[0..11]
+ * the twelve fp64 coefficients:
+ *   coordinate, mode 0:  c_a = ((double)j_a + sh[a]) * A[a],  A = k[0..2], sh = k[3..5]  -- n3d_patch_gather_aug's rule, bit for
+ *                        bit (its `identity` is A = 1, sh = 0, which the formula reproduces exactly); k[6..11] are only checked;
+ *   coordinate, mode 1:  c_a = ((m[a][0]*j_0 + m[a][1]*j_1) + m[a][2]*j_2) + off[a],  m = k[0..8] row-major, off = k[9..11]:
+ *                        products in axis order, the offset last, every product and every sum rounded to fp64 on its own (what
+ *                        scipy.ndimage.affine_transform does with a 2-D matrix);
+ *   bounds:              the voxel has a source iff 0 <= c_a <= P-1 on all three axes, tested on c itself; otherwise the data and
+ *                        every target are 0;
+ *   labels:              always the one voxel r_a = (int)floor(c_a + 0.5);
+ *   data, order 0:       the same voxel;
+ *   data, order 1:       f_a = floor(c_a), w_a = c_a - f_a in fp64; the eight taps f + d, d in {0,1}^3, visited in lexicographic
+ *                        order of (d_0, d_1, d_2); tap weight (u_0 * u_1) * u_2 with u_a = d_a ? w_a : 1.0 - w_a; acc = 0.0, then
+ *                        acc = acc + weight * (double)x per tap (a separate multiply and add); a tap whose index exceeds P-1 (it
+ *                        can only have w_a == 0) is skipped and never read, and so is a tap outside the volume (the crop's zero
+ *                        padding) -- the kernel may load voxel 0 of the channel in such a tap's place and drop the value; the
+ *                        result is (float)acc;
+ *   flip:                on an axis with aflip[a] every tap index r becomes P-1-r before corner[a] is added (the flip acts on the
+ *                        crop before it is resampled, as n3d_patch_gather_aug);
+ *   intensity:           with `intensity` set and y the resampled value of channel c: if y != 0 (-0.0 is zero), y = y * gain[c]
+ *                        rounded to fp32, then y = y + bias[c] rounded to fp32; a voxel that is 0 stays 0.  With `intensity` clear
+ *                        the bits are left as they are and gain, bias are only checked.  `intensity` needs Cv <= 4.
+ * mode and order are 0 or 1; all twelve coefficients, gain and bias are finite, and A is nonzero in mode 0.  With mode 0, order 0
+ * and `intensity` clear the output is bit-identical to n3d_patch_gather_aug (to n3d_patch_gather with A = 1, sh = 0, no aflip).
+ * descs: HOST array of at most N3D_PATCH_WARP_MAX_BATCH (the descriptors travel in the 4 KB of kernel arguments). */
+#define N3D_PATCH_WARP_MAX_BATCH 16
+typedef struct n3d_patch_wdesc {
+  n3d_patch_gdesc g;
+  int32_t aflip[3];
+  int32_t mode;        /* 0: zoom-shift rule, 1: matrix rule */
+  int32_t order;       /* 0: nearest, 1: linear -- the data only */
+  int32_t intensity;   /* != 0: gain and bias are applied to the nonzero voxels */
+  double k[12];
+  float gain[4];
+  float bias[4];
+} n3d_patch_wdesc;
+int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_wdesc* descs, int B, int P, int flags,
+                          float* x_out, int64_t xld, void* t_out, void* stream);
+
 /* ---- the step before the data step (preprocess.py:77-144, create_h5:58-66): raw scanner counts to the statistics of the data
  * set and to each subject's normalised brain-wise box.  raw: DEVICE int16 (Cm, X, Y, Z) contiguous, 2-byte aligned (a modality's
  * base need not be 16-byte aligned: X * Y * Z may be odd); X * Y * Z < 2^31.  "Brain" = the voxels with raw != 0, per modality.

@@ -115,6 +115,12 @@ class AugDesc(C.Structure):
     _fields_ = [("g", GatherDesc), ("aflip", C.c_int32 * 3), ("identity", C.c_int32), ("A", C.c_double * 3), ("sh", C.c_double * 3)]
 
 
+class WarpDesc(C.Structure):
+    """n3d_patch_wdesc (include/n3d.h)"""
+    _fields_ = [("g", GatherDesc), ("aflip", C.c_int32 * 3), ("mode", C.c_int32), ("order", C.c_int32), ("intensity", C.c_int32),
+                ("k", C.c_double * 12), ("gain", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
 class StitchEntry(C.Structure):
     """n3d_stitch_entry (include/n3d.h)"""
     _fields_ = [("d", PatchDesc), ("slot", C.c_int32)]
@@ -235,6 +241,7 @@ PROTOTYPES = {
     "n3d_patch_qualify": (_i, [_p, _i, _p, _i64, _i, _p, _p]),
     "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_aug": (_i, [_p, _i, _i, C.POINTER(AugDesc), _i, _i, _i, _p, _i64, _p, _p]),
+    "n3d_patch_gather_warp": (_i, [_p, _i, _i, C.POINTER(WarpDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_brain_scan": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "n3d_brain_sqdev_rows": (_i, [_i64]),
     "n3d_brain_sqdev": (_i, [_p, _i, _i64, _p, _p, _p, _p]),

@@ -21,10 +21,34 @@ namespace n3d {
 struct PatchDescs { n3d_patch_desc d[N3D_PATCH_MAX_BATCH]; };
 struct GatherDescs { n3d_patch_gdesc d[N3D_PATCH_MAX_BATCH]; };
 
-// one output voxel (b, i0, i1, i2) of patch d drawn from the volume (vol, truth, X, Y, Z): the index mapping shared by
-// patch_batch_kernel (one volume per launch) and patch_gather_kernel (a volume per patch).  v < P^3.
-// TT: storage of the three target maps -- float, or uint8_t (N3D_PATCH_T_U8: the generator's booleans as bytes, what n3d_head_fwd /
-// n3d_head_bwd read with t_dtype = N3D_U8)
+// the Cv data values of output voxel v of patch b, value(c) for channel c: one float4 for Cv == 4 on an aligned pitch
+template <typename F>
+__device__ __forceinline__ void patch_data_store(int Cv, int b, uint32_t v, uint32_t P3, float* __restrict__ x_out, int64_t xld, F value) {
+  float* xo = x_out + ((int64_t)b * P3 + v) * xld;
+  if (Cv == 4 && (xld & 3) == 0) {
+    float4 q;
+    q.x = value(0); q.y = value(1); q.z = value(2); q.w = value(3);
+    *reinterpret_cast<float4*>(xo) = q;
+  } else {
+    for (int c = 0; c < Cv; ++c) xo[c] = value(c);
+  }
+}
+
+// the three target maps of output voxel v of patch b from its label voxel sv (in = false: no source, label 0)
+template <typename TT>
+__device__ __forceinline__ void patch_label_store(const uint8_t* __restrict__ truth, bool in, int64_t sv, int b, uint32_t v, uint32_t P3,
+                                                  int inclusive, TT* __restrict__ t_out) {
+  // (a gathered patch whose volume has no truth reads as label 0 everywhere; n3d_patch_batch never gets here without truth)
+  const int l = (in && truth) ? (int)truth[sv] : 0;
+  // generator.py:241-243 -- the inclusive "whole tumour" channel is labels {1, 2}: np.logical_or's third argument
+  // is its OUT array there, so label 4 does not enter (reproduced, not corrected)
+  const TT c0 = inclusive ? (TT)(l == 1 || l == 4) : (TT)(l == 1);
+  const TT c1 = inclusive ? (TT)(l == 1 || l == 2) : (TT)(l == 2);
+  const TT c2 = (TT)(l == 4);
+  TT* to = t_out + (int64_t)b * 3 * P3 + v;
+  to[0] = c0; to[P3] = c1; to[2 * (int64_t)P3] = c2;
+}
+
 // the loads, the stores and the label expansion of output voxel v of patch b, given its source voxel s of the volume (ok = false:
 // the patch voxel has no source -- resampled from outside the patch -- and reads as outside the volume does: zero, label 0)
 template <typename TT>
@@ -35,25 +59,8 @@ __device__ __forceinline__ void patch_voxel_store(const float* __restrict__ vol,
   const bool in = ok && s[0] >= 0 && s[0] < X && s[1] >= 0 && s[1] < Y && s[2] >= 0 && s[2] < Z;
   const int64_t sv = in ? ((int64_t)s[0] * Y + s[1]) * Z + s[2] : 0;
   const int64_t XYZ = (int64_t)X * Y * Z;
-  float* xo = x_out + ((int64_t)b * P3 + v) * xld;
-  if (Cv == 4 && (xld & 3) == 0) {
-    float4 q;
-    q.x = in ? vol[sv] : 0.f; q.y = in ? vol[XYZ + sv] : 0.f; q.z = in ? vol[2 * XYZ + sv] : 0.f; q.w = in ? vol[3 * XYZ + sv] : 0.f;
-    *reinterpret_cast<float4*>(xo) = q;
-  } else {
-    for (int c = 0; c < Cv; ++c) xo[c] = in ? vol[c * XYZ + sv] : 0.f;
-  }
-  if (t_out) {
-    // (a gathered patch whose volume has no truth reads as label 0 everywhere; n3d_patch_batch never gets here without truth)
-    const int l = (in && truth) ? (int)truth[sv] : 0;
-    // generator.py:241-243 -- the inclusive "whole tumour" channel is labels {1, 2}: np.logical_or's third argument
-    // is its OUT array there, so label 4 does not enter (reproduced, not corrected)
-    const TT c0 = inclusive ? (TT)(l == 1 || l == 4) : (TT)(l == 1);
-    const TT c1 = inclusive ? (TT)(l == 1 || l == 2) : (TT)(l == 2);
-    const TT c2 = (TT)(l == 4);
-    TT* to = t_out + (int64_t)b * 3 * P3 + v;
-    to[0] = c0; to[P3] = c1; to[2 * (int64_t)P3] = c2;
-  }
+  patch_data_store(Cv, b, v, P3, x_out, xld, [=](int c) { return in ? vol[c * XYZ + sv] : 0.f; });
+  if (t_out) patch_label_store<TT>(truth, in, sv, b, v, P3, inclusive, t_out);
 }
 
 // patch index of output voxel v on source axis a under the isometry of d: j_a = i[perm[a]], or P-1-i[perm[a]] with flip[a]
@@ -69,6 +76,10 @@ __device__ __forceinline__ void patch_index(const n3d_patch_desc& d, uint32_t v,
   }
 }
 
+// one output voxel (b, i0, i1, i2) of patch d drawn from the volume (vol, truth, X, Y, Z): the index mapping shared by
+// patch_batch_kernel (one volume per launch) and patch_gather_kernel (a volume per patch).  v < P^3.
+// TT: storage of the three target maps -- float, or uint8_t (N3D_PATCH_T_U8: the generator's booleans as bytes, what n3d_head_fwd /
+// n3d_head_bwd read with t_dtype = N3D_U8)
 template <typename TT>
 __device__ __forceinline__ void patch_voxel(const float* __restrict__ vol, int Cv, const uint8_t* __restrict__ truth, int X, int Y, int Z,
                                             const n3d_patch_desc& d, int b, uint32_t v, int P, int inclusive, float* __restrict__ x_out,
@@ -135,6 +146,114 @@ __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const n3d_patch_v
     s[a] = ad.g.d.corner[a] + (ad.aflip[a] ? P - 1 - q : q);
   }
   patch_voxel_store<TT>(r.data, Cv, r.truth, r.dims[0], r.dims[1], r.dims[2], s, ok, b, v, P, inclusive, x_out, xld, t_out);
+}
+
+// patch_gather_aug_kernel with a 3x4 resampling map, linear interpolation of the data and a per-channel intensity map (include/n3d.h,
+// n3d_patch_wdesc, states the rule operation by operation).  The labels take the nearest voxel as above; the data takes it too (order
+// 0) or the eight voxels around the coordinate (order 1), each tap flipped, offset by the corner and tested against the volume on its
+// own.  mode, order and intensity are uniform over a workgroup (one patch per blockIdx.y).  Per output voxel at order 1: 8 * Cv loads
+// against 4 * Cv bytes stored, but the two d_2 taps are adjacent in memory and neighbouring output voxels share six or more of their
+// taps, so the source bytes that reach HBM stay those of the nearest gather; the taps are served by the L1 / L2 and what the kernel
+// waits for is their latency: 2 x 4 x 64^3 rotated by 15 degrees takes 12.7 us at order 0 and 27.2 us at order 1, 27.6 us at order 1
+// without a rotation (profiles/warp_probe.log; the plain gather: 11.4 us).
+struct WarpDescs { n3d_patch_wdesc d[N3D_PATCH_WARP_MAX_BATCH]; };
+
+template <typename TT>
+__global__ __launch_bounds__(256) void patch_gather_warp_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, WarpDescs descs, int P, int inclusive,
+                                                                float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out, FastDiv fP,
+                                                                FastDiv fPP) {
+  const int b = blockIdx.y;
+  const n3d_patch_wdesc& w = descs.d[b];
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t P3 = (uint32_t)P * P * P;
+  if (v >= P3) return;
+  const n3d_patch_volume r = vols[w.g.vol];
+  const int X = r.dims[0], Y = r.dims[1], Z = r.dims[2];
+  const int dims[3] = {X, Y, Z};
+  const int64_t XYZ = (int64_t)X * Y * Z;
+  int j[3];
+  patch_index(w.g.d, v, P, fP, fPP, j);
+  double c[3];
+  if (w.mode == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = ((double)j[a] + w.k[3 + a]) * w.k[a];
+  } else {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double t = w.k[3 * a] * (double)j[0];
+      t = t + w.k[3 * a + 1] * (double)j[1];
+      t = t + w.k[3 * a + 2] * (double)j[2];
+      c[a] = t + w.k[9 + a];
+    }
+  }
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) ok = ok && 0.0 <= c[a] && c[a] <= (double)(P - 1);
+  // the nearest voxel: the labels' source, and the data's at order 0
+  bool in = ok;
+  int64_t sv = 0;
+  {
+    int s[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int q = ok ? (int)floor(c[a] + 0.5) : 0;
+      s[a] = w.g.d.corner[a] + (w.aflip[a] ? P - 1 - q : q);
+      in = in && s[a] >= 0 && s[a] < dims[a];
+    }
+    if (in) sv = ((int64_t)s[0] * Y + s[1]) * Z + s[2];
+  }
+  const bool intensity = w.intensity != 0;
+  const float* gain = w.gain;
+  const float* bias = w.bias;
+  // y != 0 is numpy's: -0.0 is zero and stays as it is (the lambdas capture by value: by reference the stores would be taken to alias)
+  auto shade = [=](float y, int ch) {
+    if (intensity && y != 0.f) {
+      y = y * gain[ch & 3];
+      y = y + bias[ch & 3];
+    }
+    return y;
+  };
+  if (w.order == 0) {
+    patch_data_store(Cv, b, v, P3, x_out, xld, [=](int ch) { return shade(in ? r.data[ch * XYZ + sv] : 0.f, ch); });
+  } else {
+    // per axis the two tap indices (flipped, in the volume's frame), whether each is read, and its weight
+    int64_t off[3][2];
+    bool use[3][2];
+    double u[3][2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double f = ok ? floor(c[a]) : 0.0;
+      const double wa = ok ? c[a] - f : 0.0;
+      u[a][0] = 1.0 - wa;
+      u[a][1] = wa;
+      const int64_t pitch = a == 0 ? (int64_t)Y * Z : (a == 1 ? (int64_t)Z : 1);
+#pragma unroll
+      for (int d = 0; d < 2; ++d) {
+        const int q = (int)f + d;
+        const int s = w.g.d.corner[a] + (w.aflip[a] ? P - 1 - q : q);
+        use[a][d] = ok && q <= P - 1 && s >= 0 && s < dims[a];
+        off[a][d] = use[a][d] ? s * pitch : 0;
+      }
+    }
+    patch_data_store(Cv, b, v, P3, x_out, xld, [=](int ch) {
+      const float* __restrict__ src = r.data + ch * XYZ;
+      // the eight loads are issued together and unconditionally: a tap that is not used reads voxel 0 of the channel instead (its
+      // offsets are 0) and is dropped by the select below.  One branch per tap would cost eight load round trips in a row.
+      float x[8];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) x[t] = src[off[0][t >> 2] + off[1][(t >> 1) & 1] + off[2][t & 1]];
+      double acc = 0.0;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int d0 = t >> 2, d1 = (t >> 1) & 1, d2 = t & 1;
+        const double wt = (u[0][d0] * u[1][d1]) * u[2][d2];
+        const double next = acc + wt * (double)x[t];
+        acc = (use[0][d0] && use[1][d1] && use[2][d2]) ? next : acc;
+      }
+      return shade((float)acc, ch);
+    });
+  }
+  if (t_out) patch_label_store<TT>(r.truth, in, sv, b, v, P3, inclusive, t_out);
 }
 
 }  // namespace n3d
@@ -234,6 +353,50 @@ extern "C" int n3d_patch_gather_aug(const n3d_patch_volume* vols, int nvol, int 
                        (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   else
     N3D_LAUNCH(patch_gather_aug_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, ad, P, inclusive, x_out, xld,
+                       (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_wdesc* descs, int B, int P, int flags,
+                                     float* x_out, int64_t xld, void* t_out, void* stream) {
+  N3D_CHECK_ARG(vols && descs && x_out && nvol >= 1 && Cv >= 1 && P > 0 && B >= 1 && xld >= Cv, "patch_gather_warp: bad args");
+  N3D_CHECK_ARG(B <= N3D_PATCH_WARP_MAX_BATCH, "patch_gather_warp: at most N3D_PATCH_WARP_MAX_BATCH = %d patches per call (got %d)",
+                N3D_PATCH_WARP_MAX_BATCH, B);
+  N3D_CHECK_ARG((int64_t)P * P * P < (1ll << 31), "patch_gather_warp: patch too large");
+  static_assert(sizeof(WarpDescs) + 64 <= 4096, "the descriptors travel by value in the kernel arguments (4 KB)");
+  WarpDescs wd;
+  for (int i = 0; i < B; ++i) {
+    const n3d_patch_wdesc& d = descs[i];
+    wd.d[i] = d;
+    N3D_CHECK_ARG(d.g.vol >= 0 && d.g.vol < nvol, "patch_gather_warp: descriptor %d names volume %d of a set of %d", i, d.g.vol, nvol);
+    int seen = 0;
+    for (int a = 0; a < 3; ++a) {
+      N3D_CHECK_ARG(d.g.d.perm[a] >= 0 && d.g.d.perm[a] < 3, "patch_gather_warp: perm entries must be 0..2");
+      seen |= 1 << d.g.d.perm[a];
+    }
+    N3D_CHECK_ARG(seen == 7, "patch_gather_warp: perm must be a permutation of (0,1,2)");
+    N3D_CHECK_ARG(d.mode == 0 || d.mode == 1, "patch_gather_warp: descriptor %d: mode must be 0 or 1 (got %d)", i, d.mode);
+    N3D_CHECK_ARG(d.order == 0 || d.order == 1, "patch_gather_warp: descriptor %d: order must be 0 or 1 (got %d)", i, d.order);
+    for (int n = 0; n < 12; ++n)
+      N3D_CHECK_ARG(std::isfinite(d.k[n]), "patch_gather_warp: descriptor %d: coefficient %d must be finite (got %g)", i, n, d.k[n]);
+    for (int a = 0; a < 3 && d.mode == 0; ++a)
+      N3D_CHECK_ARG(d.k[a] != 0.0, "patch_gather_warp: descriptor %d axis %d: A must be nonzero in mode 0", i, a);
+    for (int c = 0; c < 4; ++c)
+      N3D_CHECK_ARG(std::isfinite(d.gain[c]) && std::isfinite(d.bias[c]),
+                    "patch_gather_warp: descriptor %d channel %d: gain and bias must be finite (got %g, %g)", i, c, d.gain[c], d.bias[c]);
+    N3D_CHECK_ARG(!d.intensity || Cv <= 4, "patch_gather_warp: descriptor %d: the intensity map supports at most 4 channels (got %d)", i, Cv);
+  }
+  for (int i = B; i < N3D_PATCH_WARP_MAX_BATCH; ++i) wd.d[i] = wd.d[0];
+  N3D_CHECK_ARG((flags & ~(N3D_PATCH_INCLUSIVE | N3D_PATCH_T_U8)) == 0, "patch_gather_warp: unknown flag bits %d", flags);
+  const uint32_t P3 = (uint32_t)P * P * P;
+  const int inclusive = flags & N3D_PATCH_INCLUSIVE;
+  const dim3 grid((unsigned)cdiv(P3, 256), B);
+  if (flags & N3D_PATCH_T_U8)
+    N3D_LAUNCH(patch_gather_warp_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, wd, P, inclusive, x_out, xld,
+                       (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  else
+    N3D_LAUNCH(patch_gather_warp_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, wd, P, inclusive, x_out, xld,
                        (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   N3D_LAUNCH_CHECK();
   return N3D_OK;

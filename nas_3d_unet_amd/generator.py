@@ -15,9 +15,14 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
     from numpy's generator exactly as the reference does and composes the resampling into the same single launch
     (n3d_patch_gather_aug): draw_augment, scale_affine, resample_transform and resample_params below are the reference's and
     nilearn's fp64 host arithmetic; the resampler is scipy.ndimage.affine_transform's rule for a diagonal matrix (order 0, mode
-    "constant") restated -- nilearn itself was never run against this package.
+    "constant") restated -- nilearn itself was never run against this package;
+  * augment_rotation / augment_interpolation / augment_intensity_scale / augment_intensity_shift (none of them the reference's)
+    add a small rotation about the patch centre, linear interpolation of the data (the truth stays nearest neighbour) and a
+    per-modality intensity scale and shift of the brain voxels, still in ONE launch per batch (n3d_patch_gather_warp):
+    rotation_matrix, warp_transform and draw_warp below are their host arithmetic and draws.
 
-Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather and n3d_patch_gather_aug (include/n3d.h).
+Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather, n3d_patch_gather_aug and
+n3d_patch_gather_warp (include/n3d.h).
 """
 from __future__ import annotations
 
@@ -30,13 +35,15 @@ import torch
 
 from . import _lib, datastep, predict, preprocess
 from . import kernels as K
-from ._lib import AugDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, check
+from ._lib import AugDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, WarpDesc, check
 
 # augment.py:95-100 draws from list(set(...)): that (deterministic) order, NOT the sorted one of datastep.random_permutation_key
 KEYS = list(datastep.generate_permutation_keys())
 LABELS = [1, 2, 4]
 MAX_BATCH = 64      # N3D_PATCH_MAX_BATCH
 AUG_MAX_BATCH = 32  # N3D_PATCH_AUG_MAX_BATCH: the widened descriptors of an augmented batch travel in 4 KB of kernel arguments
+WARP_MAX_BATCH = 16  # N3D_PATCH_WARP_MAX_BATCH
+WARP_MAX_CHANNELS = 4  # gain[4], bias[4] of n3d_patch_wdesc
 
 _ISO = {None: ([0, 1, 2], [False, False, False])}
 
@@ -125,13 +132,58 @@ def resample_params(affine, P, scale):
     return A, b / A, identity
 
 
-def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None):
+def rotation_matrix(angles_deg):
+    """R = Rz . Ry . Rx of the three angles (about axes 0, 1, 2, in degrees) as a (3, 3) float64 array.  The radians are
+    angle * pi / 180 in this order, sines and cosines are numpy's, and every entry is the written-out product below, evaluated left
+    to right in fp64 (no matrix product: a BLAS may fuse or reorder)."""
+    ax, ay, az = (np.float64(a) * np.pi / 180.0 for a in angles_deg)
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    return np.array([[cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx],
+                     [sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx],
+                     [-sy, cy * sx, cy * cx]], dtype=np.float64)
+
+
+def warp_transform(A, b, R, P):
+    """(M, off) of n3d_patch_wdesc's matrix rule for a P^3 patch: the output index is rotated by R about the patch's voxel centre
+    p = (P - 1) / 2 on every axis, then the reference's scale map c -> A * c + b (resample_transform; A = 1, b = 0 when no scale was
+    drawn or nilearn would return the image as it is) is applied:  M = A[:, None] * R,  off = A * (p - R p) + b, with
+    R p = (R[:, 0] * p + R[:, 1] * p) + R[:, 2] * p, elementwise fp64.  The rotation is in VOXEL space: the affine's diagonal enters
+    through (A, b) only, so under an anisotropic affine the rotation is not rigid in world space (BraTS is 1 mm isotropic)."""
+    A, b, R = np.asarray(A, np.float64), np.asarray(b, np.float64), np.asarray(R, np.float64)
+    if R.shape != (3, 3) or A.shape != (3,) or b.shape != (3,):
+        raise N3DError("warp_transform: A and b are (3,), R is (3, 3)")
+    p = np.float64(P - 1) / 2
+    Rp = (R[:, 0] * p + R[:, 1] * p) + R[:, 2] * p
+    return A[:, None] * R, A * (p - Rp) + b
+
+
+def draw_warp(np_rng, rotation=None, intensity_scale=None, intensity_shift=None, Cv=4):
+    """the draws of the rotation and the intensity map of one kept patch from an np.random-like object, in this order:
+    np_rng.uniform(-r, r, 3) if `rotation` is not None (r: a scalar or three per-axis maxima, degrees), then
+    np_rng.uniform(1 - g, 1 + g, Cv) if `intensity_scale` (g) is not None, then np_rng.normal(0, s, Cv) if `intensity_shift` (s) is
+    not None.  An option that is None draws nothing.  Returns (angles, gain, bias), None where nothing was drawn."""
+    angles = gain = bias = None
+    if rotation is not None:
+        r = np.asarray(rotation, np.float64)
+        angles = np_rng.uniform(-r, r, 3)
+    if intensity_scale is not None:
+        gain = np_rng.uniform(1 - intensity_scale, 1 + intensity_scale, Cv)
+    if intensity_shift is not None:
+        bias = np_rng.normal(0, intensity_shift, Cv)
+    return angles, gain, bias
+
+
+def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None, warp=None):
     """generator.py:170-217 on qualification flags: yields each batch as a list of (candidate index, isometry key or None).
     The candidate order is shuffled at the first next() (rng.shuffle, if `shuffle`), then pop()ped from the end; a kept candidate
     draws its key (rng.choice over KEYS, if `permute`) when it is popped; a batch is yielded when full, or when the list is empty.
     skip_health: the caller's skip_health AND the set has truth (without truth the reference skips nothing as healthy).
     augment: None, or (np_rng, distortion_factor, flip): a kept candidate then draws draw_augment(...) just before its key
-    (generator.py:208-214), and the batch entries are (candidate index, key, (scale, flipped axes))."""
+    (generator.py:208-214), and the batch entries are (candidate index, key, (scale, flipped axes)).
+    warp: None, or (np_rng, rotation, intensity_scale, intensity_shift, Cv): a kept candidate then draws draw_warp(...) right after
+    draw_augment and before its key, and the entries gain a fourth element (angles, gain, bias)."""
+    if warp is not None and augment is None:
+        raise N3DError("epoch_order: the warp draws follow draw_augment's: warp needs augment")
     keep = kept_mask(flags, skip_health).tolist()
     order = list(range(len(keep)))
     if shuffle:
@@ -141,7 +193,8 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
         i = order.pop()
         if keep[i]:
             aug = (draw_augment(*augment),) if augment is not None else ()      # drawn before the key
-            batch.append((i, rng.choice(KEYS) if permute else None) + aug)
+            wrp = (draw_warp(*warp),) if warp is not None else ()               # ... and these between the two
+            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp)
         if len(batch) == batch_size or (not order and batch):
             yield batch
             batch = []
@@ -257,26 +310,74 @@ class VolumeSet:
         return (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == target_dtype and t.is_contiguous()
                 and tuple(t.shape) == (B, 3, P, P, P))
 
-    def patch_batch(self, refs, patch, inclusive_label=False, target_dtype=torch.float32, out=None, augment=None):
+    def _warp_descs(self, refs, P, augment, warp):
+        """the n3d_patch_wdesc table of a warped batch (patch_batch): entry i takes its flips and its scale map (A, sh) from augment[i]
+        and its matrix, interpolation order and intensity map from warp[i]; a None entry changes nothing"""
+        B = len(refs)
+        if len(warp) != B or (augment is not None and len(augment) != B):
+            raise N3DError("VolumeSet.patch_batch: one warp entry (or None) and one augmentation (or None) per ref")
+        if B > WARP_MAX_BATCH:
+            raise N3DError("VolumeSet.patch_batch: a warped batch holds at most %d patches (N3D_PATCH_WARP_MAX_BATCH)" % WARP_MAX_BATCH)
+        descs = (WarpDesc * B)()
+        for i, (v, corner, key) in enumerate(refs):
+            perm, flip = _isometry(key)
+            g = GatherDesc(PatchDesc((C.c_int32 * 3)(*[int(c) for c in corner]), (C.c_int32 * 3)(*perm),
+                                     (C.c_int32 * 3)(*[int(f) for f in flip])), int(v))
+            a = augment[i] if augment is not None and augment[i] is not None else ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0), True, None)
+            A, sh, identity, axes = a
+            aflip = [int(n in axes) for n in range(3)] if axes else [0, 0, 0]
+            matrix, order, gain, bias = warp[i] if warp[i] is not None else (None, 0, None, None)
+            if int(order) not in (0, 1):
+                raise N3DError("VolumeSet.patch_batch: the interpolation order is 0 (nearest) or 1 (linear)")
+            if matrix is not None:
+                M, off = (np.asarray(m, np.float64) for m in matrix)
+                if M.shape != (3, 3) or off.shape != (3,):
+                    raise N3DError("VolumeSet.patch_batch: a warp entry's matrix is (M (3, 3), off (3,)) as warp_transform gives them")
+                mode, k = 1, [float(m) for m in M.reshape(-1)] + [float(o) for o in off]
+            elif identity:
+                mode, k = 0, [1.0] * 3 + [0.0] * 9
+            else:
+                mode, k = 0, [float(n) for n in A] + [float(h) for h in sh] + [0.0] * 6
+            intensity = gain is not None or bias is not None
+            if intensity and self.channels > WARP_MAX_CHANNELS:
+                raise N3DError("VolumeSet.patch_batch: the intensity map supports at most %d channels (the set has %d)" % (
+                    WARP_MAX_CHANNELS, self.channels))
+            gn, bs = [1.0] * 4, [0.0] * 4
+            if gain is not None:
+                gn[:self.channels] = [float(x) for x in np.asarray(gain, np.float64).reshape(self.channels)]
+            if bias is not None:
+                bs[:self.channels] = [float(x) for x in np.asarray(bias, np.float64).reshape(self.channels)]
+            descs[i] = WarpDesc(g, (C.c_int32 * 3)(*aflip), mode, int(order), int(intensity), (C.c_double * 12)(*k),
+                                (C.c_float * 4)(*gn), (C.c_float * 4)(*bs))
+        return descs
+
+    def patch_batch(self, refs, patch, inclusive_label=False, target_dtype=torch.float32, out=None, augment=None, warp=None):
         """One batch whose patches come from any volumes of the set: refs = [(volume index, corner, isometry key or None)].
         What datastep.patch_batch makes of each patch on its own volume, bit for bit, in ONE n3d_patch_gather launch on the current
         stream.  Returns (x, t): x (B, Cv, P, P, P) fp32 in NDHWC storage, t (B, 3, P, P, P) of target_dtype (None without truth).
         out=(x, t): written in place (NDHWC x, contiguous t; t's dtype then decides the target dtype), as datastep.patch_batch.
         augment: None, or one entry per ref -- None, or (A, sh, identity, flipped axes) as resample_params gives them: the crop
         of that ref is flipped on those axes and resampled (include/n3d.h, n3d_patch_adesc) ahead of its isometry.  With some
-        entry not None the batch is ONE n3d_patch_gather_aug launch (at most 32 patches); otherwise exactly the launch above."""
+        entry not None the batch is ONE n3d_patch_gather_aug launch (at most 32 patches); otherwise exactly the launch above.
+        warp: None, or one entry per ref -- None, or (matrix or None, order, gain or None, bias or None): matrix = (M, off) as
+        warp_transform gives them (the rotation composed with the ref's scale map (A, b): it replaces the ref's (A, sh), which hold
+        b / A and not b; the flipped axes of augment still apply), order 0 / 1 = nearest / linear interpolation of the data (the truth
+        stays nearest), gain / bias = Cv factors / offsets applied to the nonzero voxels (include/n3d.h, n3d_patch_wdesc).  With
+        some entry not None the batch is ONE n3d_patch_gather_warp launch (at most 16 patches): the matrix rule for the entries
+        with a matrix, the zoom-shift rule with the entry's (A, sh) otherwise.  Otherwise the launches are exactly the ones above."""
         if target_dtype not in (torch.float32, torch.uint8):
             raise N3DError("VolumeSet.patch_batch: targets are float32 or uint8")
         B, P = len(refs), int(patch)
         if B < 1 or not self.volumes:
             raise N3DError("VolumeSet.patch_batch: need at least one patch of a non-empty set")
-        augmented = augment is not None and any(a is not None for a in augment)
+        warped = warp is not None and any(w is not None for w in warp)
+        augmented = not warped and augment is not None and any(a is not None for a in augment)
         if augmented and len(augment) != B:
             raise N3DError("VolumeSet.patch_batch: one augmentation (or None) per ref")
         if augmented and B > AUG_MAX_BATCH:
             raise N3DError("VolumeSet.patch_batch: an augmented batch holds at most %d patches (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
-        descs = ((AugDesc if augmented else GatherDesc) * B)()
-        for i, (v, corner, key) in enumerate(refs):
+        descs = self._warp_descs(refs, P, augment, warp) if warped else ((AugDesc if augmented else GatherDesc) * B)()
+        for i, (v, corner, key) in enumerate(() if warped else refs):
             perm, flip = _isometry(key)
             g = GatherDesc(PatchDesc((C.c_int32 * 3)(*[int(c) for c in corner]), (C.c_int32 * 3)(*perm),
                                      (C.c_int32 * 3)(*[int(f) for f in flip])), int(v))
@@ -308,7 +409,10 @@ class VolumeSet:
             t = torch.empty((B, 3, P, P, P), dtype=target_dtype, device=self.device) if self.has_truth else None
             xv = K.as_view(x)
         flags = (_lib.PATCH_INCLUSIVE if inclusive_label else 0) | (_lib.PATCH_T_U8 if target_dtype == torch.uint8 else 0)
-        if augmented:
+        if warped:
+            check(_lib.load().n3d_patch_gather_warp(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
+                                                    K.stream_ptr()), "n3d_patch_gather_warp")
+        elif augmented:
             check(_lib.load().n3d_patch_gather_aug(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
                                                    K.stream_ptr()), "n3d_patch_gather_aug")
         else:
@@ -333,6 +437,18 @@ class Generator:
     construction.  The resampler is scipy.ndimage.affine_transform's rule as nilearn calls it (order 0, mode "constant"),
     restated in the kernel; nilearn itself was never run against it.
 
+    Beyond the reference, all acting only with augment=True (setting one with augment=False raises N3DError) and all composed into
+    the batch's single launch (n3d_patch_gather_warp; batch_size at most 16, N3D_PATCH_WARP_MAX_BATCH):
+    augment_rotation=r (degrees; a scalar or three per-axis maxima): a rotation Rz.Ry.Rx by angles uniform in [-r, r] about the
+    patch's voxel centre, in voxel space, ahead of the scale map (rotation_matrix, warp_transform);
+    augment_interpolation="linear": the data is interpolated linearly over the eight voxels around the coordinate; the truth stays
+    nearest neighbour;
+    augment_intensity_scale=g / augment_intensity_shift=s: every modality's NONZERO voxels are multiplied by a factor uniform in
+    [1 - g, 1 + g] and shifted by a normal(0, s) offset, per patch and modality (at most 4 channels); background stays exactly 0.
+    np_rng then sees, per kept patch and after draw_augment's calls: uniform(-r, r, 3), uniform(1 - g, 1 + g, Cv), normal(0, s, Cv),
+    each only if its option is set (draw_warp), and then rng's key draw.  With all four at their defaults the generator makes the
+    calls, launches and bits it made without them.
+
     epoch_init(): one n3d_patch_qualify launch and one device -> host copy of the candidates' flag bytes.
     epoch(out=None): a generator of (x, t) device tensors (t None without truth), one n3d_patch_gather launch per batch
     (n3d_patch_gather_aug with augment) on the current stream.  out: a tuple (x, t) or a zero-argument callable returning one (e.g. trainer.input_buffers), evaluated per
@@ -341,7 +457,8 @@ class Generator:
 
     def __init__(self, indices_list, volumes, patch_shape, patch_overlap=None, batch_size=1, labels=None, augment=False, permute=False,
                  shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None,
-                 augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None):
+                 augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None, augment_rotation=None,
+                 augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None):
         if labels is not None and list(labels) != LABELS:
             raise N3DError("Generator: labels must be None or [1, 2, 4] (the three BraTS regions the kernels expand)")
         ps = [patch_shape] * 3 if isinstance(patch_shape, int) else [int(p) for p in patch_shape]
@@ -353,6 +470,24 @@ class Generator:
             raise N3DError("Generator: targets are float32 or uint8")
         if augment and int(batch_size) > AUG_MAX_BATCH:
             raise N3DError("Generator: batch_size must be 1..%d with augment=True (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
+        if augment_interpolation not in ("nearest", "linear"):
+            raise N3DError("Generator: augment_interpolation is 'nearest' or 'linear' (got %r)" % (augment_interpolation,))
+        intensity = augment_intensity_scale is not None or augment_intensity_shift is not None
+        warped = augment_rotation is not None or augment_interpolation != "nearest" or intensity
+        if warped and not augment:
+            raise N3DError("Generator: augment_rotation, augment_interpolation and augment_intensity_scale / _shift act only with "
+                           "augment=True")
+        if warped and int(batch_size) > WARP_MAX_BATCH:
+            raise N3DError("Generator: batch_size must be 1..%d with a rotation, linear interpolation or an intensity map "
+                           "(N3D_PATCH_WARP_MAX_BATCH)" % WARP_MAX_BATCH)
+        if augment_rotation is not None:
+            r = np.asarray(augment_rotation, np.float64)
+            if r.shape not in ((), (3,)) or not np.isfinite(r).all() or (r < 0).any():
+                raise N3DError("Generator: augment_rotation is a maximum angle in degrees, a scalar or one per axis (got %r)" % (
+                    augment_rotation,))
+        for name, val in (("augment_intensity_scale", augment_intensity_scale), ("augment_intensity_shift", augment_intensity_shift)):
+            if val is not None and not (np.ndim(val) == 0 and np.isfinite(val) and val >= 0):
+                raise N3DError("Generator: %s is a non-negative number (got %r)" % (name, val))
         self.affine = check_affine(affine) if augment else affine
         if augment:
             # fail here, not in the middle of an epoch with draws already consumed: the batches are made by volumes.patch_batch,
@@ -361,10 +496,22 @@ class Generator:
             if gather is None or "augment" not in inspect.signature(gather).parameters:
                 raise NotImplementedError("Generator: augment=True needs a volume set whose patch_batch(..., augment=) resamples in "
                                           "the gather (VolumeSet); %s has none" % type(volumes).__name__)
+            if warped and "warp" not in inspect.signature(gather).parameters:
+                raise NotImplementedError("Generator: augment_rotation / augment_interpolation / augment_intensity_* need a volume set "
+                                          "whose patch_batch(..., warp=) resamples in the gather (VolumeSet); %s has none"
+                                          % type(volumes).__name__)
+            channels = getattr(volumes, "channels", None)
+            if intensity and channels is not None and channels > WARP_MAX_CHANNELS:
+                raise N3DError("Generator: the intensity map supports at most %d channels (the set has %d)" % (WARP_MAX_CHANNELS, channels))
         self.augment = bool(augment)
         self.augment_flip = augment_flip
         self.augment_distortion_factor = augment_distortion_factor
         self.np_rng = np.random if np_rng is None else np_rng
+        self.warped = warped
+        self.augment_rotation = augment_rotation
+        self.augment_interpolation = augment_interpolation
+        self.augment_intensity_scale = augment_intensity_scale
+        self.augment_intensity_shift = augment_intensity_shift
         self.indices_list = list(indices_list)
         self.volumes = volumes
         self.patch_shape = ps
@@ -401,6 +548,9 @@ class Generator:
     def epoch(self, out=None):
         cand = self.candidates
         draws = (self.np_rng, self.augment_distortion_factor, self.augment_flip) if self.augment else None
+        if self.warped:
+            yield from self._warped_epoch(out, draws)
+            return
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
                                  augment=draws):
             o = out() if callable(out) else out
@@ -409,5 +559,26 @@ class Generator:
             aug = [resample_params(self.affine, self.patch, scale) + (axes,) for _, _, (scale, axes) in batch] if self.augment else None
             fit = o if self.volumes.fits(o, B, self.patch, self.target_dtype) else None
             yield self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug)
+        if self.patch_overlap:
+            self.epoch_init()
+
+    def _warped_epoch(self, out, draws):
+        """epoch() with one of the rotation / interpolation / intensity options set: every batch is one n3d_patch_gather_warp launch"""
+        cand, P = self.candidates, self.patch
+        order = 1 if self.augment_interpolation == "linear" else 0
+        wdraws = (self.np_rng, self.augment_rotation, self.augment_intensity_scale, self.augment_intensity_shift, self.volumes.channels)
+        for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
+                                 augment=draws, warp=wdraws):
+            o = out() if callable(out) else out
+            B = len(batch)
+            refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
+            aug, warp = [], []
+            for _, _, (scale, axes), (angles, gain, bias) in batch:
+                A, b, identity = resample_transform(self.affine, P, scale)
+                aug.append((A, b / A, identity, axes))
+                matrix = warp_transform(A, b, rotation_matrix(angles), P) if angles is not None else None
+                warp.append((matrix, order, gain, bias))
+            fit = o if self.volumes.fits(o, B, P, self.target_dtype) else None
+            yield self.volumes.patch_batch(refs, P, self.inclusive_label, self.target_dtype, out=fit, augment=aug, warp=warp)
         if self.patch_overlap:
             self.epoch_init()
