@@ -722,6 +722,24 @@ int n3d_stitch_add(const float* patches, int64_t sb, int64_t sc, int64_t sv, int
 int n3d_stitch_finish(const double* sum, const int32_t* cnt, int C, int X, int Y, int Z, double* probs, uint8_t* labels, double threshold,
                       int inclusive, const float* mask_vol, int Cv, int FX, int FY, int FZ, int ox, int oy, int oz, void* stream);
 
+/* ---- the same subject-level stitch with an importance weight per covering patch (sliding-window inference with Gaussian
+ * blending) and a running fp64 weight sum in place of the count: wsum float64 (X, Y, Z), zeroed by the caller with sum.
+ * n3d_stitch_add_w: everything as n3d_stitch_add (records, the isometry solved in the kernel, the bounding-box launch, one thread
+ * per voxel, no atomics, the records of the range in table order) but the weight.  profile: DEVICE double[P], P <= 1024 (staged in
+ * LDS once per workgroup), positive and symmetric (profile[i] == profile[P-1-i]: the caller's to check).  For a covering record
+ * with patch corner c at the voxel (x, y, z), l = (x, y, z) - c on the VOLUME's grid (not the net's own index: with a symmetric
+ * profile the two differ in the order of the factors only, and the order is fixed here), operation by operation in fp64, each
+ * `*` and `+` rounded once (no fused multiply-add):
+ *   w = (profile[l0] * profile[l1]) * profile[l2];   sum[ch] = sum[ch] + w * (double)p[ch];   wsum = wsum + w
+ * A dead record (slot < 0 or >= nslots) adds w to wsum only.  A voxel no record of the range covers is not stored to.  With a
+ * profile of ones sum is bit for bit n3d_stitch_add's and wsum its count.
+ * n3d_stitch_finish_w: n3d_stitch_finish with mean = wsum > 0 ? sum / wsum : 0 in place of sum / max(cnt, 1); box placement,
+ * probs / labels, skull mask and "every output voxel written exactly once" as there. */
+int n3d_stitch_add_w(const float* patches, int64_t sb, int64_t sc, int64_t sv, int C, int P, int nslots, const n3d_stitch_entry* entries, int n,
+                     const double* profile, const int32_t* lo, const int32_t* hi, int X, int Y, int Z, double* sum, double* wsum, void* stream);
+int n3d_stitch_finish_w(const double* sum, const double* wsum, int C, int X, int Y, int Z, double* probs, uint8_t* labels, double threshold,
+                        int inclusive, const float* mask_vol, int Cv, int FX, int FY, int FZ, int ox, int oy, int oz, void* stream);
+
 /* ---- whole-image prediction (prediction.py:102-119, `fs_pred`): one forward on the full image zero-padded at the high end; no
  * patches, no stitch.  full / padded / flip / origin: HOST int32[3] each.  The image (FX, FY, FZ) sits at the low corner of the
  * padded grid (PX, PY, PZ), P >= F per axis; FX * FY * FZ < 2^31 (and PX * PY * PZ < 2^31 for the embed).  flip[a] != 0 mirrors

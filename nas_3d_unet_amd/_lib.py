@@ -250,6 +250,8 @@ PROTOTYPES = {
     "n3d_tumor_labels": (_i, [_p, _i64, C.c_double, _i, _p, _p]),
     "n3d_stitch_add": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, _p, _p, _p]),
     "n3d_stitch_finish": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, C.c_double, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "n3d_stitch_add_w": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _p, _i, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, _p, _p, _p]),
+    "n3d_stitch_finish_w": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, C.c_double, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "n3d_image_embed": (_i, [_p, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i64, _p]),
     "n3d_image_add": (_i, [_p, _i64, _i64, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i, _p]),
     "n3d_image_finish": (_i, [_p, _i64, _i64, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i, _p, _p, C.c_double, _i, _p, _i, _i, _i, _i, C.POINTER(C.c_int32), _p]),

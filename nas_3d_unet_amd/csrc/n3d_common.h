@@ -85,6 +85,17 @@ struct FastDiv {
 #endif
 };
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// a stitch chunk's bounding box [lo, hi) on the brain-wide grid, clipped to the box `dims`: its corner b0 and sizes bs inside the
+// box; false: wholly outside (n3d_stitch_add, n3d_stitch_add_w: the launch covers the clipped box and nothing else)
+static inline bool stitch_clip_box(const int32_t* lo, const int32_t* hi, const int (&dims)[3], int (&b0)[3], int (&bs)[3]) {
+  for (int a = 0; a < 3; ++a) {
+    const int l = lo[a] < 0 ? 0 : lo[a], h = hi[a] > dims[a] ? dims[a] : hi[a];
+    if (h <= l) return false;
+    b0[a] = l;
+    bs[a] = h - l;
+  }
+  return true;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Element-wise mapping over a pitched NDHWC tensor with C % 4 == 0:
@@ -158,6 +169,33 @@ __device__ __forceinline__ void entry_signal(const EntrySignal& e) {
 // "zero" of the data step and the step after it (n3d_volume_sat, the skull mask of n3d_stitch_finish): numpy's `== 0` on fp32 -- +-0 is
 // zero, NaN / inf / denormals are not (on the bit pattern: a denormal flush cannot change it)
 __device__ __forceinline__ int nonzero_f32(float f) { return (__float_as_uint(f) & 0x7fffffffu) != 0; }
+// threshold + label fusion of the three sigmoid channels (prediction.py:150-170): n3d_tumor_labels and the finishing passes of the
+// stitches (post_step.hip, blend.hip)
+__device__ __forceinline__ int fuse_labels(double p0, double p1, double p2, double thr, int inclusive) {
+  const bool a = p0 >= thr, b = p1 >= thr, c = p2 >= thr;
+  if (inclusive) return c ? 4 : (a ? 1 : (b ? 2 : 0));          // later assignments win: WT(2), then TC(1), then ET(4)
+  // channels vote; two votes are settled by the larger probability, the earlier channel on equality (np.argmax)
+  int t = (a && b) ? (p0 >= p1 ? 1 : 2) : (a ? 1 : 0) + (b ? 2 : 0);
+  if (c) t = t == 1 ? (p0 >= p2 ? 1 : 4) : (t == 2 ? (p1 >= p2 ? 2 : 4) : t + 4);
+  return t;
+}
+// the channels of a stitch (registers, not a runtime-indexed array: 1 <= C <= 4)
+#define N3D_EACH_CHANNEL(c, C) _Pragma("unroll") for (int c = 0; c < 4; ++c) if (c < (C))
+// A stitch entry's patch was gathered as q[i] = x[s(i)], s_a = i[perm[a]] or P-1-i[perm[a]]; the voxel of q's prediction that
+// comes back at the local coordinates l = s: i[perm[a]] = l[a] or P-1-l[a], as (i0 * P + i1) * P + i2.  A perm that is none
+// leaves an index at 0, never outside.
+__device__ __forceinline__ int64_t stitch_entry_voxel(const n3d_patch_desc& d, const int (&l)[3], int P) {
+  int i0 = 0, i1 = 0, i2 = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int s = d.flip[a] ? P - 1 - l[a] : l[a];
+    const int pa = d.perm[a];
+    i0 = pa == 0 ? s : i0;
+    i1 = pa == 1 ? s : i1;
+    i2 = pa == 2 ? s : i2;
+  }
+  return ((int64_t)i0 * P + i1) * P + i2;
+}
 // Kernels of the dependent chain raise their waves' issue priority (s_setprio 0..3, 0 = the reset value): the weight-gradient
 // kernels, which only ever run beside the chain on the side streams, stay at 0, so where both have waves on a SIMD the chain's
 // instructions go first.  No effect when a kernel has the chip to itself.

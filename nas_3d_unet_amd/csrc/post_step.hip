@@ -33,25 +33,13 @@ __global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ p
   (void)inv;
 }
 
-// threshold + label fusion of the three sigmoid channels (prediction.py:150-170)
-__device__ __forceinline__ int fuse_labels(double p0, double p1, double p2, double thr, int inclusive) {
-  const bool a = p0 >= thr, b = p1 >= thr, c = p2 >= thr;
-  if (inclusive) return c ? 4 : (a ? 1 : (b ? 2 : 0));          // later assignments win: WT(2), then TC(1), then ET(4)
-  // channels vote; two votes are settled by the larger probability, the earlier channel on equality (np.argmax)
-  int t = (a && b) ? (p0 >= p1 ? 1 : 2) : (a ? 1 : 0) + (b ? 2 : 0);
-  if (c) t = t == 1 ? (p0 >= p2 ? 1 : 4) : (t == 2 ? (p1 >= p2 ? 2 : 4) : t + 4);
-  return t;
-}
-
+// threshold + label fusion of the three sigmoid channels (prediction.py:150-170): fuse_labels, n3d_common.h
 __global__ __launch_bounds__(256) void tumor_labels_kernel(const double* __restrict__ pred, int64_t N, double thr, int inclusive,
                                                            uint8_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   out[i] = (uint8_t)fuse_labels(pred[i], pred[N + i], pred[2 * N + i], thr, inclusive);
 }
-
-// (registers, not a runtime-indexed array: 1 <= C <= 4)
-#define N3D_EACH_CHANNEL(c, C) _Pragma("unroll") for (int c = 0; c < 4; ++c) if (c < (C))
 
 // Subject-level stitching, chunk by chunk (predict.SubjectPredictor): the running fp64 sums and covering counts of the brain-wide
 // box live in HBM between the chunks of a subject, so no patch prediction outlives its chunk.  One thread per voxel of the
@@ -81,16 +69,7 @@ __global__ __launch_bounds__(256) void stitch_add_kernel(const float* __restrict
     if ((unsigned)l[0] < (unsigned)P && (unsigned)l[1] < (unsigned)P && (unsigned)l[2] < (unsigned)P) {
       ++hits;
       if ((unsigned)t.slot < (unsigned)nslots) {
-        int i0 = 0, i1 = 0, i2 = 0;             // i[perm[a]] = l[a] or P-1-l[a]; a perm that is none leaves an index at 0, never outside
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const int s = t.d.flip[a] ? P - 1 - l[a] : l[a];
-          const int pa = t.d.perm[a];
-          i0 = pa == 0 ? s : i0;
-          i1 = pa == 1 ? s : i1;
-          i2 = pa == 2 ? s : i2;
-        }
-        const float* p = patches + t.slot * sb + (((int64_t)i0 * P + i1) * P + i2) * sv;
+        const float* p = patches + t.slot * sb + stitch_entry_voxel(t.d, l, P) * sv;
         N3D_EACH_CHANNEL(c, C) acc[c] += (double)p[c * sc];
       }
     }
@@ -248,12 +227,7 @@ extern "C" int n3d_stitch_add(const float* patches, int64_t sb, int64_t sc, int6
   // the chunk's bounding box [lo, hi) on the brain-wide grid, clipped to the box here: the launch covers it and nothing else
   const int dims[3] = {X, Y, Z};
   int b0[3], bs[3];
-  for (int a = 0; a < 3; ++a) {
-    const int l = lo[a] < 0 ? 0 : lo[a], h = hi[a] > dims[a] ? dims[a] : hi[a];
-    if (h <= l) return N3D_OK;     // wholly outside the box: nothing to add
-    b0[a] = l;
-    bs[a] = h - l;
-  }
+  if (!stitch_clip_box(lo, hi, dims, b0, bs)) return N3D_OK;     // wholly outside the box: nothing to add
   const uint32_t nvox = (uint32_t)((int64_t)bs[0] * bs[1] * bs[2]);
   N3D_LAUNCH(stitch_add_kernel, dim3((unsigned)cdiv(nvox, 256)), dim3(256), 0, (hipStream_t)stream, patches, sb, sc, sv, C, P, nslots, entries, n,
              X, Y, Z, b0[0], b0[1], b0[2], nvox, FastDiv((uint32_t)bs[2]), FastDiv((uint32_t)bs[1] * bs[2]), sum, cnt);

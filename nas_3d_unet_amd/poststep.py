@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -72,12 +73,34 @@ def stitch_buffers(channels, box_shape, device):
             torch.zeros((X, Y, Z), dtype=torch.int32, device=device))
 
 
-def _running(sum_, cnt):
+def _running(sum_, cnt, cover=torch.int32, what="int32 (X, Y, Z) count"):
     if not (isinstance(sum_, torch.Tensor) and sum_.is_cuda and sum_.dtype == torch.float64 and sum_.dim() == 4 and sum_.is_contiguous()
-            and isinstance(cnt, torch.Tensor) and cnt.device == sum_.device and cnt.dtype == torch.int32 and cnt.is_contiguous()
+            and isinstance(cnt, torch.Tensor) and cnt.device == sum_.device and cnt.dtype == cover and cnt.is_contiguous()
             and tuple(cnt.shape) == tuple(sum_.shape[1:])):
-        raise N3DError("stitch: running buffers are a contiguous float64 (C, X, Y, Z) sum and int32 (X, Y, Z) count on one HIP device")
+        raise N3DError("stitch: running buffers are a contiguous float64 (C, X, Y, Z) sum and %s on one HIP device" % what)
     return tuple(int(v) for v in sum_.shape)
+
+
+def _add_args(name, patches, table, first, count, lo, hi, sum_, Cc):
+    """what n3d_stitch_add and n3d_stitch_add_w share -> (the patch tensor the pointer is into, for the caller to hold through the
+    launch; P; the leading arguments patches .. n; (lo, hi))"""
+    es = C.sizeof(StitchEntry)
+    if not (isinstance(table, torch.Tensor) and table.dtype == torch.uint8 and table.device == sum_.device and table.is_contiguous()
+            and first >= 0 and count >= 1 and (first + count) * es <= table.numel()):
+        raise N3DError("%s: records [%d, %d) are not in the entry table" % (name, first, first + count))
+    if isinstance(patches, tuple):
+        pp, (sb, sc, sv), B, P = None, (0, 0, 0), 0, int(patches[1])
+    else:
+        if not (isinstance(patches, torch.Tensor) and patches.device == sum_.device and patches.dtype == torch.float32 and patches.dim() == 5
+                and patches.shape[1] == Cc and patches.shape[2] == patches.shape[3] == patches.shape[4]):
+            raise N3DError("%s: patches must be a (B, %d, P, P, P) fp32 tensor on the buffers' device" % (name, Cc))
+        st = K._bcv_strides(patches)
+        if st is None:
+            patches = patches.contiguous()
+            st = K._bcv_strides(patches)
+        pp, (sb, sc, sv), B, P = K.ptr(patches), st, int(patches.shape[0]), int(patches.shape[2])
+    head = (pp, sb, sc, sv, Cc, P, B, table.data_ptr() + first * es, int(count))
+    return patches, P, head, ((C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]))
 
 
 def stitch_add(patches, table, first, count, lo, hi, sum_, cnt):
@@ -85,23 +108,24 @@ def stitch_add(patches, table, first, count, lo, hi, sum_, cnt):
     (B, C, P, P, P) fp32 predictions in any layout the ops produce, or (None, P) when every record of the range is dead; lo / hi:
     the bounding box [lo, hi) of those records' patches on the brain-wide grid (the launch covers it, clipped to the box)."""
     Cc, X, Y, Z = _running(sum_, cnt)
-    es = C.sizeof(StitchEntry)
-    if not (isinstance(table, torch.Tensor) and table.dtype == torch.uint8 and table.device == sum_.device and table.is_contiguous()
-            and first >= 0 and count >= 1 and (first + count) * es <= table.numel()):
-        raise N3DError("stitch_add: records [%d, %d) are not in the entry table" % (first, first + count))
-    if isinstance(patches, tuple):
-        pp, (sb, sc, sv), B, P = None, (0, 0, 0), 0, int(patches[1])
-    else:
-        if not (isinstance(patches, torch.Tensor) and patches.device == sum_.device and patches.dtype == torch.float32 and patches.dim() == 5
-                and patches.shape[1] == Cc and patches.shape[2] == patches.shape[3] == patches.shape[4]):
-            raise N3DError("stitch_add: patches must be a (B, %d, P, P, P) fp32 tensor on the buffers' device" % Cc)
-        st = K._bcv_strides(patches)
-        if st is None:
-            patches = patches.contiguous()
-            st = K._bcv_strides(patches)
-        pp, (sb, sc, sv), B, P = K.ptr(patches), st, int(patches.shape[0]), int(patches.shape[2])
-    check(_lib.load().n3d_stitch_add(pp, sb, sc, sv, Cc, P, B, table.data_ptr() + first * es, int(count), (C.c_int32 * 3)(*[int(v) for v in lo]),
-                                     (C.c_int32 * 3)(*[int(v) for v in hi]), X, Y, Z, K.ptr(sum_), K.ptr(cnt), K.stream_ptr()), "n3d_stitch_add")
+    patches, _, head, box = _add_args("stitch_add", patches, table, first, count, lo, hi, sum_, Cc)
+    check(_lib.load().n3d_stitch_add(*head, *box, X, Y, Z, K.ptr(sum_), K.ptr(cnt), K.stream_ptr()), "n3d_stitch_add")
+
+
+def _finish_args(name, sum_, X, Y, Z, full_shape, want_probs, want_labels, mask_vol):
+    """what n3d_stitch_finish and n3d_stitch_finish_w share: ((FX, FY, FZ), Cv, probs, labels), the outputs freshly allocated"""
+    if not (want_probs or want_labels):
+        raise N3DError("%s: neither probabilities nor labels asked for" % name)
+    full = tuple(int(v) for v in (full_shape if full_shape is not None else (X, Y, Z)))
+    Cv = 0
+    if mask_vol is not None:
+        if not (isinstance(mask_vol, torch.Tensor) and mask_vol.device == sum_.device and mask_vol.dtype == torch.float32 and mask_vol.dim() == 4
+                and mask_vol.is_contiguous() and tuple(mask_vol.shape[1:]) == (X, Y, Z)):
+            raise N3DError("%s: mask_vol must be the subject's contiguous (Cv, %d, %d, %d) fp32 box on the buffers' device" % (name, X, Y, Z))
+        Cv = int(mask_vol.shape[0])
+    probs = torch.empty((int(sum_.shape[0]),) + full, dtype=torch.float64, device=sum_.device) if want_probs else None
+    labels = torch.empty(full, dtype=torch.uint8, device=sum_.device) if want_labels else None
+    return full, Cv, probs, labels
 
 
 def stitch_finish(sum_, cnt, full_shape=None, origin=(0, 0, 0), want_probs=True, want_labels=True, threshold=0.5, inclusive_label=False,
@@ -110,20 +134,76 @@ def stitch_finish(sum_, cnt, full_shape=None, origin=(0, 0, 0), want_probs=True,
     None): the mean sum / max(cnt, 1) of the box placed at `origin`, and / or tumor_labels of that mean; mask_vol: the subject's
     (Cv, X, Y, Z) fp32 box -- labels are 0 where all of its channels are (the skull mask, prediction.py:83-96)."""
     Cc, X, Y, Z = _running(sum_, cnt)
-    if not (want_probs or want_labels):
-        raise N3DError("stitch_finish: neither probabilities nor labels asked for")
-    FX, FY, FZ = (int(v) for v in (full_shape if full_shape is not None else (X, Y, Z)))
-    Cv = 0
-    if mask_vol is not None:
-        if not (isinstance(mask_vol, torch.Tensor) and mask_vol.device == sum_.device and mask_vol.dtype == torch.float32 and mask_vol.dim() == 4
-                and mask_vol.is_contiguous() and tuple(mask_vol.shape[1:]) == (X, Y, Z)):
-            raise N3DError("stitch_finish: mask_vol must be the subject's contiguous (Cv, %d, %d, %d) fp32 box on the buffers' device" % (X, Y, Z))
-        Cv = int(mask_vol.shape[0])
-    probs = torch.empty((Cc, FX, FY, FZ), dtype=torch.float64, device=sum_.device) if want_probs else None
-    labels = torch.empty((FX, FY, FZ), dtype=torch.uint8, device=sum_.device) if want_labels else None
+    (FX, FY, FZ), Cv, probs, labels = _finish_args("stitch_finish", sum_, X, Y, Z, full_shape, want_probs, want_labels, mask_vol)
     check(_lib.load().n3d_stitch_finish(K.ptr(sum_), K.ptr(cnt), Cc, X, Y, Z, K.ptr(probs), K.ptr(labels), float(threshold),
                                         1 if inclusive_label else 0, K.ptr(mask_vol), Cv, FX, FY, FZ, int(origin[0]), int(origin[1]),
                                         int(origin[2]), K.stream_ptr()), "n3d_stitch_finish")
+    return labels, probs
+
+
+# ---- the same with an importance weight per covering patch (sliding-window inference with Gaussian blending): a separable
+# profile over the position inside the patch, and a running fp64 weight sum in place of the count
+def blend_profile(P, kind="gaussian", sigma_scale=0.125):
+    """the float64 (P,) profile of a patch of P voxels per axis; a patch prediction is weighted by profile[l0] * profile[l1] *
+    profile[l2] at the local voxel l.  "gaussian": exp(-0.5 * ((i - (P - 1) / 2) / (sigma_scale * P)) ** 2), not normalised (the
+    weights of nnU-Net and of MONAI's sliding_window_inference(mode="gaussian"), sigma = P / 8); "mean": ones; an array: the
+    profile itself.  Whatever comes out must be 1-D of length P, finite, strictly positive and exactly symmetric (profile[i] ==
+    profile[P-1-i]: the kernel takes the weight on the volume's grid, whatever isometry the patch was gathered with)."""
+    P = int(P)
+    if isinstance(kind, str):
+        if kind == "gaussian":
+            if not float(sigma_scale) > 0:
+                raise N3DError("blend_profile: sigma_scale must be positive, got %r" % (sigma_scale,))
+            i = np.arange(P, dtype=np.float64)
+            prof = np.exp(-0.5 * ((i - (P - 1) / 2) / (float(sigma_scale) * P)) ** 2)
+        elif kind == "mean":
+            prof = np.ones(P, dtype=np.float64)
+        else:
+            raise N3DError("blend_profile: unknown kind %r (\"gaussian\", \"mean\" or an array of %d weights)" % (kind, P))
+    else:
+        try:
+            prof = np.array(kind, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise N3DError("blend_profile: not a profile: %s" % e)
+    if prof.ndim != 1 or len(prof) != P:
+        raise N3DError("blend_profile: the profile of a patch of %d is 1-D of length %d, got shape %s" % (P, P, prof.shape))
+    if not (np.isfinite(prof).all() and (prof > 0).all()):
+        raise N3DError("blend_profile: the weights must be finite and strictly positive")
+    if not np.array_equal(prof, prof[::-1]):
+        raise N3DError("blend_profile: the profile must be exactly symmetric (profile[i] == profile[P-1-i])")
+    return prof
+
+
+def stitch_buffers_w(channels, box_shape, device):
+    """the zeroed running buffers of one subject: (sum float64 (C, X, Y, Z), wsum float64 (X, Y, Z))"""
+    X, Y, Z = (int(v) for v in box_shape)
+    return (torch.zeros((int(channels), X, Y, Z), dtype=torch.float64, device=device),
+            torch.zeros((X, Y, Z), dtype=torch.float64, device=device))
+
+
+def _running_w(sum_, wsum):
+    return _running(sum_, wsum, torch.float64, "float64 (X, Y, Z) weight sum")
+
+
+def stitch_add_w(patches, table, first, count, lo, hi, profile_dev, sum_, wsum):
+    """stitch_add with the weight profile[l0] * profile[l1] * profile[l2] per covering record (n3d_stitch_add_w).  profile_dev: a
+    blend_profile on the buffers' device, float64 (P,)."""
+    Cc, X, Y, Z = _running_w(sum_, wsum)
+    patches, P, head, box = _add_args("stitch_add_w", patches, table, first, count, lo, hi, sum_, Cc)
+    if not (isinstance(profile_dev, torch.Tensor) and profile_dev.device == sum_.device and profile_dev.dtype == torch.float64
+            and profile_dev.is_contiguous() and tuple(profile_dev.shape) == (P,)):
+        raise N3DError("stitch_add_w: the profile must be a contiguous float64 (%d,) tensor on the buffers' device" % P)
+    check(_lib.load().n3d_stitch_add_w(*head, K.ptr(profile_dev), *box, X, Y, Z, K.ptr(sum_), K.ptr(wsum), K.stream_ptr()), "n3d_stitch_add_w")
+
+
+def stitch_finish_w(sum_, wsum, full_shape=None, origin=(0, 0, 0), want_probs=True, want_labels=True, threshold=0.5,
+                    inclusive_label=False, mask_vol=None):
+    """stitch_finish on the weighted buffers (n3d_stitch_finish_w): the mean is sum / wsum where wsum > 0, else 0"""
+    Cc, X, Y, Z = _running_w(sum_, wsum)
+    (FX, FY, FZ), Cv, probs, labels = _finish_args("stitch_finish_w", sum_, X, Y, Z, full_shape, want_probs, want_labels, mask_vol)
+    check(_lib.load().n3d_stitch_finish_w(K.ptr(sum_), K.ptr(wsum), Cc, X, Y, Z, K.ptr(probs), K.ptr(labels), float(threshold),
+                                          1 if inclusive_label else 0, K.ptr(mask_vol), Cv, FX, FY, FZ, int(origin[0]), int(origin[1]),
+                                          int(origin[2]), K.stream_ptr()), "n3d_stitch_finish_w")
     return labels, probs
 
 

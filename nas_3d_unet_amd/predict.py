@@ -6,6 +6,8 @@ are n3d_patch_batch, the net's own ops, n3d_stitch and n3d_tumor_labels.
 SubjectPredictor is the subject-level pass (prediction.py:64-170) over a generator.VolumeSet: empty patches never reach the net
 (n3d_patch_qualify), the forward is one captured graph replayed per chunk, chunks are stitched as they come (n3d_stitch_add, which
 also brings the prediction of an isometry of the patch back) and one pass fuses mean, labels and skull mask (n3d_stitch_finish).
+blend="gaussian" weights a patch prediction by the position inside the patch (n3d_stitch_add_w / n3d_stitch_finish_w), and
+EnsemblePredictor lets several SubjectPredictors add into the same running buffers.
 
 ImagePredictor is the reference's other mode (prediction.py:102-119, predict(no_patch=True)): ONE forward per subject on the whole
 image zero-padded at the high end (n3d_image_embed), cropped, averaged over flips and fused into labels in one pass
@@ -251,7 +253,8 @@ class SubjectPredictor(_ForwardHost):
     subject whatever its box -- and n3d_stitch_add adds the chunk to the subject's running fp64 sums, inverting each entry's
     isometry on the way.  n3d_stitch_finish then writes the labels (skull mask included) and, only if asked for, the fp64 image.
     keys: isometry keys of datastep.generate_permutation_keys() (None: the identity); the prediction is the mean over every
-    (corner, key) patch, for a net trained with `permute`.
+    (corner, key) patch, for a net trained with `permute`.  blend: "mean" (that mean; the default), "gaussian" or an array of `patch`
+    weights (poststep.blend_profile) -- the weighted mean, same plan, same forward, n3d_stitch_add_w / n3d_stitch_finish_w.
 
     stats: entries / live / chunks of the last subject; captures / replays / forwards since the predictor was made."""
     _what = "SubjectPredictor"
@@ -261,6 +264,7 @@ class SubjectPredictor(_ForwardHost):
         if not 1 <= self.batch <= 64:
             raise N3DError("SubjectPredictor: batch must be 1..64 (N3D_PATCH_MAX_BATCH)")
         self._init_forward(model, graph, _net, _padded)
+        self._profiles = _Profiles()
         self.stats = types.SimpleNamespace(entries=0, live=0, chunks=0, captures=0, replays=0, forwards=0)
 
     def _prepare(self, volumes):
@@ -272,43 +276,133 @@ class SubjectPredictor(_ForwardHost):
         B, P = self.batch, self.patch
         self._make_forward(device, K.empty_ndhwc(B, volumes.channels, P, P, P, device, torch.float32).zero_(), sig)
 
-    # -- one subject ------------------------------------------------------------------------------
+    # -- one subject: plan (plan_entries), accumulate into running buffers, finish (finish_subject) ----------------------------
+    def _accumulate(self, volumes, sub, profile, bufs):
+        """this predictor's share of a subject: the live entries of `sub` go through the net `batch` at a time and every chunk is
+        added to the running buffers -- `bufs`, or fresh ones when it is None (made at the first chunk, which tells the head's
+        channel count; no live entry: None comes back).  profile None: (sum, cnt) and n3d_stitch_add; a device profile: (sum,
+        wsum) and n3d_stitch_add_w.  Call inside _eval_mode(), after _prepare()."""
+        index, P, B, corners, keys = sub.index, self.patch, self.batch, sub.corners, sub.keys
+        plan = plan_subject(sub.dead, len(keys), B)
+        table = poststep.entry_table([(corners[c], sub.isos[k], s) for c, k, s in zip(plan.corner, plan.key, plan.slot)], volumes.device)
+        if volumes.has_truth and self._t is None:
+            self._t = torch.empty((B, 3, P, P, P), dtype=torch.uint8, device=volumes.device)   # (the gather's labels: not used)
+        for ch in plan.chunks:
+            volumes.patch_batch([(index, corners[plan.corner[e]], keys[plan.key[e]]) for e in ch.refs], P, out=(self._x, self._t))
+            y = self._forward()
+            if bufs is None:
+                bufs = (poststep.stitch_buffers if profile is None else poststep.stitch_buffers_w)(int(y.shape[1]), sub.box, volumes.device)
+            cs = corners[plan.corner[ch.first:ch.last]]
+            if profile is None:
+                poststep.stitch_add(y, table, ch.first, ch.last - ch.first, cs.min(axis=0), cs.max(axis=0) + P, *bufs)
+            else:
+                poststep.stitch_add_w(y, table, ch.first, ch.last - ch.first, cs.min(axis=0), cs.max(axis=0) + P, profile, *bufs)
+        self.stats.entries, self.stats.live, self.stats.chunks = len(plan.slot), int((plan.slot >= 0).sum()), len(plan.chunks)
+        return bufs
+
     def predict(self, volumes, index, overlap=None, both_ps=False, keys=(None,), full_shape=None, origin=(0, 0, 0), threshold=0.5,
-                inclusive_label=True, skull_mask=True, want_probs=False):
-        index, P, B = int(index), self.patch, self.batch
-        if not 0 <= index < len(volumes):
-            raise N3DError("SubjectPredictor: volume index %d outside the set of %d" % (index, len(volumes)))
-        keys = list(keys)
-        if not keys:
-            raise N3DError("SubjectPredictor: need at least one isometry key (None: the identity)")
-        isos = [poststep.IDENTITY if k is None else datastep.isometry_of_key(k) for k in keys]
-        box = tuple(volumes.box(index))
-        corners = patching(box, (P, P, P), overlap, both_ps)
+                inclusive_label=True, skull_mask=True, want_probs=False, blend="mean", sigma_scale=0.125):
+        """blend: "mean" (every covering patch counts the same: the reference's stitch), "gaussian" or a length-`patch` array
+        (poststep.blend_profile: a patch prediction is weighted by its position inside the patch; sigma_scale: the Gaussian's)."""
+        sub = plan_entries(self._what, volumes, index, self.patch, overlap, both_ps, keys)
+        profile = self._profiles.on_device(self.patch, blend, sigma_scale, volumes.device)
         with self._eval_mode():
             self._prepare(volumes)
-            # the subject's one host sync: which corners are dead (bit 0 clear: every modality zero)
-            flags = volumes.qualify([index] * len(corners), corners, P).cpu().numpy()
-            plan = plan_subject((flags & 1) == 0, len(keys), B)
-            n = len(plan.slot)
-            table = poststep.entry_table([(corners[c], isos[k], s) for c, k, s in zip(plan.corner, plan.key, plan.slot)], volumes.device)
-            if volumes.has_truth and self._t is None:
-                self._t = torch.empty((B, 3, P, P, P), dtype=torch.uint8, device=volumes.device)   # (the gather's labels: not used)
-            n_out = None
-            sum_ = cnt = None
-            for ch in plan.chunks:
-                volumes.patch_batch([(index, corners[plan.corner[e]], keys[plan.key[e]]) for e in ch.refs], P, out=(self._x, self._t))
-                y = self._forward()
-                if sum_ is None:
-                    n_out = int(y.shape[1])
-                    sum_, cnt = poststep.stitch_buffers(n_out, box, volumes.device)
-                cs = corners[plan.corner[ch.first:ch.last]]
-                poststep.stitch_add(y, table, ch.first, ch.last - ch.first, cs.min(axis=0), cs.max(axis=0) + P, sum_, cnt)
-            if sum_ is None:
-                # no live patch: the prediction is 0 everywhere (the head's channel count is then the net's to tell)
-                sum_, cnt = poststep.stitch_buffers(int(self._the_net().last_conv[0].conv.weight.shape[0]), box, volumes.device)
-            self.stats.entries, self.stats.live, self.stats.chunks = n, int((plan.slot >= 0).sum()), len(plan.chunks)
-        return poststep.stitch_finish(sum_, cnt, full_shape, origin, want_probs, True, threshold, inclusive_label,
-                                      volumes.volumes[index] if skull_mask else None)
+            sub = qualify_entries(volumes, sub, self.patch)
+            bufs = self._accumulate(volumes, sub, profile, None)
+        return finish_subject(self, volumes, sub, profile, bufs, full_shape, origin, threshold, inclusive_label, skull_mask, want_probs)
+
+
+# the entries of one subject before they are chunked: the corner list, the key list with its isometries, one dead flag per corner
+SubjectEntries = collections.namedtuple("SubjectEntries", "index box corners keys isos dead")
+
+
+def plan_entries(what, volumes, index, P, overlap, both_ps, keys):
+    """the corner list and key list of subject `index` (host work only; `dead` is qualify_entries' to fill in)"""
+    index = int(index)
+    if not 0 <= index < len(volumes):
+        raise N3DError("%s: volume index %d outside the set of %d" % (what, index, len(volumes)))
+    keys = list(keys)
+    if not keys:
+        raise N3DError("%s: need at least one isometry key (None: the identity)" % what)
+    isos = [poststep.IDENTITY if k is None else datastep.isometry_of_key(k) for k in keys]
+    box = tuple(volumes.box(index))
+    return SubjectEntries(index, box, patching(box, (P, P, P), overlap, both_ps), keys, isos, None)
+
+
+def qualify_entries(volumes, sub, P):
+    """the subject's one host sync: which corners are dead (bit 0 of n3d_patch_qualify's flags clear: every modality zero) -- one
+    launch and one read of its flag bytes"""
+    flags = volumes.qualify([sub.index] * len(sub.corners), sub.corners, P).cpu().numpy()
+    return sub._replace(dead=(flags & 1) == 0)
+
+
+def finish_subject(member, volumes, sub, profile, bufs, full_shape, origin, threshold, inclusive_label, skull_mask, want_probs):
+    """the one finishing pass over the running buffers -> (labels, probs or None)"""
+    if bufs is None:
+        # no live patch: the prediction is 0 everywhere (the head's channel count is then the net's to tell)
+        n_out = int(member._the_net().last_conv[0].conv.weight.shape[0])
+        bufs = (poststep.stitch_buffers if profile is None else poststep.stitch_buffers_w)(n_out, sub.box, volumes.device)
+    finish = poststep.stitch_finish if profile is None else poststep.stitch_finish_w
+    return finish(*bufs, full_shape, origin, want_probs, True, threshold, inclusive_label, volumes.volumes[sub.index] if skull_mask else None)
+
+
+class _Profiles:
+    """the blend profiles a predictor has used, on the device: uploaded once per profile and kept"""
+
+    def __init__(self):
+        self._dev = {}
+
+    def on_device(self, P, blend, sigma_scale, device):
+        """None for "mean" (the unweighted kernels), else the float64 (P,) device tensor of poststep.blend_profile"""
+        if isinstance(blend, str) and blend == "mean":
+            return None
+        prof = poststep.blend_profile(P, blend, sigma_scale)       # (an unknown name raises here)
+        key = (torch.device(device), prof.tobytes())
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(prof).to(device)
+        return self._dev[key]
+
+
+class EnsemblePredictor:
+    """Several SubjectPredictors -- the models of the cross-validation folds, say (Trainer.predictor of several trainers) --
+    averaged in the same running buffers: the prediction is the (weighted) mean over every (member, corner, key) patch.
+
+    predict(volumes, index, ...) takes SubjectPredictor.predict's keywords and returns what it returns.  The subject's entry list
+    is planned once -- one qualification launch and one host sync for all members -- then member 0 adds all its chunks in list
+    order, then member 1 into the same buffers, and so on (each with its own `batch` and captured forward), and ONE finishing
+    pass divides.  A dead patch counts as covering once per member.  EnsemblePredictor([sp]) is sp, bit for bit.
+
+    stats: members; entries / live (per member) and qualifies (qualification syncs) of the last subject."""
+    _what = "EnsemblePredictor"
+
+    def __init__(self, members):
+        members = list(members)
+        if not members or not all(isinstance(m, SubjectPredictor) for m in members):
+            raise N3DError("EnsemblePredictor: members must be a non-empty list of SubjectPredictors")
+        if len({m.patch for m in members}) != 1:
+            raise N3DError("EnsemblePredictor: the members must share one patch size, got %s" % ([m.patch for m in members],))
+        self.members, self.patch = members, members[0].patch
+        self._profiles = _Profiles()
+        self.stats = types.SimpleNamespace(members=len(members), entries=0, live=0, qualifies=0)
+
+    def predict(self, volumes, index, overlap=None, both_ps=False, keys=(None,), full_shape=None, origin=(0, 0, 0), threshold=0.5,
+                inclusive_label=True, skull_mask=True, want_probs=False, blend="mean", sigma_scale=0.125):
+        sub = plan_entries(self._what, volumes, index, self.patch, overlap, both_ps, keys)
+        profile = self._profiles.on_device(self.patch, blend, sigma_scale, volumes.device)
+        for m in self.members:
+            m._device_for(volumes)            # every member on the volumes' device, before anything runs
+        bufs, self.stats.qualifies = None, 0
+        for m in self.members:
+            with m._eval_mode():
+                m._prepare(volumes)
+                if sub.dead is None:
+                    sub = qualify_entries(volumes, sub, self.patch)
+                    self.stats.qualifies += 1
+                bufs = m._accumulate(volumes, sub, profile, bufs)
+        self.stats.entries, self.stats.live = self.members[0].stats.entries, self.members[0].stats.live
+        return finish_subject(self.members[0], volumes, sub, profile, bufs, full_shape, origin, threshold, inclusive_label, skull_mask,
+                              want_probs)
 
 
 # ---- whole-image inference ---------------------------------------------------------------------------------------------------
