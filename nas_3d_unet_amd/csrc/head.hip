@@ -625,6 +625,10 @@ static int head_bwd_run(const n3d_head* h, const char* what, const float* dp, in
                         void* stream) {
   N3D_CHECK_ARG(dx && dxld >= (h->node_c ? h->node_c : h->Ci) && dxld % 4 == 0 && (!h->node_c || h->dx_node_stride % 4 == 0), "%s: bad dx", what);
   N3D_CHECK_ARG(dx_dtype == N3D_F32 || dx_dtype == N3D_BF16, "%s: unknown dx dtype", what);
+  // (the kernel stores a channel quad per st4: 16 bytes, 8 in bf16 -- the alignment check_head asks of x)
+  const bool dx_quad = reinterpret_cast<uintptr_t>(dx) % (4 * (dx_dtype == N3D_BF16 ? 2 : 4)) == 0;
+  if (h->node_c) N3D_CHECK_ARG(dx_quad, "%s: node-planar dx needs ld >= node_c, ld %% 4 == 0, quad-aligned base and node stride", what);
+  else N3D_CHECK_ARG(dx_quad, "%s: dx needs ld %% 4 == 0 and quad alignment", what);
   const bool want_w = dw || dbias;
   const int cps = (int)cdiv(h->N, HEAD_CHUNK);
   const size_t need = n3d_head_workspace_bytes(h);
