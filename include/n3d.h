@@ -334,7 +334,8 @@ typedef struct n3d_gn_fwd_term {
 } n3d_gn_fwd_term;
 int n3d_affine_act_gn2(const n3d_gn_fwd_term* t0, const n3d_gn_fwd_term* t1, int G, float eps, float* out, int64_t old_,
                        float* out1 /* NULL: out = term0 + term1 (a node); else two independent outputs (the two preprocess
-                       ops of a cell, cell.py:47-50): term0 -> out, term1 -> out1 */, int64_t old1, int B, int64_t N, int C,
+                       ops of a cell, cell.py:47-50): term0 -> out, term1 -> out1.  With N3D_ACCUMULATE and out1 set, only
+                       `out` is accumulated into; out1 is overwritten */, int64_t old1, int B, int64_t N, int C,
                        int flags /* N3D_ACCUMULATE */, void* stream);
 
 typedef struct n3d_gn_bwd_term {

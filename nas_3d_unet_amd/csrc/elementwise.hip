@@ -2720,6 +2720,8 @@ int n3d_affine_act_bwd_apply_gn2(const float* dout, int64_t dld, const float* do
   N3D_CHECK_ARG(dout && t0 && t1 && B > 0 && N > 0, "affine_act_bwd_apply_gn2: bad args");
   if (!pair_shape_ok(C, G) || t0->rows < 1 || t1->rows < 1 || t0->rows > n3d_fused_max_rows() || t1->rows > n3d_fused_max_rows())
     N3D_UNSUPPORTED("affine_act_bwd_apply_gn2: shape not supported by the pair kernel (C=%d G=%d rows=%d/%d)", C, G, t0->rows, t1->rows);
+  // (the parameter-gradient wave holds at most GNF_MAXB samples: with more it would leave its own sample out of dgamma / dbeta / ...)
+  if (B > GNF_MAXB) N3D_UNSUPPORTED("affine_act_bwd_apply_gn2: at most %d samples (B=%d); call n3d_gn_bwd_coeffs2 + n3d_affine_act_bwd_apply2", GNF_MAXB, B);
   N3D_CHECK_ARG(t0->dtype == t1->dtype, "affine_act_bwd_apply_gn2: both terms must share one storage type");
   const bool bf = t0->dtype == N3D_BF16;
   if (int e = check_vec(dout, dld, C, "bwd_apply_gn2(dout)", bf)) return e;

@@ -15,14 +15,32 @@ def group_count(c):
     return 1 if c % 16 else c // 16
 
 
+# (C, shape, B) -> (partial rows, forward route, backward route) under today's row mapping (ew_map, csrc/n3d_common.h), asserted in the
+# test so that a retuning says so: fused = n3d_affine_act_gn2, coeffs = n3d_gn_coeffs2 + n3d_affine_act2; small = the one-launch
+# n3d_affine_act_bwd_small, apply_gn2 = reduce2 + apply_gn2, apply2 = reduce2 + n3d_gn_bwd_coeffs2 + n3d_affine_act_bwd_apply2
+PAIR_ROUTES = {
+    (4, (8, 8, 16), 2): (4, "fused", "small"), (8, (4, 8, 8), 2): (2, "fused", "small"), (16, (4, 4, 8), 3): (2, "fused", "small"),
+    (32, (4, 4, 4), 2): (2, "fused", "small"), (64, (2, 2, 2), 2): (1, "fused", "small"),
+    (4, (32, 32, 32), 2): (64, "fused", "apply_gn2"),      # exactly n3d_fused_max_rows() rows: still the fused kernels
+    (8, (16, 32, 32), 5): (64, "coeffs", "apply2"),        # 64 rows as well; separate coefficients only because B = 5 > 4
+    (4, (32, 32, 33), 2): (66, "coeffs", "apply2"),        # > 64 partial rows
+}
+
+
 @pytest.mark.parametrize("C,shape,B,relu_b", [(4, (8, 8, 16), 2, True), (8, (4, 8, 8), 2, False), (16, (4, 4, 8), 3, True),
                                                (32, (4, 4, 4), 2, True), (64, (2, 2, 2), 2, True),
-                                               (4, (32, 32, 32), 2, True), (8, (16, 32, 32), 5, False)])  # last two: > 64 partial rows
+                                               (4, (32, 32, 32), 2, True), (8, (16, 32, 32), 5, False), (4, (32, 32, 33), 2, True)])
 def test_pair_forward_backward(C, shape, B, relu_b):
     from nas_3d_unet_amd import kernels as K
     dev = torch.device("cuda")
     rng = np.random.default_rng(C)
     G = group_count(C)
+    N = shape[0] * shape[1] * shape[2]
+    rows = K.stats_rows(N, C)
+    fused = K.pair_ok(C, G, rows, rows, B)
+    route = (rows, "fused" if fused else "coeffs",
+             "small" if K.SMALL_NODE_BACKWARD and K.small_backward_mode(B, N, C, G) else "apply_gn2" if fused else "apply2")
+    assert route == PAIR_ROUTES[(C, shape, B)], "route moved, pick a new shape: %s now takes %s" % ((C, shape, B), route)
     raws = [rng.standard_normal((B, C) + shape).astype(np.float32) * 1.5 + 0.3 for _ in range(2)]
     gam = [rng.standard_normal(C).astype(np.float32) * 0.5 + 1.0 for _ in range(2)]
     bet = [rng.standard_normal(C).astype(np.float32) * 0.2 for _ in range(2)]
