@@ -870,6 +870,92 @@ int n3d_cc_clean(const uint8_t* labels, const int32_t* full, int connectivity, i
 int n3d_cc_phases(int variant, int first, int last, const uint8_t* labels, const int32_t* full, int connectivity, int64_t min_voxels,
                   int keep_largest, int64_t et_min_voxels, void* workspace, uint8_t* out, void* stream);
 
+/* ---- Lesion-wise metrics: the BraTS 2023 scoring -- lesion-wise Dice and Hausdorff95 per region -- of a predicted label volume.
+ * The reference has no code for it; the definitions are pinned to scipy.ndimage (tests/golden/make_golden_lesion.py).
+ *   pred / truth / full / box / origin, labels and regions (0 WT, 1 TC, 2 ET): as in "Segmentation metrics".  Axes up to
+ *     N3D_LW_MAX_AXIS (surface coordinates are packed 10 bits per axis), FX * FY * FZ < 2^31.
+ * Per region, operation by operation:
+ *   Masks.  G: the truth's region mask in full-image coordinates, zero outside the box; P: the prediction's.
+ *   Dilation.  Gd = scipy.ndimage.binary_dilation(G, generate_binary_structure(3, 2), iterations=dilation), border value 0:
+ *     `dilation` times "a voxel of the image is set when it or one of its 18 neighbours (|dx| + |dy| + |dz| <= 2, no corner) was";
+ *     nothing outside the image is ever set.  0 <= dilation <= N3D_LW_MAX_DILATION; 0: Gd = G.
+ *   Lesions.  The 26-connected components of Gd.  Lesion l owns the G voxels in its component; its id is the component's id as
+ *     n3d_cc_label defines it, the smallest linear index of the DILATED component.  Lesions are listed by ascending id; a lesion's
+ *     position in that list is its rank.
+ *   Predicted components.  The 26-connected components of P.
+ *   Matching.  Component c matches lesion l iff some voxel has P-component c and Gd-component l; a component may match several
+ *     lesions and counts for each, and may match through the dilation rim alone.
+ *   Per lesion l.  gt_voxels = |G_l|; tp = |P & G_l|; pred_voxels = the summed sizes of the matched components; n_matched = their
+ *     number.  Distances: the surface (6-neighbourhood, as in "Segmentation metrics") of P restricted to the matched components
+ *     against the surface of G restricted to the lesion: D = {d2 from every voxel of one to the nearest voxel of the other}, both
+ *     directions concatenated, exact integers; n = |D|, D[k], D[min(k + 1, n - 1)] of the sorted D with k = floor((n - 1) * 0.95)
+ *     (one fp64 product) and max D.  n_matched == 0: n = 0 and the three distances 0.
+ *   False positives.  n_fp = the predicted components that match no lesion, fp_voxels = their voxels.
+ * The host folds these into the two numbers (nas_3d_unet_amd.metrics.finish_lesions).
+ *
+ * rec: DEVICE int64[N3D_LW_REC_WORDS], 8-byte aligned; the subject's one device -> host copy; n3d_lw_score clears and fills it.
+ * Per region N3D_LW_REGION_WORDS words: a header of N3D_LW_HEADER_WORDS (n_lesions, n_pred_components, n_fp, fp_voxels, overflow
+ * bits, 0, 0, 0), then N3D_LW_MAX_LESIONS rows of N3D_LW_ROW_WORDS (id, gt_voxels, tp, pred_voxels, n_matched, n, D[k], D[k + 1],
+ * max D), rows past n_lesions zero.
+ * Caps.  N3D_LW_MAX_LESIONS lesions per region; N3D_LW_MAX_SURFACE entries per region and side of the surface lists (a truth
+ * surface voxel is one entry; a prediction surface voxel is one entry per lesion its component matches, none for a false positive).
+ * Exceeding a cap sets its overflow bit and the call returns normally: N3D_LW_OVERFLOW_LESIONS leaves n_lesions (the true number)
+ * and no other word of the region; a surface bit leaves the counts and no distance (n = 0 in every row).
+ * Integer atomics only (add / min / max / or): the same inputs give the same bits.  The launch count is fixed (47) whatever the
+ * data; no kernel waits on another workgroup.
+ *
+ * n3d_lw_workspace_bytes: bytes of one allocation (28 per voxel + 6 MiB of lists) for an image shape, 0 on a bad shape; offsets
+ * (HOST int64[N3D_LW_WS_PARTS], may be NULL) receives the byte offsets of: region bits, surface bits, the dilated mask, the
+ * prediction's region mask (a byte per voxel each), parent, the prediction's component ids, the dilated truth's component ids,
+ * component sizes (int32 per voxel each), component match masks (uint64 per voxel), the surface lists, the control block.
+ * Nothing in the workspace has to be cleared. */
+#define N3D_LW_MAX_DILATION 5
+#define N3D_LW_MAX_LESIONS 64
+#define N3D_LW_MAX_SURFACE (1 << 18)
+#define N3D_LW_MAX_AXIS 1024
+#define N3D_LW_HEADER_WORDS 8
+#define N3D_LW_ROW_WORDS 9
+#define N3D_LW_REGION_WORDS (N3D_LW_HEADER_WORDS + N3D_LW_MAX_LESIONS * N3D_LW_ROW_WORDS)   /* 584 */
+#define N3D_LW_REC_WORDS (3 * N3D_LW_REGION_WORDS)                                          /* 1752 */
+#define N3D_LW_HDR_LESIONS 0
+#define N3D_LW_HDR_COMPONENTS 1
+#define N3D_LW_HDR_FP 2
+#define N3D_LW_HDR_FP_VOXELS 3
+#define N3D_LW_HDR_OVERFLOW 4
+#define N3D_LW_ROW_ID 0
+#define N3D_LW_ROW_GT 1
+#define N3D_LW_ROW_TP 2
+#define N3D_LW_ROW_PRED 3
+#define N3D_LW_ROW_MATCHED 4
+#define N3D_LW_ROW_N 5
+#define N3D_LW_ROW_DK 6
+#define N3D_LW_ROW_DK1 7
+#define N3D_LW_ROW_DMAX 8
+#define N3D_LW_OVERFLOW_LESIONS 1
+#define N3D_LW_OVERFLOW_TRUTH_SURFACE 2
+#define N3D_LW_OVERFLOW_PRED_SURFACE 4
+#define N3D_LW_WS_PARTS 11
+size_t n3d_lw_workspace_bytes(int FX, int FY, int FZ, int64_t* offsets);
+/* ONE launch: out (DEVICE uint8 (FX, FY, FZ), not mask) = 1 where the dilation of `mask != 0` (any nonzero byte) is set, 0
+ * elsewhere.  bbox: DEVICE int32[6] (lo x, y, z, hi x, y, z inclusive) holding every nonzero voxel of mask, or NULL: only the
+ * 8 x 8 x 32 tiles that meet the box grown by `iterations` are dilated (in LDS, with a halo of `iterations`), the others are
+ * written as zeros; a mask voxel outside bbox is ignored there.  iterations outside 0 .. N3D_LW_MAX_DILATION: N3D_ERR_INVALID. */
+int n3d_lw_dilate(const uint8_t* mask, const int32_t* full, const int32_t* bbox, int iterations, uint8_t* out, void* stream);
+/* 47 launches: init, the region and surface bits with the truth's boxes, then per region: the prediction's mask, its components
+ * (n3d_cc_label), the dilation, its components (n3d_cc_label), roots, ranks, matching and per-lesion counts, component sums,
+ * surface lists, distances (brute force over the lists in LDS tiles, filtered by lesion), order statistics (bisection on the
+ * value).  workspace: n3d_lw_workspace_bytes(FX, FY, FZ) bytes, 8-byte aligned. */
+int n3d_lw_score(const uint8_t* pred, const uint8_t* truth, const int32_t* full, const int32_t* box, const int32_t* origin, int dilation,
+                 void* workspace, int64_t* rec, void* stream);
+/* The phases first .. last of n3d_lw_score, for measuring them one by one: 0 init, 1 region bits, then per region r the
+ * N3D_LW_REGION_PHASES phases 2 + 11 r + (0 select, 1 label P, 2 dilate, 3 label Gd, 4 roots, 5 ranks, 6 match, 7 components,
+ * 8 surface lists, 9 distances, 10 order statistics).  A phase expects the workspace as the phases before it leave it; 0 .. k
+ * repeats. */
+#define N3D_LW_REGION_PHASES 11
+#define N3D_LW_PHASES (2 + 3 * N3D_LW_REGION_PHASES)
+int n3d_lw_phases(int first, int last, const uint8_t* pred, const uint8_t* truth, const int32_t* full, const int32_t* box,
+                  const int32_t* origin, int dilation, void* workspace, int64_t* rec, void* stream);
+
 /* ---- RCCL exchange step of data-parallel training (no reference counterpart: config.yml:54 `multi_gpus` is never read;
  * SURVEY 8(e)).  One process per GPU; the hot path's only exchange is a SUM all-reduce of the flat fp32 gradient buffer, in
  * place, stream-ordered on `stream` (a side HIP stream lets it run under the backward kernels of the next bucket).

@@ -264,6 +264,10 @@ PROTOTYPES = {
     "n3d_cc_label": (_i, [_p, C.POINTER(C.c_int32), _i, _p, _p, _p]),
     "n3d_cc_clean": (_i, [_p, C.POINTER(C.c_int32), _i, _i64, _i, _i64, _p, _p, _p]),
     "n3d_cc_phases": (_i, [_i, _i, _i, _p, C.POINTER(C.c_int32), _i, _i64, _i, _i64, _p, _p, _p]),
+    "n3d_lw_workspace_bytes": (_sz, [_i, _i, _i, C.POINTER(C.c_int64)]),
+    "n3d_lw_dilate": (_i, [_p, C.POINTER(C.c_int32), _p, _i, _p, _p]),
+    "n3d_lw_score": (_i, [_p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _p, _p, _p]),
+    "n3d_lw_phases": (_i, [_i, _i, _p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _p, _p, _p]),
     "n3d_comm_available": (_i, []),
     "n3d_comm_unique_id": (_i, [_p]),
     "n3d_comm_init": (_i, [_p, _i, _i, C.POINTER(C.c_void_p)]),

@@ -14,7 +14,13 @@ draws -- without the labels leaving the device.  The reference has no code for t
 
 score_labels enqueues four kernels' worth of work (n3d_seg_regions, n3d_seg_edt -- three launches --, n3d_seg_sample,
 n3d_seg_order) and makes ONE host sync: the copy of a 240-byte record.  Scratch is allocated once per image shape and device and
-reused across subjects.  No CPU fallback: a host tensor is an error."""
+reused across subjects.  No CPU fallback: a host tensor is an error.
+
+Lesion-wise scores (BraTS 2023; include/n3d.h, "Lesion-wise metrics"): the truth's region mask is dilated `dilation` times with the
+18-neighbourhood, the 26-connected components of the dilated mask are the lesions, and every lesion is scored against the predicted
+components that touch its dilated component; a predicted component that touches none is a false positive, a case of Dice 0 and
+HD95 `penalty_hd95`.  lesion_record enqueues n3d_lw_score's fixed 47 launches and makes ONE host sync, the copy of a 14 KB integer
+record; finish_lesions folds it in fp64 on the host."""
 from __future__ import annotations
 
 import csv
@@ -33,11 +39,23 @@ CRITERIA = ("Dice", "Sensitivity", "Specificity", "Hausdorff95")
 # the portal's column order: per criterion ET, WT, TC
 COLUMNS = ("Label",) + tuple("%s_%s" % (c, r) for c in CRITERIA for r in ("ET", "WT", "TC"))
 SUMMARY_ROWS = ("Mean", "StdDev", "Median", "25quantile", "75quantile")
+LESION_CRITERIA = ("LesionWise_Dice", "LesionWise_Hausdorff95")
+LESION_COLUMNS = tuple("%s_%s" % (c, r) for c in LESION_CRITERIA for r in ("ET", "WT", "TC"))
 
 INF = 1 << 29            # N3D_SEG_INF
 MAX_AXIS = 1024          # N3D_SEG_MAX_AXIS
 REC_WORDS, REC_ORDER, REC_BBOX = 30, 9, 21   # N3D_SEG_REC_*
 _I32_MAX = 2 ** 31 - 1
+# N3D_LW_*
+LW_MAX_DILATION, LW_MAX_LESIONS, LW_MAX_SURFACE, LW_MAX_AXIS = 5, 64, 1 << 18, 1024
+LW_HEADER_WORDS, LW_ROW_WORDS = 8, 9
+LW_REGION_WORDS = LW_HEADER_WORDS + LW_MAX_LESIONS * LW_ROW_WORDS
+LW_REC_WORDS = 3 * LW_REGION_WORDS
+LW_PHASES = 35
+LW_REGION_PHASES = ("select", "label_pred", "dilate", "label_truth", "roots", "ranks", "match", "components", "surfaces", "distances", "order")
+_LW_OVERFLOW = ((1, "N3D_LW_MAX_LESIONS = %d lesions" % LW_MAX_LESIONS),
+                (2, "N3D_LW_MAX_SURFACE = %d surface entries of the truth" % LW_MAX_SURFACE),
+                (4, "N3D_LW_MAX_SURFACE = %d surface entries of the prediction" % LW_MAX_SURFACE))
 
 
 # ---- host: pure numpy, needs neither a GPU nor the library
@@ -90,10 +108,10 @@ def row_of(label, scores):
     return row
 
 
-def summary_rows(rows):
+def summary_rows(rows, columns=COLUMNS):
     """the portal's five trailing rows over `rows`, NaN entries left out (an all-NaN column stays NaN)"""
     out = [{"Label": s} for s in SUMMARY_ROWS]
-    for col in COLUMNS[1:]:
+    for col in columns[1:]:
         v = np.array([r[col] for r in rows], dtype=np.float64)
         v = v[~np.isnan(v)]
         if v.size:
@@ -105,15 +123,75 @@ def summary_rows(rows):
     return out
 
 
-def write_csv(path, rows):
+def write_csv(path, rows, columns=COLUMNS):
     """rows (score_set's) followed by Mean, StdDev, Median, 25quantile, 75quantile: the file evaluation_plot reads (its [:-5]
-    strips exactly those five).  NaN is written as an empty field, which pandas reads back as NaN."""
-    rows = list(rows)
+    strips exactly those five).  NaN is written as an empty field, which pandas reads back as NaN.  columns: COLUMNS, or
+    COLUMNS + LESION_COLUMNS for rows of score_set(..., lesionwise=True); keys of a row that are no column are not written."""
+    rows, columns = list(rows), tuple(columns)
+    if not columns or columns[0] != "Label":
+        raise N3DError("write_csv: the first column must be Label (got %s)" % (columns[:1],))
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(COLUMNS)
-        for r in rows + summary_rows(rows):
-            w.writerow([r["Label"]] + ["" if math.isnan(r[c]) else repr(float(r[c])) for c in COLUMNS[1:]])
+        w.writerow(columns)
+        for r in rows + summary_rows(rows, columns):
+            w.writerow([r["Label"]] + ["" if math.isnan(r[c]) else repr(float(r[c])) for c in columns[1:]])
+
+
+def finish_lesions(record, min_lesion_voxels=50, penalty_hd95=374.0):
+    """record: the int64 words of n3d_lw_score (include/n3d.h) -> {region: {"lesionwise_dice", "lesionwise_hausdorff95",
+    "n_lesions", "n_kept", "n_fn", "n_fp", "fp_voxels", "lesions": [{"id", "gt_voxels", "pred_voxels", "tp", "n_matched", "dice",
+    "hausdorff95", "hausdorff100"}, ...]}}.  Lesions are listed by ascending id, all of them; the kept ones are those with
+    gt_voxels > min_lesion_voxels.  A lesion without a matched component has Dice 0 and both distances penalty_hd95.  The sums
+    run over the kept lesions in that order, one fp64 addition each; den = kept lesions + false positives; den == 0 gives Dice 1
+    and HD95 0.  An overflow bit in the record raises N3DError."""
+    if isinstance(min_lesion_voxels, bool) or int(min_lesion_voxels) != min_lesion_voxels or min_lesion_voxels < 0:
+        raise N3DError("finish_lesions: min_lesion_voxels %r: must be an integer >= 0" % (min_lesion_voxels,))
+    penalty = float(penalty_hd95)
+    if math.isnan(penalty) or penalty < 0:
+        raise N3DError("finish_lesions: penalty_hd95 %r: must be a number >= 0" % (penalty_hd95,))
+    record = np.asarray(record)
+    if record.size != LW_REC_WORDS or record.dtype.kind not in "iu":
+        raise N3DError("finish_lesions: the record must hold %d integers (got %s of %s)" % (LW_REC_WORDS, record.shape, record.dtype))
+    record = record.astype(np.int64).reshape(3, LW_REGION_WORDS)
+    out = {}
+    for r, name in enumerate(REGIONS):
+        n_lesions, _, n_fp, fp_voxels, overflow = (int(v) for v in record[r, :5])
+        for bit, what in _LW_OVERFLOW:
+            if overflow & bit:
+                raise N3DError("finish_lesions: region %s holds more than %s%s" % (
+                    name, what, " (%d)" % n_lesions if bit == 1 else ""))
+        if not 0 <= n_lesions <= LW_MAX_LESIONS:
+            raise N3DError("finish_lesions: region %s: n_lesions %d outside 0 .. %d" % (name, n_lesions, LW_MAX_LESIONS))
+        rows = record[r, LW_HEADER_WORDS:].reshape(LW_MAX_LESIONS, LW_ROW_WORDS)
+        lesions, n_kept, n_fn = [], 0, 0
+        dice_sum, hd_sum = np.float64(0.0), np.float64(0.0)
+        for row in rows[:n_lesions]:
+            lid, gt, tp, pv, nm, n, d_lo, d_hi, d_max = (int(v) for v in row)
+            if nm > 0 and n > 0:
+                dice, hd95, hd100 = _ratio(2 * tp, pv + gt), hd_from_order(n, d_lo, d_hi), float(np.sqrt(np.float64(d_max)))
+            else:
+                dice, hd95, hd100 = 0.0, penalty, penalty
+            lesions.append({"id": lid, "gt_voxels": gt, "pred_voxels": pv, "tp": tp, "n_matched": nm, "dice": dice,
+                            "hausdorff95": hd95, "hausdorff100": hd100})
+            if gt > min_lesion_voxels:
+                n_kept += 1
+                n_fn += nm == 0
+                dice_sum = dice_sum + np.float64(dice)
+                hd_sum = hd_sum + np.float64(hd95)
+        den = n_kept + n_fp
+        if den == 0:
+            lw_dice, lw_hd = 1.0, 0.0
+        else:
+            lw_dice = float(dice_sum / np.float64(den))
+            lw_hd = float((hd_sum + np.float64(penalty) * np.float64(n_fp)) / np.float64(den))
+        out[name] = {"lesionwise_dice": lw_dice, "lesionwise_hausdorff95": lw_hd, "n_lesions": n_lesions, "n_kept": n_kept,
+                     "n_fn": int(n_fn), "n_fp": n_fp, "fp_voxels": fp_voxels, "lesions": lesions}
+    return out
+
+
+def lesion_columns_of(lesion_scores):
+    """the six LESION_COLUMNS entries of a finish_lesions result"""
+    return {"%s_%s" % (c, r): lesion_scores[r][c.lower()] for c in LESION_CRITERIA for r in REGIONS}
 
 
 # ---- device
@@ -236,8 +314,92 @@ def score_labels(pred, truth, origin=None):
     return finish(rec[:9].reshape(3, 3), n, rec[REC_ORDER:REC_BBOX].reshape(3, 4))
 
 
-def score_subject(volumes, index, labels):
-    """labels (a predictor's output for volumes[index]) against volumes.truths[index] at volumes.origins[index]"""
+class _LesionWorkspace:
+    def __init__(self, lib, device, full):
+        nbytes = int(lib.n3d_lw_workspace_bytes(full[0], full[1], full[2], None))
+        if nbytes == 0:
+            raise N3DError("lesion_record: image shape %s: needs 1 <= FX * FY * FZ < 2^31" % (tuple(full),))
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+_lesion_workspaces = {}
+
+
+def _check_dilation(dilation, what):
+    if isinstance(dilation, bool) or not isinstance(dilation, (int, np.integer)) or not 0 <= dilation <= LW_MAX_DILATION:
+        raise N3DError("%s: dilation %r: must be an integer in 0 .. %d" % (what, dilation, LW_MAX_DILATION))
+    return int(dilation)
+
+
+def dilate_mask(mask, iterations=3):
+    """mask: (X, Y, Z) uint8 or bool device tensor -> uint8 (X, Y, Z), 1 where scipy.ndimage.binary_dilation(mask != 0,
+    generate_binary_structure(3, 2), iterations=iterations) is set (border value 0; 0 iterations: the mask itself as 0 / 1).
+    One launch, no host sync.  0 <= iterations <= 5."""
+    if not (isinstance(mask, torch.Tensor) and mask.dim() == 3 and mask.dtype in (torch.uint8, torch.bool) and mask.is_cuda
+            and mask.numel() > 0):
+        raise N3DError("dilate_mask: mask must be a non-empty (X, Y, Z) uint8 or bool tensor on a HIP device (got %s); there is no CPU "
+                       "fallback" % ("%s %s on %s" % (tuple(mask.shape), mask.dtype, mask.device) if isinstance(mask, torch.Tensor)
+                                     else type(mask).__name__))
+    iterations = _check_dilation(iterations, "dilate_mask")
+    full = tuple(int(s) for s in mask.shape)
+    if full[0] * full[1] * full[2] >= 2 ** 31:
+        raise N3DError("dilate_mask: mask %s: needs X * Y * Z < 2^31" % (full,))
+    src = (mask.view(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+    out = torch.empty(full, dtype=torch.uint8, device=mask.device)
+    check(_lib.load().n3d_lw_dilate(K.ptr(src), _i3(full), None, iterations, K.ptr(out), K.stream_ptr()), "n3d_lw_dilate")
+    return out
+
+
+def _lesion_setup(pred, truth, origin, dilation):
+    pred, truth, full, box, org = _geometry(pred, truth, origin, "lesion_record")
+    dilation = _check_dilation(dilation, "lesion_record")
+    if max(full) > LW_MAX_AXIS:
+        raise N3DError("lesion_record: image %s: the packed surface coordinates take axes up to %d" % (full, LW_MAX_AXIS))
+    lib = _lib.load()
+    key = (pred.device, full)
+    ws = _lesion_workspaces.get(key)
+    if ws is None:
+        _lesion_workspaces.clear()     # one shape at a time: the scratch of a full-size image is 28 bytes per voxel
+        ws = _lesion_workspaces[key] = _LesionWorkspace(lib, pred.device, full)
+    return lib, pred, truth, full, box, org, dilation, ws
+
+
+def lesion_phases(pred, truth, origin=None, dilation=3, first=0, last=LW_PHASES - 1, rec=None):
+    """the phases first .. last of n3d_lw_score (include/n3d.h, n3d_lw_phases) on the shared scratch, for timing -> the device
+    record (int64, LW_REC_WORDS)"""
+    lib, pred, truth, full, box, org, dilation, ws = _lesion_setup(pred, truth, origin, dilation)
+    if rec is None:
+        rec = torch.empty(LW_REC_WORDS, dtype=torch.int64, device=pred.device)
+    check(lib.n3d_lw_phases(int(first), int(last), K.ptr(pred), K.ptr(truth), _i3(full), _i3(box), _i3(org), dilation, K.ptr(ws.buf),
+                            K.ptr(rec), K.stream_ptr()), "n3d_lw_phases")
+    return rec
+
+
+def lesion_record(pred, truth, origin=None, dilation=3):
+    """the device work of score_lesions: -> (record int64 (LW_REC_WORDS,) numpy array as include/n3d.h lays it out, voxels of the
+    image).  The subject's one host sync is the copy of the record."""
+    lib, pred, truth, full, box, org, dilation, ws = _lesion_setup(pred, truth, origin, dilation)
+    rec = torch.empty(LW_REC_WORDS, dtype=torch.int64, device=pred.device)
+    check(lib.n3d_lw_score(K.ptr(pred), K.ptr(truth), _i3(full), _i3(box), _i3(org), dilation, K.ptr(ws.buf), K.ptr(rec), K.stream_ptr()),
+          "n3d_lw_score")
+    return rec.cpu().numpy(), full[0] * full[1] * full[2]
+
+
+def score_lesions(pred, truth, origin=None, dilation=3, min_lesion_voxels=50, penalty_hd95=374.0):
+    """pred, truth, origin as score_labels -> finish_lesions' result: the BraTS 2023 lesion-wise Dice and Hausdorff95 per region
+    with the per-lesion figures.  One host sync."""
+    if isinstance(min_lesion_voxels, bool) or int(min_lesion_voxels) != min_lesion_voxels or min_lesion_voxels < 0:
+        raise N3DError("score_lesions: min_lesion_voxels %r: must be an integer >= 0" % (min_lesion_voxels,))
+    return finish_lesions(lesion_record(pred, truth, origin, dilation)[0], min_lesion_voxels, penalty_hd95)
+
+
+def score_subject(volumes, index, labels, lesionwise=False, **lesion_kw):
+    """labels (a predictor's output for volumes[index]) against volumes.truths[index] at volumes.origins[index].  lesionwise: the
+    result also carries the six LESION_COLUMNS (score_lesions with lesion_kw: dilation, min_lesion_voxels, penalty_hd95)."""
+    if lesion_kw and not lesionwise:
+        raise N3DError("score_subject: %s given without lesionwise=True" % sorted(lesion_kw))
+    if set(lesion_kw) - {"dilation", "min_lesion_voxels", "penalty_hd95"}:
+        raise N3DError("score_subject: unknown keywords %s" % sorted(set(lesion_kw) - {"dilation", "min_lesion_voxels", "penalty_hd95"}))
     index = int(index)
     if not 0 <= index < len(volumes):
         raise N3DError("score_subject: volume index %d outside the set of %d" % (index, len(volumes)))
@@ -250,17 +412,30 @@ def score_subject(volumes, index, labels):
     shape = tuple(int(s) for s in getattr(labels, "shape", ()))
     if len(shape) != 3 or any(o + b > f for o, b, f in zip(org, box, shape)) or (origin is None and shape != box):
         raise N3DError("score_subject: labels of shape %s do not hold subject %d's box %s at %s" % (shape, index, box, org))
-    return score_labels(labels, truth, origin)
+    scores = score_labels(labels, truth, origin)
+    if lesionwise:
+        scores.update(lesion_columns_of(score_lesions(labels, truth, origin, **lesion_kw)))
+    return scores
 
 
-def score_set(predictor, volumes, indices, names=None, **predict_kw):
+def score_set(predictor, volumes, indices, names=None, lesionwise=False, dilation=3, min_lesion_voxels=50, penalty_hd95=374.0,
+              **predict_kw):
     """predictor.predict(volumes, i, **predict_kw)[0] scored per index -> rows (dicts keyed by COLUMNS; Label = names[j] or the
-    index) for write_csv"""
+    index) for write_csv.  lesionwise: the rows also carry LESION_COLUMNS (write_csv(path, rows, COLUMNS + LESION_COLUMNS)),
+    scored with dilation, min_lesion_voxels and penalty_hd95."""
     indices = list(indices)
     if names is not None and len(names) != len(indices):
         raise N3DError("score_set: %d names for %d indices" % (len(names), len(indices)))
     rows = []
     for j, i in enumerate(indices):
         labels = predictor.predict(volumes, i, **predict_kw)[0]
-        rows.append(row_of(str(names[j]) if names is not None else str(i), score_subject(volumes, i, labels)))
+        if lesionwise:
+            scores = score_subject(volumes, i, labels, lesionwise=True, dilation=dilation, min_lesion_voxels=min_lesion_voxels,
+                                   penalty_hd95=penalty_hd95)
+        else:
+            scores = score_subject(volumes, i, labels)
+        row = row_of(str(names[j]) if names is not None else str(i), scores)
+        if lesionwise:
+            row.update({c: scores[c] for c in LESION_COLUMNS})
+        rows.append(row)
     return rows
