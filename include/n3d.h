@@ -665,6 +665,64 @@ typedef struct n3d_patch_wdesc {
 int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_wdesc* descs, int B, int P, int flags,
                           float* x_out, int64_t xld, void* t_out, void* stream);
 
+/* ---- appearance augmentation of a gathered batch, in place (none of it the reference's: the four transforms of batchgenerators /
+ * nnU-Net that the BraTS recipes train with).  x: DEVICE fp32 batch (B, Cv, P, P, P) in NDHWC storage with channel pitch ld >= Cv,
+ * as n3d_patch_gather* write it; the lanes between Cv and ld are never touched.  descs: HOST array, one record per patch.
+ *
+ * The brain mask of a (patch, channel) is x != 0 on entry (-0.0 is zero, as in n3d_patch_gather_warp), taken ONCE before the first
+ * stage.  Every stage writes only masked voxels and takes its statistics over them; the background stays exactly 0.0f; a (patch,
+ * channel) without a masked voxel is left alone by contrast and gamma (n = 0: no division).  The stages run in the fixed order
+ * noise, blur, contrast, gamma, each only on the patches whose flag is set, each on the values the earlier stages left.  All
+ * arithmetic is fp64 on fp32 loads, every product, sum, quotient and library call rounded on its own in the association written;
+ * "fp32(..)" is the one rounding to fp32 where a stage stores.  v = (i * P + j) * P + k is the voxel's index in its patch.
+ *
+ *   noise     w0..w3 = Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85, ten rounds) of the
+ *             counter (v, 0, 0, 0) under the patch's key (key[0], key[1]);  u1 = ((double)w0 + 1) * 2^-32,  u2 = (double)w1 * 2^-32,
+ *             rho = sqrt(-2 * log(u1)),  th = 6.283185307179586 * u2,  z0 = rho * cos(th),  z1 = rho * sin(th);  (w2, w3) give
+ *             (z2, z3) the same way.  Channel c:  y = fp32(x + sigma * z_c).
+ *   blur      y = fp32(G * x), G * x the separable Gaussian of the channel's whole P^3 patch (background zeros take part), what
+ *             scipy.ndimage.gaussian_filter(x, sigma_c, mode="reflect", truncate=4.0) computes on fp64 input: three passes, axis 0,
+ *             1, 2, each  out[i] = sum over k = -r .. +r IN THAT ORDER of weights[c][|k|] * in[refl(i + k)]  (the first product, then
+ *             acc = acc + product), refl(i) = -i - 1 below 0 and 2 P - 1 - i from P on; the intermediates stay fp64 and the one
+ *             rounding is at the end.  radius[c] = r = int(4 sigma_c + 0.5) and weights[c][0 .. r] = exp(-0.5 / sigma_c^2 * k^2) /
+ *             (their sum over -r .. r) come from the host (numpy): the device evaluates no exp.  0 <= r <= N3D_APPEAR_MAX_RADIUS and
+ *             r <= P (one reflection suffices), else N3D_ERR_INVALID.  The result does not depend on any read / write order: the
+ *             launch writes to scratch and a second one lands the masked voxels in x.
+ *   sums      "the sum" of the terms a[v] of a (patch, channel) below is this fixed order: terms of voxels outside the mask are
+ *             +0.0; FOLD(a[0 .. 256 n)) = lane t adds a[t], a[t + 256], .. in that order onto 0.0, then the 256 lanes are folded
+ *             in halves, lane[t] = lane[t] + lane[t + s] for s = 128, 64, .. 1; each chunk of 1024 consecutive voxels (the last
+ *             padded with +0.0) gives FOLD(chunk); the sum is FOLD(the chunk results in chunk order, padded with +0.0 to a
+ *             multiple of 256).  n counts the masked voxels; lo / hi are their minimum / maximum.
+ *   contrast  n, lo, hi and m = S / n with S the sum of x;  y = fp32(min(max((x - m) * factor[c] + m, lo), hi))
+ *             (batchgenerators' augment_contrast(preserve_range=True, per_channel=True)).
+ *   gamma     n, lo, hi, m as above, sd = sqrt(sum((x - m) * (x - m)) / n);
+ *             x' = fp32(pow((x - lo) / ((hi - lo) + 1e-7), gamma_c[c]) * (hi - lo) + lo);  then m' and sd' of x' the same way and
+ *             y = fp32((x' - m') / (sd' + 1e-8) * sd + m)   (augment_gamma(retain_stats=True, per_channel=True)).
+ *
+ * How the parameters travel: each stage's share of the descriptors is repacked into that stage's own launch-argument block (the
+ * blur's half kernels, 16 x 4 x 7 doubles, are 3.5 KB of the 4 KB a launch takes); nothing is copied to the device and nothing
+ * synchronises.  A stage that no patch asks for launches nothing; with no flag set at all the call launches nothing and does not
+ * look at the scratch.  Launches otherwise: the mask 1, noise 1, blur 2, contrast 2, gamma 4.  No floating-point atomics: two
+ * runs on the same input give the same bits.  Bad arguments (B > N3D_APPEAR_MAX_BATCH, Cv > 4, a radius beyond the bounds, a
+ * parameter that is not finite, sigma or gamma below 0, a scratch that is too small) return N3D_ERR_INVALID before any launch.
+ * scratch: DEVICE, 8-byte aligned, n3d_patch_appearance_scratch(B, Cv, P) bytes (0 for arguments out of range): a mask byte per
+ * voxel, the blur's fp32 output and the chunk partials. */
+#define N3D_APPEAR_MAX_BATCH 16
+#define N3D_APPEAR_MAX_RADIUS 6
+#define N3D_APPEAR_MAX_PATCH 256
+typedef struct n3d_appear_desc {
+  int32_t noise, blur, contrast, gamma;            /* != 0: the stage acts on this patch */
+  uint32_t key[2];                                 /* noise: the Philox key */
+  double sigma;                                    /* noise */
+  int32_t radius[4];                               /* blur, per channel */
+  double weights[4][N3D_APPEAR_MAX_RADIUS + 1];    /* blur: weights[c][|k|] */
+  double factor[4];                                /* contrast */
+  double gamma_c[4];                               /* gamma */
+} n3d_appear_desc;
+int n3d_patch_appearance(void* x, int64_t ld, int B, int Cv, int P, const n3d_appear_desc* descs, void* scratch, size_t scratch_bytes,
+                         void* stream);
+size_t n3d_patch_appearance_scratch(int B, int Cv, int P);
+
 /* ---- the step before the data step (preprocess.py:77-144, create_h5:58-66): raw scanner counts to the statistics of the data
  * set and to each subject's normalised brain-wise box.  raw: DEVICE int16 (Cm, X, Y, Z) contiguous, 2-byte aligned (a modality's
  * base need not be 16-byte aligned: X * Y * Z may be odd); X * Y * Z < 2^31.  "Brain" = the voxels with raw != 0, per modality.

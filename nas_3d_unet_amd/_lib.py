@@ -121,6 +121,13 @@ class WarpDesc(C.Structure):
                 ("k", C.c_double * 12), ("gain", C.c_float * 4), ("bias", C.c_float * 4)]
 
 
+class AppearDesc(C.Structure):
+    """n3d_appear_desc (include/n3d.h)"""
+    _fields_ = [("noise", C.c_int32), ("blur", C.c_int32), ("contrast", C.c_int32), ("gamma", C.c_int32), ("key", C.c_uint32 * 2),
+                ("sigma", C.c_double), ("radius", C.c_int32 * 4), ("weights", (C.c_double * 7) * 4), ("factor", C.c_double * 4),
+                ("gamma_c", C.c_double * 4)]
+
+
 class StitchEntry(C.Structure):
     """n3d_stitch_entry (include/n3d.h)"""
     _fields_ = [("d", PatchDesc), ("slot", C.c_int32)]
@@ -242,6 +249,8 @@ PROTOTYPES = {
     "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_aug": (_i, [_p, _i, _i, C.POINTER(AugDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_warp": (_i, [_p, _i, _i, C.POINTER(WarpDesc), _i, _i, _i, _p, _i64, _p, _p]),
+    "n3d_patch_appearance": (_i, [_p, _i64, _i, _i, _i, C.POINTER(AppearDesc), _p, _sz, _p]),
+    "n3d_patch_appearance_scratch": (_sz, [_i, _i, _i]),
     "n3d_brain_scan": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "n3d_brain_sqdev_rows": (_i, [_i64]),
     "n3d_brain_sqdev": (_i, [_p, _i, _i64, _p, _p, _p, _p]),

@@ -21,8 +21,11 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
     per-modality intensity scale and shift of the brain voxels, still in ONE launch per batch (n3d_patch_gather_warp):
     rotation_matrix, warp_transform and draw_warp below are their host arithmetic and draws.
 
-Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather, n3d_patch_gather_aug and
-n3d_patch_gather_warp (include/n3d.h).
+  * augment_appearance (appearance.Appearance; not the reference's either) adds Gaussian noise, Gaussian blur, contrast and gamma of
+    the brain voxels, applied to the gathered batch in place by n3d_patch_appearance (1 to 10 launches, no host sync).
+
+Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather, n3d_patch_gather_aug,
+n3d_patch_gather_warp and n3d_patch_appearance (include/n3d.h).
 """
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib, datastep, predict, preprocess
+from . import _lib, appearance, datastep, predict, preprocess
 from . import kernels as K
 from ._lib import AugDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, WarpDesc, check
 
@@ -173,7 +176,7 @@ def draw_warp(np_rng, rotation=None, intensity_scale=None, intensity_shift=None,
     return angles, gain, bias
 
 
-def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None, warp=None):
+def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None, warp=None, appearance=None):
     """generator.py:170-217 on qualification flags: yields each batch as a list of (candidate index, isometry key or None).
     The candidate order is shuffled at the first next() (rng.shuffle, if `shuffle`), then pop()ped from the end; a kept candidate
     draws its key (rng.choice over KEYS, if `permute`) when it is popped; a batch is yielded when full, or when the list is empty.
@@ -181,9 +184,13 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
     augment: None, or (np_rng, distortion_factor, flip): a kept candidate then draws draw_augment(...) just before its key
     (generator.py:208-214), and the batch entries are (candidate index, key, (scale, flipped axes)).
     warp: None, or (np_rng, rotation, intensity_scale, intensity_shift, Cv): a kept candidate then draws draw_warp(...) right after
-    draw_augment and before its key, and the entries gain a fourth element (angles, gain, bias)."""
+    draw_augment and before its key, and the entries gain a fourth element (angles, gain, bias).
+    appearance: None, or (np_rng, an appearance.Appearance, Cv): a kept candidate then makes Appearance.draw(np_rng, Cv)'s calls right
+    after draw_warp's (after draw_augment's without warp) and before its key, and the entries gain a last element, that draw."""
     if warp is not None and augment is None:
         raise N3DError("epoch_order: the warp draws follow draw_augment's: warp needs augment")
+    if appearance is not None and augment is None:
+        raise N3DError("epoch_order: the appearance draws follow draw_augment's: appearance needs augment")
     keep = kept_mask(flags, skip_health).tolist()
     order = list(range(len(keep)))
     if shuffle:
@@ -194,7 +201,8 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
         if keep[i]:
             aug = (draw_augment(*augment),) if augment is not None else ()      # drawn before the key
             wrp = (draw_warp(*warp),) if warp is not None else ()               # ... and these between the two
-            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp)
+            app = (appearance[1].draw(appearance[0], appearance[2]),) if appearance is not None else ()      # ... and these last
+            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp + app)
         if len(batch) == batch_size or (not order and batch):
             yield batch
             batch = []
@@ -449,6 +457,13 @@ class Generator:
     each only if its option is set (draw_warp), and then rng's key draw.  With all four at their defaults the generator makes the
     calls, launches and bits it made without them.
 
+    augment_appearance=appearance.Appearance(...): Gaussian noise, Gaussian blur, contrast and gamma of the brain voxels of the
+    gathered data (include/n3d.h, n3d_appear_desc), applied in place by n3d_patch_appearance after the batch's gather and before it is
+    yielded -- in the trainer's input buffers when the batch went there; the truth is never touched.  Also only with augment=True
+    (else N3DError); batch_size at most 16 (N3D_APPEAR_MAX_BATCH), at most 4 channels.  np_rng sees Appearance.draw's calls per
+    kept patch right after draw_warp's and before rng's key draw.  It composes with every option above; left None, the generator
+    makes the calls, draws, launches and bits it made without it.
+
     epoch_init(): one n3d_patch_qualify launch and one device -> host copy of the candidates' flag bytes.
     epoch(out=None): a generator of (x, t) device tensors (t None without truth), one n3d_patch_gather launch per batch
     (n3d_patch_gather_aug with augment) on the current stream.  out: a tuple (x, t) or a zero-argument callable returning one (e.g. trainer.input_buffers), evaluated per
@@ -458,7 +473,7 @@ class Generator:
     def __init__(self, indices_list, volumes, patch_shape, patch_overlap=None, batch_size=1, labels=None, augment=False, permute=False,
                  shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None,
                  augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None, augment_rotation=None,
-                 augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None):
+                 augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None, augment_appearance=None):
         if labels is not None and list(labels) != LABELS:
             raise N3DError("Generator: labels must be None or [1, 2, 4] (the three BraTS regions the kernels expand)")
         ps = [patch_shape] * 3 if isinstance(patch_shape, int) else [int(p) for p in patch_shape]
@@ -488,6 +503,18 @@ class Generator:
         for name, val in (("augment_intensity_scale", augment_intensity_scale), ("augment_intensity_shift", augment_intensity_shift)):
             if val is not None and not (np.ndim(val) == 0 and np.isfinite(val) and val >= 0):
                 raise N3DError("Generator: %s is a non-negative number (got %r)" % (name, val))
+        if augment_appearance is not None:
+            if not isinstance(augment_appearance, appearance.Appearance):
+                raise N3DError("Generator: augment_appearance is an appearance.Appearance (got %r)" % (augment_appearance,))
+            if not augment:
+                raise N3DError("Generator: augment_appearance acts only with augment=True")
+            if int(batch_size) > appearance.MAX_BATCH:
+                raise N3DError("Generator: batch_size must be 1..%d with augment_appearance (N3D_APPEAR_MAX_BATCH)" % appearance.MAX_BATCH)
+            channels = getattr(volumes, "channels", None)
+            if channels is not None and channels > appearance.MAX_CHANNELS:
+                raise N3DError("Generator: augment_appearance supports at most %d channels (the set has %d)" % (
+                    appearance.MAX_CHANNELS, channels))
+        self.augment_appearance = augment_appearance
         self.affine = check_affine(affine) if augment else affine
         if augment:
             # fail here, not in the middle of an epoch with draws already consumed: the batches are made by volumes.patch_batch,
@@ -552,15 +579,26 @@ class Generator:
             yield from self._warped_epoch(out, draws)
             return
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
-                                 augment=draws):
+                                 augment=draws, appearance=self._appearance_draws()):
             o = out() if callable(out) else out
             B = len(batch)
             refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
-            aug = [resample_params(self.affine, self.patch, scale) + (axes,) for _, _, (scale, axes) in batch] if self.augment else None
+            aug = [resample_params(self.affine, self.patch, e[2][0]) + (e[2][1],) for e in batch] if self.augment else None
             fit = o if self.volumes.fits(o, B, self.patch, self.target_dtype) else None
-            yield self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug)
+            yield self._appear(self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug), batch)
         if self.patch_overlap:
             self.epoch_init()
+
+    def _appearance_draws(self):
+        a = self.augment_appearance
+        return (self.np_rng, a, self.volumes.channels) if a is not None else None
+
+    def _appear(self, xt, batch):
+        """the batch's appearance draws (the last element of its entries) applied to the gathered x where it lies -- the trainer's
+        input buffers when the batch went there; the truth is never touched"""
+        if self.augment_appearance is not None:
+            self.augment_appearance.apply(xt[0], [e[-1] for e in batch])
+        return xt
 
     def _warped_epoch(self, out, draws):
         """epoch() with one of the rotation / interpolation / intensity options set: every batch is one n3d_patch_gather_warp launch"""
@@ -568,17 +606,17 @@ class Generator:
         order = 1 if self.augment_interpolation == "linear" else 0
         wdraws = (self.np_rng, self.augment_rotation, self.augment_intensity_scale, self.augment_intensity_shift, self.volumes.channels)
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
-                                 augment=draws, warp=wdraws):
+                                 augment=draws, warp=wdraws, appearance=self._appearance_draws()):
             o = out() if callable(out) else out
             B = len(batch)
             refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
             aug, warp = [], []
-            for _, _, (scale, axes), (angles, gain, bias) in batch:
+            for (scale, axes), (angles, gain, bias) in (e[2:4] for e in batch):
                 A, b, identity = resample_transform(self.affine, P, scale)
                 aug.append((A, b / A, identity, axes))
                 matrix = warp_transform(A, b, rotation_matrix(angles), P) if angles is not None else None
                 warp.append((matrix, order, gain, bias))
             fit = o if self.volumes.fits(o, B, P, self.target_dtype) else None
-            yield self.volumes.patch_batch(refs, P, self.inclusive_label, self.target_dtype, out=fit, augment=aug, warp=warp)
+            yield self._appear(self.volumes.patch_batch(refs, P, self.inclusive_label, self.target_dtype, out=fit, augment=aug, warp=warp), batch)
         if self.patch_overlap:
             self.epoch_init()
