@@ -665,6 +665,57 @@ typedef struct n3d_patch_wdesc {
 int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_wdesc* descs, int B, int P, int flags,
                           float* x_out, int64_t xld, void* t_out, void* stream);
 
+/* n3d_patch_gather_warp with an elastic (non-rigid) displacement added to the coordinate, in the same single launch: a free-form
+ * deformation on a coarse lattice of uniform cubic B-splines (batchgenerators' / TorchIO's / MONAI's elastic transform; none of it
+ * the reference's) whose control values are generated on the device from an 8-byte key.  A descriptor is n3d_patch_wdesc `w` plus:
+ *   lattice:     cells = n cells per axis, 1 <= n <= 8; G = n + 3 control points per axis, each holding a 3-vector; lattice point
+ *                l = (l_0 * G + l_1) * G + l_2.
+ *   values:      w0..w3 = Philox4x32-10 (the constants and rounds of n3d_appear_desc's noise stage) of the counter (l, 1, 0, 0)
+ *                under the key (key[0], key[1]);  D[a][l] = 2.0 * ((double)w_a * 2^-32) - 1.0 for a = 0, 1, 2: in [-1, 1), exact.
+ *   lock:        L, 0 <= L <= 3, G - 2 L >= 1:  D[a][l] = +0.0 where some lattice index l_i < L or l_i >= G - L.  L = 2 is TorchIO's
+ *                locked_borders; L = 3 holds the patch's faces still (below).
+ *   evaluation:  at the patch index j the isometry of w.g.d gives -- the j the warp rule starts from.  Per axis a:
+ *                  s = (double)j_a * inv_h          inv_h = (double)n / (double)(P - 1), computed by the host and passed;
+ *                  cell = (int)min(floor(s), (double)(n - 1));   f = s - (double)cell;   g = 1.0 - f;   with S = 1.0 / 6.0 (the fp64
+ *                  constant 0.16666666666666666) the four weights of the axis are
+ *                  b[0] = ((g * g) * g) * S
+ *                  b[1] = ((((3.0 * f - 6.0) * f) * f) + 4.0) * S
+ *                  b[2] = ((((3.0 - 3.0 * f) * f + 3.0) * f) + 1.0) * S
+ *                  b[3] = ((f * f) * f) * S
+ *                (b0, cell0), (b1, cell1), (b2, cell2) for the three axes.  For each component a the 64 control points cell + m,
+ *                m in {0..3}^3, are summed separably, innermost along axis 2, every sum left to right starting from the m = 0 product:
+ *                  T(m_0, m_1) = ((b2[0] * D(m_0, m_1, 0) + b2[1] * D(m_0, m_1, 1)) + b2[2] * D(m_0, m_1, 2)) + b2[3] * D(m_0, m_1, 3)
+ *                  U(m_0)      = ((b1[0] * T(m_0, 0) + b1[1] * T(m_0, 1)) + b1[2] * T(m_0, 2)) + b1[3] * T(m_0, 3)
+ *                  acc_a       = ((b0[0] * U(0) + b0[1] * U(1)) + b0[2] * U(2)) + b0[3] * U(3)
+ *                with D(m) = D[a][((cell0 + m_0) * G + cell1 + m_1) * G + cell2 + m_2];  delta_a = amp[a] * acc_a.
+ *   coordinate:  c'_a = c_a + delta_a, c the coordinate of n3d_patch_wdesc (mode 0 or 1, unchanged).  Everything downstream is the
+ *                warp rule applied to c': the bounds test on c' itself, the nearest voxel of the labels, order 0 / 1 of the data,
+ *                aflip, the crop's zero padding, the intensity map.
+ * Every product, sum and difference is rounded to fp64 on its own (no contraction).  With `elastic` clear nothing above is
+ * evaluated (cells, lock, amp and inv_h are still checked) and the output is bit-identical to n3d_patch_gather_warp; so it is
+ * with `elastic` set and amp = 0.  The weights are non-negative on [0, 1] and sum to 1, so |delta_a| <= amp[a] (up to rounding),
+ * and the field's slope is at most 2 amp / h, h = (P - 1) / n: for amp < h / 2 the map does not fold.  With L = 3 the field is
+ * exactly 0 on the faces j_a = 0 (f = 0: b[3] = 0 and the three other points are locked); on the faces j_a = P - 1 it is exactly 0
+ * when (double)(P - 1) * inv_h rounds to n (g = 0; it does for every n at P <= 25) and at most amp * 2^-149 in size otherwise (|g| <=
+ * 2^-49), which is absorbed by every c of size 2^-96 or above.
+ * cells and lock in range, amp finite and >= 0, inv_h finite and >= 0, and all n3d_patch_gather_warp checks, else
+ * N3D_ERR_INVALID before any launch.  descs: HOST array of at most N3D_PATCH_ELASTIC_MAX_BATCH (the descriptors travel in the
+ * 4 KB of kernel arguments: sixteen of them would leave under 100 bytes). */
+#define N3D_PATCH_ELASTIC_MAX_BATCH 8
+#define N3D_PATCH_ELASTIC_MAX_CELLS 8
+typedef struct n3d_patch_edesc {
+  n3d_patch_wdesc w;
+  int32_t elastic;     /* != 0: the displacement is added */
+  int32_t cells;       /* n */
+  int32_t lock;        /* L */
+  uint32_t key[2];     /* the Philox key of the control values */
+  int32_t pad_;
+  double amp[3];       /* largest displacement per axis, in voxels */
+  double inv_h;        /* n / (P - 1) */
+} n3d_patch_edesc;
+int n3d_patch_gather_elastic(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_edesc* descs, int B, int P, int flags,
+                             float* x_out, int64_t xld, void* t_out, void* stream);
+
 /* ---- appearance augmentation of a gathered batch, in place (none of it the reference's: the four transforms of batchgenerators /
  * nnU-Net that the BraTS recipes train with).  x: DEVICE fp32 batch (B, Cv, P, P, P) in NDHWC storage with channel pitch ld >= Cv,
  * as n3d_patch_gather* write it; the lanes between Cv and ld are never touched.  descs: HOST array, one record per patch.

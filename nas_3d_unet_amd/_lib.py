@@ -121,6 +121,12 @@ class WarpDesc(C.Structure):
                 ("k", C.c_double * 12), ("gain", C.c_float * 4), ("bias", C.c_float * 4)]
 
 
+class ElasticDesc(C.Structure):
+    """n3d_patch_edesc (include/n3d.h)"""
+    _fields_ = [("w", WarpDesc), ("elastic", C.c_int32), ("cells", C.c_int32), ("lock", C.c_int32), ("key", C.c_uint32 * 2),
+                ("pad_", C.c_int32), ("amp", C.c_double * 3), ("inv_h", C.c_double)]
+
+
 class AppearDesc(C.Structure):
     """n3d_appear_desc (include/n3d.h)"""
     _fields_ = [("noise", C.c_int32), ("blur", C.c_int32), ("contrast", C.c_int32), ("gamma", C.c_int32), ("key", C.c_uint32 * 2),
@@ -249,6 +255,7 @@ PROTOTYPES = {
     "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_aug": (_i, [_p, _i, _i, C.POINTER(AugDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_warp": (_i, [_p, _i, _i, C.POINTER(WarpDesc), _i, _i, _i, _p, _i64, _p, _p]),
+    "n3d_patch_gather_elastic": (_i, [_p, _i, _i, C.POINTER(ElasticDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_appearance": (_i, [_p, _i64, _i, _i, _i, C.POINTER(AppearDesc), _p, _sz, _p]),
     "n3d_patch_appearance_scratch": (_sz, [_i, _i, _i]),
     "n3d_brain_scan": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),

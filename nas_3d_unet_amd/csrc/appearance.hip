@@ -66,22 +66,7 @@ __global__ __launch_bounds__(256) void appear_mask_kernel(const float* __restric
   mask[v] = (uint8_t)m;
 }
 
-// ---- noise
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&w)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
+// ---- noise (philox4x32_10: n3d_common.h)
 __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, double& za, double& zb) {
   const double u1 = ((double)wa + 1.0) * 0x1p-32, u2 = (double)wb * 0x1p-32;
   const double rho = sqrt(-2.0 * log(u1)), th = 6.283185307179586 * u2;

@@ -158,22 +158,8 @@ __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const n3d_patch_v
 // without a rotation (profiles/warp_probe.log; the plain gather: 11.4 us).
 struct WarpDescs { n3d_patch_wdesc d[N3D_PATCH_WARP_MAX_BATCH]; };
 
-template <typename TT>
-__global__ __launch_bounds__(256) void patch_gather_warp_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, WarpDescs descs, int P, int inclusive,
-                                                                float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out, FastDiv fP,
-                                                                FastDiv fPP) {
-  const int b = blockIdx.y;
-  const n3d_patch_wdesc& w = descs.d[b];
-  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
-  const uint32_t P3 = (uint32_t)P * P * P;
-  if (v >= P3) return;
-  const n3d_patch_volume r = vols[w.g.vol];
-  const int X = r.dims[0], Y = r.dims[1], Z = r.dims[2];
-  const int dims[3] = {X, Y, Z};
-  const int64_t XYZ = (int64_t)X * Y * Z;
-  int j[3];
-  patch_index(w.g.d, v, P, fP, fPP, j);
-  double c[3];
+// the warp rule's coordinate of patch index j
+__device__ __forceinline__ void patch_warp_coordinate(const n3d_patch_wdesc& w, const int (&j)[3], double (&c)[3]) {
   if (w.mode == 0) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) c[a] = ((double)j[a] + w.k[3 + a]) * w.k[a];
@@ -186,6 +172,18 @@ __global__ __launch_bounds__(256) void patch_gather_warp_kernel(const n3d_patch_
       c[a] = t + w.k[9 + a];
     }
   }
+}
+
+// everything of the warp rule downstream of the coordinate c of output voxel v of patch b: bounds, nearest voxel, order 0 / 1, aflip,
+// the crop's zero padding, the intensity map, the stores
+template <typename TT>
+__device__ __forceinline__ void patch_warp_resample(const n3d_patch_volume& r, const n3d_patch_wdesc& w, const double (&c)[3], int Cv, int b,
+                                                    uint32_t v, int P, int inclusive, float* __restrict__ x_out, int64_t xld,
+                                                    TT* __restrict__ t_out) {
+  const uint32_t P3 = (uint32_t)P * P * P;
+  const int X = r.dims[0], Y = r.dims[1], Z = r.dims[2];
+  const int dims[3] = {X, Y, Z};
+  const int64_t XYZ = (int64_t)X * Y * Z;
   bool ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) ok = ok && 0.0 <= c[a] && c[a] <= (double)(P - 1);
@@ -254,6 +252,115 @@ __global__ __launch_bounds__(256) void patch_gather_warp_kernel(const n3d_patch_
     });
   }
   if (t_out) patch_label_store<TT>(r.truth, in, sv, b, v, P3, inclusive, t_out);
+}
+
+template <typename TT>
+__global__ __launch_bounds__(256) void patch_gather_warp_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, WarpDescs descs, int P, int inclusive,
+                                                                float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out, FastDiv fP,
+                                                                FastDiv fPP) {
+  const int b = blockIdx.y;
+  const n3d_patch_wdesc& w = descs.d[b];
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= (uint32_t)P * P * P) return;
+  const n3d_patch_volume r = vols[w.g.vol];
+  int j[3];
+  patch_index(w.g.d, v, P, fP, fPP, j);
+  double c[3];
+  patch_warp_coordinate(w, j, c);
+  patch_warp_resample<TT>(r, w, c, Cv, b, v, P, inclusive, x_out, xld, t_out);
+}
+
+// patch_gather_warp_kernel with an elastic displacement added to the coordinate (include/n3d.h, n3d_patch_edesc, states the rule
+// operation by operation): a cubic B-spline free-form deformation on a lattice of G = cells + 3 points per axis.  Each workgroup
+// first writes its patch's 3 * G^3 control values into LDS -- at most 1331 Philox blocks per 256 threads, at most 31.9 KB of fp64;
+// every workgroup of a patch regenerates the same lattice from the 8-byte key, nothing is read from memory -- and after a barrier
+// every thread evaluates its voxel: 12 weights, then per component 64 LDS reads and 84 multiplies + 63 adds in the separable order.
+// `elastic` is uniform over the workgroup (one patch per blockIdx.y): a patch without it skips the lattice and the barrier and is
+// the warp kernel.  What a deformed voxel adds: 192 fp64 LDS reads (0.8 GB per 2 x 4 x 64^3 batch, some 10 us at the chip's LDS rate)
+// and 441 fp64 operations (some 6 us).  2 x 4 x 64^3, both patches deformed: 27.2 us at cells 4 and order 0, 37.0 / 40.3 us at order 1
+// and cells 4 / 8; with no patch deformed 13.4 us against the warp kernel's 11.5 (168 registers and the LDS leave fewer waves to
+// hide the gather's loads): profiles/elastic_probe.log.  Not examined with counters.
+struct ElasticDescs { n3d_patch_edesc d[N3D_PATCH_ELASTIC_MAX_BATCH]; };
+constexpr int kElasticMaxG = N3D_PATCH_ELASTIC_MAX_CELLS + 3;
+constexpr int kElasticMaxG3 = kElasticMaxG * kElasticMaxG * kElasticMaxG;
+
+// the four uniform cubic B-spline weights of f
+__device__ __forceinline__ void bspline_weights(double f, double (&bw)[4]) {
+  const double S = 1.0 / 6.0;
+  const double g = 1.0 - f;
+  bw[0] = ((g * g) * g) * S;
+  bw[1] = ((((3.0 * f - 6.0) * f) * f) + 4.0) * S;
+  bw[2] = ((((3.0 - 3.0 * f) * f + 3.0) * f) + 1.0) * S;
+  bw[3] = ((f * f) * f) * S;
+}
+
+template <typename TT>
+__global__ __launch_bounds__(256) void patch_gather_elastic_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, ElasticDescs descs, int P,
+                                                                   int inclusive, float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out,
+                                                                   FastDiv fP, FastDiv fPP) {
+  __shared__ double lattice[3 * kElasticMaxG3];
+  const int b = blockIdx.y;
+  const n3d_patch_edesc& e = descs.d[b];
+  const n3d_patch_wdesc& w = e.w;
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  const bool elastic = e.elastic != 0;
+  const int n = e.cells, G = n + 3, G3 = G * G * G;        // the host checked 1 <= n <= N3D_PATCH_ELASTIC_MAX_CELLS
+  if (elastic) {
+    const int L = e.lock;
+    for (int l = threadIdx.x; l < G3; l += 256) {
+      const int l0 = l / (G * G), l1 = (l / G) % G, l2 = l % G;
+      const bool locked = l0 < L || l0 >= G - L || l1 < L || l1 >= G - L || l2 < L || l2 >= G - L;
+      uint32_t r[4];
+      philox4x32_10((uint32_t)l, 1, 0, 0, e.key[0], e.key[1], r);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) lattice[a * G3 + l] = locked ? 0.0 : 2.0 * ((double)r[a] * 0x1p-32) - 1.0;
+    }
+    __syncthreads();      // every thread of the workgroup gets here: the ones past the patch's end leave only below
+  }
+  if (v >= (uint32_t)P * P * P) return;
+  const n3d_patch_volume r = vols[w.g.vol];
+  int j[3];
+  patch_index(w.g.d, v, P, fP, fPP, j);
+  double c[3];
+  patch_warp_coordinate(w, j, c);
+  if (elastic) {
+    double bw[3][4];
+    int cell[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double s = (double)j[a] * e.inv_h;
+      cell[a] = (int)fmin(floor(s), (double)(n - 1));       // s >= 0 (inv_h >= 0 was checked): 0 <= cell <= n - 1, cell + 3 <= G - 1
+      bspline_weights(s - (double)cell[a], bw[a]);
+    }
+    const int base = (cell[0] * G + cell[1]) * G + cell[2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double* __restrict__ D = lattice + a * G3 + base;
+      double U[4];
+#pragma unroll
+      for (int m0 = 0; m0 < 4; ++m0) {
+        double T[4];
+#pragma unroll
+        for (int m1 = 0; m1 < 4; ++m1) {
+          const double* d = D + (m0 * G + m1) * G;
+          double t = bw[2][0] * d[0];
+          t = t + bw[2][1] * d[1];
+          t = t + bw[2][2] * d[2];
+          T[m1] = t + bw[2][3] * d[3];
+        }
+        double u = bw[1][0] * T[0];
+        u = u + bw[1][1] * T[1];
+        u = u + bw[1][2] * T[2];
+        U[m0] = u + bw[1][3] * T[3];
+      }
+      double acc = bw[0][0] * U[0];
+      acc = acc + bw[0][1] * U[1];
+      acc = acc + bw[0][2] * U[2];
+      acc = acc + bw[0][3] * U[3];
+      c[a] = c[a] + e.amp[a] * acc;
+    }
+  }
+  patch_warp_resample<TT>(r, w, c, Cv, b, v, P, inclusive, x_out, xld, t_out);
 }
 
 }  // namespace n3d
@@ -358,6 +465,26 @@ extern "C" int n3d_patch_gather_aug(const n3d_patch_volume* vols, int nvol, int 
   return N3D_OK;
 }
 
+// the checks of one n3d_patch_wdesc, for the entry point `fn`
+static int patch_wdesc_check(const char* fn, const n3d_patch_wdesc& d, int i, int nvol, int Cv) {
+  N3D_CHECK_ARG(d.g.vol >= 0 && d.g.vol < nvol, "%s: descriptor %d names volume %d of a set of %d", fn, i, d.g.vol, nvol);
+  int seen = 0;
+  for (int a = 0; a < 3; ++a) {
+    N3D_CHECK_ARG(d.g.d.perm[a] >= 0 && d.g.d.perm[a] < 3, "%s: perm entries must be 0..2", fn);
+    seen |= 1 << d.g.d.perm[a];
+  }
+  N3D_CHECK_ARG(seen == 7, "%s: perm must be a permutation of (0,1,2)", fn);
+  N3D_CHECK_ARG(d.mode == 0 || d.mode == 1, "%s: descriptor %d: mode must be 0 or 1 (got %d)", fn, i, d.mode);
+  N3D_CHECK_ARG(d.order == 0 || d.order == 1, "%s: descriptor %d: order must be 0 or 1 (got %d)", fn, i, d.order);
+  for (int n = 0; n < 12; ++n) N3D_CHECK_ARG(std::isfinite(d.k[n]), "%s: descriptor %d: coefficient %d must be finite (got %g)", fn, i, n, d.k[n]);
+  for (int a = 0; a < 3 && d.mode == 0; ++a) N3D_CHECK_ARG(d.k[a] != 0.0, "%s: descriptor %d axis %d: A must be nonzero in mode 0", fn, i, a);
+  for (int c = 0; c < 4; ++c)
+    N3D_CHECK_ARG(std::isfinite(d.gain[c]) && std::isfinite(d.bias[c]), "%s: descriptor %d channel %d: gain and bias must be finite (got %g, %g)", fn,
+                  i, c, d.gain[c], d.bias[c]);
+  N3D_CHECK_ARG(!d.intensity || Cv <= 4, "%s: descriptor %d: the intensity map supports at most 4 channels (got %d)", fn, i, Cv);
+  return N3D_OK;
+}
+
 extern "C" int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_wdesc* descs, int B, int P, int flags,
                                      float* x_out, int64_t xld, void* t_out, void* stream) {
   N3D_CHECK_ARG(vols && descs && x_out && nvol >= 1 && Cv >= 1 && P > 0 && B >= 1 && xld >= Cv, "patch_gather_warp: bad args");
@@ -367,25 +494,8 @@ extern "C" int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int
   static_assert(sizeof(WarpDescs) + 64 <= 4096, "the descriptors travel by value in the kernel arguments (4 KB)");
   WarpDescs wd;
   for (int i = 0; i < B; ++i) {
-    const n3d_patch_wdesc& d = descs[i];
-    wd.d[i] = d;
-    N3D_CHECK_ARG(d.g.vol >= 0 && d.g.vol < nvol, "patch_gather_warp: descriptor %d names volume %d of a set of %d", i, d.g.vol, nvol);
-    int seen = 0;
-    for (int a = 0; a < 3; ++a) {
-      N3D_CHECK_ARG(d.g.d.perm[a] >= 0 && d.g.d.perm[a] < 3, "patch_gather_warp: perm entries must be 0..2");
-      seen |= 1 << d.g.d.perm[a];
-    }
-    N3D_CHECK_ARG(seen == 7, "patch_gather_warp: perm must be a permutation of (0,1,2)");
-    N3D_CHECK_ARG(d.mode == 0 || d.mode == 1, "patch_gather_warp: descriptor %d: mode must be 0 or 1 (got %d)", i, d.mode);
-    N3D_CHECK_ARG(d.order == 0 || d.order == 1, "patch_gather_warp: descriptor %d: order must be 0 or 1 (got %d)", i, d.order);
-    for (int n = 0; n < 12; ++n)
-      N3D_CHECK_ARG(std::isfinite(d.k[n]), "patch_gather_warp: descriptor %d: coefficient %d must be finite (got %g)", i, n, d.k[n]);
-    for (int a = 0; a < 3 && d.mode == 0; ++a)
-      N3D_CHECK_ARG(d.k[a] != 0.0, "patch_gather_warp: descriptor %d axis %d: A must be nonzero in mode 0", i, a);
-    for (int c = 0; c < 4; ++c)
-      N3D_CHECK_ARG(std::isfinite(d.gain[c]) && std::isfinite(d.bias[c]),
-                    "patch_gather_warp: descriptor %d channel %d: gain and bias must be finite (got %g, %g)", i, c, d.gain[c], d.bias[c]);
-    N3D_CHECK_ARG(!d.intensity || Cv <= 4, "patch_gather_warp: descriptor %d: the intensity map supports at most 4 channels (got %d)", i, Cv);
+    wd.d[i] = descs[i];
+    if (int rc = patch_wdesc_check("patch_gather_warp", descs[i], i, nvol, Cv)) return rc;
   }
   for (int i = B; i < N3D_PATCH_WARP_MAX_BATCH; ++i) wd.d[i] = wd.d[0];
   N3D_CHECK_ARG((flags & ~(N3D_PATCH_INCLUSIVE | N3D_PATCH_T_U8)) == 0, "patch_gather_warp: unknown flag bits %d", flags);
@@ -397,6 +507,45 @@ extern "C" int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int
                        (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   else
     N3D_LAUNCH(patch_gather_warp_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, wd, P, inclusive, x_out, xld,
+                       (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_patch_gather_elastic(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_edesc* descs, int B, int P, int flags,
+                                        float* x_out, int64_t xld, void* t_out, void* stream) {
+  N3D_CHECK_ARG(vols && descs && x_out && nvol >= 1 && Cv >= 1 && P > 0 && B >= 1 && xld >= Cv, "patch_gather_elastic: bad args");
+  N3D_CHECK_ARG(B <= N3D_PATCH_ELASTIC_MAX_BATCH, "patch_gather_elastic: at most N3D_PATCH_ELASTIC_MAX_BATCH = %d patches per call (got %d)",
+                N3D_PATCH_ELASTIC_MAX_BATCH, B);
+  N3D_CHECK_ARG((int64_t)P * P * P < (1ll << 31), "patch_gather_elastic: patch too large");
+  static_assert(sizeof(ElasticDescs) + 64 <= 4096, "the descriptors travel by value in the kernel arguments (4 KB)");
+  static_assert(sizeof(n3d_patch_edesc) == 248, "n3d_patch_edesc: no hidden padding");
+  ElasticDescs ed;
+  for (int i = 0; i < B; ++i) {
+    const n3d_patch_edesc& d = descs[i];
+    ed.d[i] = d;
+    if (int rc = patch_wdesc_check("patch_gather_elastic", d.w, i, nvol, Cv)) return rc;
+    N3D_CHECK_ARG(d.cells >= 1 && d.cells <= N3D_PATCH_ELASTIC_MAX_CELLS, "patch_gather_elastic: descriptor %d: cells must be 1..%d (got %d)", i,
+                  N3D_PATCH_ELASTIC_MAX_CELLS, d.cells);
+    N3D_CHECK_ARG(d.lock >= 0 && d.lock <= 3, "patch_gather_elastic: descriptor %d: lock must be 0..3 (got %d)", i, d.lock);
+    N3D_CHECK_ARG(d.cells + 3 - 2 * d.lock >= 1, "patch_gather_elastic: descriptor %d: lock %d leaves no free control point on a lattice of %d", i,
+                  d.lock, d.cells + 3);
+    for (int a = 0; a < 3; ++a)
+      N3D_CHECK_ARG(std::isfinite(d.amp[a]) && d.amp[a] >= 0.0, "patch_gather_elastic: descriptor %d axis %d: amp must be finite and >= 0 (got %g)",
+                    i, a, d.amp[a]);
+    N3D_CHECK_ARG(std::isfinite(d.inv_h) && d.inv_h >= 0.0, "patch_gather_elastic: descriptor %d: inv_h must be finite and >= 0 (got %g)", i,
+                  d.inv_h);
+  }
+  for (int i = B; i < N3D_PATCH_ELASTIC_MAX_BATCH; ++i) ed.d[i] = ed.d[0];
+  N3D_CHECK_ARG((flags & ~(N3D_PATCH_INCLUSIVE | N3D_PATCH_T_U8)) == 0, "patch_gather_elastic: unknown flag bits %d", flags);
+  const uint32_t P3 = (uint32_t)P * P * P;
+  const int inclusive = flags & N3D_PATCH_INCLUSIVE;
+  const dim3 grid((unsigned)cdiv(P3, 256), B);
+  if (flags & N3D_PATCH_T_U8)
+    N3D_LAUNCH(patch_gather_elastic_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, ed, P, inclusive, x_out, xld,
+                       (uint8_t*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
+  else
+    N3D_LAUNCH(patch_gather_elastic_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vols, Cv, ed, P, inclusive, x_out, xld,
                        (float*)t_out, FastDiv((uint32_t)P), FastDiv((uint32_t)P * P));
   N3D_LAUNCH_CHECK();
   return N3D_OK;

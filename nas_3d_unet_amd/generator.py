@@ -21,11 +21,15 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
     per-modality intensity scale and shift of the brain voxels, still in ONE launch per batch (n3d_patch_gather_warp):
     rotation_matrix, warp_transform and draw_warp below are their host arithmetic and draws.
 
+  * augment_elastic (elastic.Elastic; not the reference's either) adds a non-rigid displacement to the gather's coordinate: a cubic
+    B-spline free-form deformation whose control values the device generates from a key drawn per patch, still in ONE launch per
+    batch (n3d_patch_gather_elastic).
+
   * augment_appearance (appearance.Appearance; not the reference's either) adds Gaussian noise, Gaussian blur, contrast and gamma of
     the brain voxels, applied to the gathered batch in place by n3d_patch_appearance (1 to 10 launches, no host sync).
 
 Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather, n3d_patch_gather_aug,
-n3d_patch_gather_warp and n3d_patch_appearance (include/n3d.h).
+n3d_patch_gather_warp, n3d_patch_gather_elastic and n3d_patch_appearance (include/n3d.h).
 """
 from __future__ import annotations
 
@@ -37,8 +41,9 @@ import numpy as np
 import torch
 
 from . import _lib, appearance, datastep, predict, preprocess
+from . import elastic as elastic_mod
 from . import kernels as K
-from ._lib import AugDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, WarpDesc, check
+from ._lib import AugDesc, ElasticDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, WarpDesc, check
 
 # augment.py:95-100 draws from list(set(...)): that (deterministic) order, NOT the sorted one of datastep.random_permutation_key
 KEYS = list(datastep.generate_permutation_keys())
@@ -47,6 +52,7 @@ MAX_BATCH = 64      # N3D_PATCH_MAX_BATCH
 AUG_MAX_BATCH = 32  # N3D_PATCH_AUG_MAX_BATCH: the widened descriptors of an augmented batch travel in 4 KB of kernel arguments
 WARP_MAX_BATCH = 16  # N3D_PATCH_WARP_MAX_BATCH
 WARP_MAX_CHANNELS = 4  # gain[4], bias[4] of n3d_patch_wdesc
+ELASTIC_MAX_BATCH = elastic_mod.MAX_BATCH  # N3D_PATCH_ELASTIC_MAX_BATCH
 
 _ISO = {None: ([0, 1, 2], [False, False, False])}
 
@@ -176,7 +182,8 @@ def draw_warp(np_rng, rotation=None, intensity_scale=None, intensity_shift=None,
     return angles, gain, bias
 
 
-def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None, warp=None, appearance=None):
+def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None, warp=None, appearance=None,
+                elastic=None):
     """generator.py:170-217 on qualification flags: yields each batch as a list of (candidate index, isometry key or None).
     The candidate order is shuffled at the first next() (rng.shuffle, if `shuffle`), then pop()ped from the end; a kept candidate
     draws its key (rng.choice over KEYS, if `permute`) when it is popped; a batch is yielded when full, or when the list is empty.
@@ -186,11 +193,16 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
     warp: None, or (np_rng, rotation, intensity_scale, intensity_shift, Cv): a kept candidate then draws draw_warp(...) right after
     draw_augment and before its key, and the entries gain a fourth element (angles, gain, bias).
     appearance: None, or (np_rng, an appearance.Appearance, Cv): a kept candidate then makes Appearance.draw(np_rng, Cv)'s calls right
-    after draw_warp's (after draw_augment's without warp) and before its key, and the entries gain a last element, that draw."""
+    after draw_warp's (after draw_augment's without warp) and before its key, and the entries gain a last element, that draw.
+    elastic: None, or (np_rng, an elastic.Elastic): a kept candidate then makes Elastic.draw(np_rng)'s calls right after draw_warp's
+    (after draw_augment's without warp) and before Appearance.draw's and its key, and the entries gain one element ahead of the
+    appearance one: the drawn key (k0, k1), or None for a patch that is not deformed."""
     if warp is not None and augment is None:
         raise N3DError("epoch_order: the warp draws follow draw_augment's: warp needs augment")
     if appearance is not None and augment is None:
         raise N3DError("epoch_order: the appearance draws follow draw_augment's: appearance needs augment")
+    if elastic is not None and augment is None:
+        raise N3DError("epoch_order: the elastic draws follow draw_augment's: elastic needs augment")
     keep = kept_mask(flags, skip_health).tolist()
     order = list(range(len(keep)))
     if shuffle:
@@ -201,8 +213,9 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
         if keep[i]:
             aug = (draw_augment(*augment),) if augment is not None else ()      # drawn before the key
             wrp = (draw_warp(*warp),) if warp is not None else ()               # ... and these between the two
+            ela = (elastic[1].draw(elastic[0]),) if elastic is not None else ()  # ... then these
             app = (appearance[1].draw(appearance[0], appearance[2]),) if appearance is not None else ()      # ... and these last
-            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp + app)
+            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp + ela + app)
         if len(batch) == batch_size or (not order and batch):
             yield batch
             batch = []
@@ -322,6 +335,8 @@ class VolumeSet:
         """the n3d_patch_wdesc table of a warped batch (patch_batch): entry i takes its flips and its scale map (A, sh) from augment[i]
         and its matrix, interpolation order and intensity map from warp[i]; a None entry changes nothing"""
         B = len(refs)
+        if warp is None:
+            warp = [None] * B
         if len(warp) != B or (augment is not None and len(augment) != B):
             raise N3DError("VolumeSet.patch_batch: one warp entry (or None) and one augmentation (or None) per ref")
         if B > WARP_MAX_BATCH:
@@ -359,7 +374,31 @@ class VolumeSet:
                                 (C.c_float * 4)(*gn), (C.c_float * 4)(*bs))
         return descs
 
-    def patch_batch(self, refs, patch, inclusive_label=False, target_dtype=torch.float32, out=None, augment=None, warp=None):
+    def _elastic_descs(self, refs, P, augment, warp, elastic):
+        """the n3d_patch_edesc table of a batch with a deformed patch (patch_batch): entry i is _warp_descs' record plus elastic[i] =
+        (cells, lock, key, amp); a None entry leaves the patch to the warp rule alone"""
+        B = len(refs)
+        if len(elastic) != B:
+            raise N3DError("VolumeSet.patch_batch: one elastic entry (or None) per ref")
+        if B > ELASTIC_MAX_BATCH:
+            raise N3DError("VolumeSet.patch_batch: a batch with an elastic deformation holds at most %d patches "
+                           "(N3D_PATCH_ELASTIC_MAX_BATCH)" % ELASTIC_MAX_BATCH)
+        wdescs = self._warp_descs(refs, P, augment, warp)
+        descs = (ElasticDesc * B)()
+        for i, e in enumerate(elastic):
+            if e is None:
+                descs[i] = ElasticDesc(wdescs[i], 0, 1, 0, (C.c_uint32 * 2)(0, 0), 0, (C.c_double * 3)(0.0, 0.0, 0.0), 0.0)
+                continue
+            cells, lock, key, amp = e
+            elastic_mod.check_lattice(cells, lock, "VolumeSet.patch_batch")
+            amp = np.broadcast_to(np.asarray(amp, np.float64), (3,))
+            if not np.isfinite(amp).all() or (amp < 0).any():
+                raise N3DError("VolumeSet.patch_batch: an elastic entry's amp is finite and >= 0 (got %r)" % (e[3],))
+            descs[i] = ElasticDesc(wdescs[i], 1, int(cells), int(lock), (C.c_uint32 * 2)(int(key[0]), int(key[1])), 0,
+                                   (C.c_double * 3)(*[float(a) for a in amp]), float(elastic_mod.inv_h(cells, P)))
+        return descs
+
+    def patch_batch(self, refs, patch, inclusive_label=False, target_dtype=torch.float32, out=None, augment=None, warp=None, elastic=None):
         """One batch whose patches come from any volumes of the set: refs = [(volume index, corner, isometry key or None)].
         What datastep.patch_batch makes of each patch on its own volume, bit for bit, in ONE n3d_patch_gather launch on the current
         stream.  Returns (x, t): x (B, Cv, P, P, P) fp32 in NDHWC storage, t (B, 3, P, P, P) of target_dtype (None without truth).
@@ -372,19 +411,28 @@ class VolumeSet:
         b / A and not b; the flipped axes of augment still apply), order 0 / 1 = nearest / linear interpolation of the data (the truth
         stays nearest), gain / bias = Cv factors / offsets applied to the nonzero voxels (include/n3d.h, n3d_patch_wdesc).  With
         some entry not None the batch is ONE n3d_patch_gather_warp launch (at most 16 patches): the matrix rule for the entries
-        with a matrix, the zoom-shift rule with the entry's (A, sh) otherwise.  Otherwise the launches are exactly the ones above."""
+        with a matrix, the zoom-shift rule with the entry's (A, sh) otherwise.  Otherwise the launches are exactly the ones above.
+        elastic: None, or one entry per ref -- None, or (cells, lock, key, amp): the cubic B-spline displacement of include/n3d.h,
+        n3d_patch_edesc (cells per axis, locked border layers, the Philox key (k0, k1) of the control values, the largest displacement
+        in voxels -- a scalar or one per axis) is added to that ref's coordinate, whatever augment and warp make of it.  With some entry
+        not None the batch is ONE n3d_patch_gather_elastic launch (at most 8 patches).  Otherwise the launches are exactly the ones
+        above."""
         if target_dtype not in (torch.float32, torch.uint8):
             raise N3DError("VolumeSet.patch_batch: targets are float32 or uint8")
         B, P = len(refs), int(patch)
         if B < 1 or not self.volumes:
             raise N3DError("VolumeSet.patch_batch: need at least one patch of a non-empty set")
-        warped = warp is not None and any(w is not None for w in warp)
+        deformed = elastic is not None and any(e is not None for e in elastic)
+        warped = deformed or (warp is not None and any(w is not None for w in warp))
         augmented = not warped and augment is not None and any(a is not None for a in augment)
         if augmented and len(augment) != B:
             raise N3DError("VolumeSet.patch_batch: one augmentation (or None) per ref")
         if augmented and B > AUG_MAX_BATCH:
             raise N3DError("VolumeSet.patch_batch: an augmented batch holds at most %d patches (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
-        descs = self._warp_descs(refs, P, augment, warp) if warped else ((AugDesc if augmented else GatherDesc) * B)()
+        if deformed:
+            descs = self._elastic_descs(refs, P, augment, warp, elastic)
+        else:
+            descs = self._warp_descs(refs, P, augment, warp) if warped else ((AugDesc if augmented else GatherDesc) * B)()
         for i, (v, corner, key) in enumerate(() if warped else refs):
             perm, flip = _isometry(key)
             g = GatherDesc(PatchDesc((C.c_int32 * 3)(*[int(c) for c in corner]), (C.c_int32 * 3)(*perm),
@@ -417,7 +465,10 @@ class VolumeSet:
             t = torch.empty((B, 3, P, P, P), dtype=target_dtype, device=self.device) if self.has_truth else None
             xv = K.as_view(x)
         flags = (_lib.PATCH_INCLUSIVE if inclusive_label else 0) | (_lib.PATCH_T_U8 if target_dtype == torch.uint8 else 0)
-        if warped:
+        if deformed:
+            check(_lib.load().n3d_patch_gather_elastic(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
+                                                       K.stream_ptr()), "n3d_patch_gather_elastic")
+        elif warped:
             check(_lib.load().n3d_patch_gather_warp(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
                                                     K.stream_ptr()), "n3d_patch_gather_warp")
         elif augmented:
@@ -464,6 +515,15 @@ class Generator:
     kept patch right after draw_warp's and before rng's key draw.  It composes with every option above; left None, the generator
     makes the calls, draws, launches and bits it made without it.
 
+    augment_elastic=elastic.Elastic(...): a non-rigid displacement of the crop, added to the coordinate the options above give
+    (include/n3d.h, n3d_patch_edesc): a cubic B-spline free-form deformation on a lattice of cells + 3 control points per axis whose
+    values the device generates from a key drawn per patch; data and truth move alike.  Also only with augment=True (else N3DError);
+    batch_size at most 8 (N3D_PATCH_ELASTIC_MAX_BATCH); Elastic.check(patch) -- the folding bound -- runs at construction; a
+    `data_file` whose patch_batch takes no `elastic` raises NotImplementedError.  np_rng sees Elastic.draw's calls per kept patch
+    right after draw_warp's and before Appearance.draw's: uniform(), and for a deformed patch randint(0, 2**32, 2, dtype=np.uint32).
+    A batch with a deformed patch is ONE n3d_patch_gather_elastic launch, any other batch the launch it was without the option.  It
+    composes with every option above; left None, the generator makes the calls, draws, launches and bits it made without it.
+
     epoch_init(): one n3d_patch_qualify launch and one device -> host copy of the candidates' flag bytes.
     epoch(out=None): a generator of (x, t) device tensors (t None without truth), one n3d_patch_gather launch per batch
     (n3d_patch_gather_aug with augment) on the current stream.  out: a tuple (x, t) or a zero-argument callable returning one (e.g. trainer.input_buffers), evaluated per
@@ -473,7 +533,8 @@ class Generator:
     def __init__(self, indices_list, volumes, patch_shape, patch_overlap=None, batch_size=1, labels=None, augment=False, permute=False,
                  shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None,
                  augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None, augment_rotation=None,
-                 augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None, augment_appearance=None):
+                 augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None, augment_appearance=None,
+                 augment_elastic=None):
         if labels is not None and list(labels) != LABELS:
             raise N3DError("Generator: labels must be None or [1, 2, 4] (the three BraTS regions the kernels expand)")
         ps = [patch_shape] * 3 if isinstance(patch_shape, int) else [int(p) for p in patch_shape]
@@ -515,6 +576,15 @@ class Generator:
                 raise N3DError("Generator: augment_appearance supports at most %d channels (the set has %d)" % (
                     appearance.MAX_CHANNELS, channels))
         self.augment_appearance = augment_appearance
+        if augment_elastic is not None:
+            if not isinstance(augment_elastic, elastic_mod.Elastic):
+                raise N3DError("Generator: augment_elastic is an elastic.Elastic (got %r)" % (augment_elastic,))
+            if not augment:
+                raise N3DError("Generator: augment_elastic acts only with augment=True")
+            if int(batch_size) > ELASTIC_MAX_BATCH:
+                raise N3DError("Generator: batch_size must be 1..%d with augment_elastic (N3D_PATCH_ELASTIC_MAX_BATCH)" % ELASTIC_MAX_BATCH)
+            augment_elastic.check(ps[0])
+        self.augment_elastic = augment_elastic
         self.affine = check_affine(affine) if augment else affine
         if augment:
             # fail here, not in the middle of an epoch with draws already consumed: the batches are made by volumes.patch_batch,
@@ -527,6 +597,9 @@ class Generator:
                 raise NotImplementedError("Generator: augment_rotation / augment_interpolation / augment_intensity_* need a volume set "
                                           "whose patch_batch(..., warp=) resamples in the gather (VolumeSet); %s has none"
                                           % type(volumes).__name__)
+            if augment_elastic is not None and "elastic" not in inspect.signature(gather).parameters:
+                raise NotImplementedError("Generator: augment_elastic needs a volume set whose patch_batch(..., elastic=) deforms in the "
+                                          "gather (VolumeSet); %s has none" % type(volumes).__name__)
             channels = getattr(volumes, "channels", None)
             if intensity and channels is not None and channels > WARP_MAX_CHANNELS:
                 raise N3DError("Generator: the intensity map supports at most %d channels (the set has %d)" % (WARP_MAX_CHANNELS, channels))
@@ -579,19 +652,30 @@ class Generator:
             yield from self._warped_epoch(out, draws)
             return
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
-                                 augment=draws, appearance=self._appearance_draws()):
+                                 augment=draws, appearance=self._appearance_draws(), **self._elastic_draws()):
             o = out() if callable(out) else out
             B = len(batch)
             refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
             aug = [resample_params(self.affine, self.patch, e[2][0]) + (e[2][1],) for e in batch] if self.augment else None
             fit = o if self.volumes.fits(o, B, self.patch, self.target_dtype) else None
-            yield self._appear(self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug), batch)
+            yield self._appear(self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug,
+                                                        **self._elastic_entries(batch, 3)), batch)
         if self.patch_overlap:
             self.epoch_init()
 
     def _appearance_draws(self):
         a = self.augment_appearance
         return (self.np_rng, a, self.volumes.channels) if a is not None else None
+
+    def _elastic_draws(self):
+        """epoch_order's `elastic` argument: absent without the option, so that a stand-in epoch_order sees today's call"""
+        return {"elastic": (self.np_rng, self.augment_elastic)} if self.augment_elastic is not None else {}
+
+    def _elastic_entries(self, batch, at):
+        """patch_batch's `elastic` argument from element `at` of the batch's entries: absent without the option"""
+        if self.augment_elastic is None:
+            return {}
+        return {"elastic": [self.augment_elastic.entry(e[at]) for e in batch]}
 
     def _appear(self, xt, batch):
         """the batch's appearance draws (the last element of its entries) applied to the gathered x where it lies -- the trainer's
@@ -606,7 +690,7 @@ class Generator:
         order = 1 if self.augment_interpolation == "linear" else 0
         wdraws = (self.np_rng, self.augment_rotation, self.augment_intensity_scale, self.augment_intensity_shift, self.volumes.channels)
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
-                                 augment=draws, warp=wdraws, appearance=self._appearance_draws()):
+                                 augment=draws, warp=wdraws, appearance=self._appearance_draws(), **self._elastic_draws()):
             o = out() if callable(out) else out
             B = len(batch)
             refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
@@ -617,6 +701,7 @@ class Generator:
                 matrix = warp_transform(A, b, rotation_matrix(angles), P) if angles is not None else None
                 warp.append((matrix, order, gain, bias))
             fit = o if self.volumes.fits(o, B, P, self.target_dtype) else None
-            yield self._appear(self.volumes.patch_batch(refs, P, self.inclusive_label, self.target_dtype, out=fit, augment=aug, warp=warp), batch)
+            yield self._appear(self.volumes.patch_batch(refs, P, self.inclusive_label, self.target_dtype, out=fit, augment=aug, warp=warp,
+                                                        **self._elastic_entries(batch, 4)), batch)
         if self.patch_overlap:
             self.epoch_init()
