@@ -13,7 +13,7 @@ import os
 import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("N3D_LIB") or os.path.join(_HERE, "libn3d.so")   # N3D_LIB: another build of the same ABI (A/B timing of a kernel change)
+LIB_PATH = os.environ.get("N3D_LIB") or os.path.join(_HERE, "libn3d.so")   # environment variable N3D_LIB: another build of the same ABI (A/B timing of a kernel change)
 
 
 class N3DError(RuntimeError):
@@ -318,12 +318,12 @@ PROTOTYPES = {
 }
 
 # flags (include/n3d.h)
-RELU_IN, RELU, ACCUMULATE, POOL_MAX, NO_MFMA, PREPACKED = 1, 2, 4, 8, 16, 32
+RELU_IN, RELU, ACCUMULATE, POOL_MAX, NO_MFMA, PREPACKED = 1, 2, 4, 8, 16, 32   # N3D_RELU_IN / N3D_RELU / N3D_ACCUMULATE / N3D_POOL_MAX / N3D_NO_MFMA / N3D_PREPACKED
 F32, BF16, U8 = 0, 1, 2   # N3D_F32 / N3D_BF16 / N3D_U8 (byte targets of the head passes and of the data step)
-PATCH_INCLUSIVE, PATCH_T_U8 = 1, 2   # n3d_patch_batch flags
-SRC_BF16, DST_BF16, ACT_BF16 = 64, 128, 64   # storage flags of the conv / epilogue families
-NO_POINTWISE = 512   # conv family: small pointwise convs take the generic gather kernel instead of conv_point_kernel (A/B, bit comparison)
-MM_BF16 = 256   # conv family, bf16 configuration: the C >= 16 MFMA kernels round their operands to bf16 (fp32 storage, fp32 accumulate)
+PATCH_INCLUSIVE, PATCH_T_U8 = 1, 2   # N3D_PATCH_INCLUSIVE / N3D_PATCH_T_U8 (n3d_patch_batch flags)
+SRC_BF16, DST_BF16, ACT_BF16 = 64, 128, 64   # N3D_SRC_BF16 / N3D_DST_BF16 / N3D_ACT_BF16: storage flags of the conv / epilogue families
+NO_POINTWISE = 512   # N3D_NO_POINTWISE: conv family: small pointwise convs take the generic gather kernel instead of conv_point_kernel (A/B, bit comparison)
+MM_BF16 = 256   # N3D_MM_BF16: conv family, bf16 configuration: the C >= 16 MFMA kernels round their operands to bf16 (fp32 storage, fp32 accumulate)
 
 _lib = None
 

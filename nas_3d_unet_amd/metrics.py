@@ -44,15 +44,15 @@ LESION_COLUMNS = tuple("%s_%s" % (c, r) for c in LESION_CRITERIA for r in ("ET",
 
 INF = 1 << 29            # N3D_SEG_INF
 MAX_AXIS = 1024          # N3D_SEG_MAX_AXIS
-REC_WORDS, REC_ORDER, REC_BBOX = 30, 9, 21   # N3D_SEG_REC_*
+REC_WORDS, REC_ORDER, REC_BBOX = 30, 9, 21   # N3D_SEG_REC_WORDS / N3D_SEG_REC_ORDER / N3D_SEG_REC_BBOX
 _I32_MAX = 2 ** 31 - 1
-# N3D_LW_*
-LW_MAX_DILATION, LW_MAX_LESIONS, LW_MAX_SURFACE, LW_MAX_AXIS = 5, 64, 1 << 18, 1024
-LW_HEADER_WORDS, LW_ROW_WORDS = 8, 9
-LW_REGION_WORDS = LW_HEADER_WORDS + LW_MAX_LESIONS * LW_ROW_WORDS
-LW_REC_WORDS = 3 * LW_REGION_WORDS
-LW_PHASES = 35
-LW_REGION_PHASES = ("select", "label_pred", "dilate", "label_truth", "roots", "ranks", "match", "components", "surfaces", "distances", "order")
+# the lesion-wise limits and record layout of include/n3d.h
+LW_MAX_DILATION, LW_MAX_LESIONS, LW_MAX_SURFACE, LW_MAX_AXIS = 5, 64, 1 << 18, 1024   # N3D_LW_MAX_DILATION / N3D_LW_MAX_LESIONS / N3D_LW_MAX_SURFACE / N3D_LW_MAX_AXIS
+LW_HEADER_WORDS, LW_ROW_WORDS = 8, 9   # N3D_LW_HEADER_WORDS / N3D_LW_ROW_WORDS
+LW_REGION_WORDS = LW_HEADER_WORDS + LW_MAX_LESIONS * LW_ROW_WORDS   # N3D_LW_REGION_WORDS
+LW_REC_WORDS = 3 * LW_REGION_WORDS   # N3D_LW_REC_WORDS
+LW_PHASES = 35   # N3D_LW_PHASES
+LW_REGION_PHASES = ("select", "label_pred", "dilate", "label_truth", "roots", "ranks", "match", "components", "surfaces", "distances", "order")   # N3D_LW_REGION_PHASES names, in order
 _LW_OVERFLOW = ((1, "N3D_LW_MAX_LESIONS = %d lesions" % LW_MAX_LESIONS),
                 (2, "N3D_LW_MAX_SURFACE = %d surface entries of the truth" % LW_MAX_SURFACE),
                 (4, "N3D_LW_MAX_SURFACE = %d surface entries of the prediction" % LW_MAX_SURFACE))

@@ -24,9 +24,9 @@ from ._lib import N3DError, check
 
 CONNECTIVITIES = (6, 18, 26)
 # N3D_CC_REC_*: the record's int64 words
-REC_WORDS = 10
+REC_WORDS = 10   # N3D_CC_REC_WORDS
 REC_COMPONENTS, REC_KEPT, REC_VOXELS_IN, REC_VOXELS_KEPT, REC_LARGEST_SIZE, REC_LARGEST_ID, REC_ET_IN, REC_ET_KEPT, REC_ET_RELABELLED, \
-    REC_PACKED = range(10)
+    REC_PACKED = range(10)   # N3D_CC_REC_COMPONENTS / N3D_CC_REC_KEPT / N3D_CC_REC_VOXELS_IN / N3D_CC_REC_VOXELS_KEPT / N3D_CC_REC_LARGEST_SIZE / N3D_CC_REC_LARGEST_ID / N3D_CC_REC_ET_IN / N3D_CC_REC_ET_KEPT / N3D_CC_REC_ET_RELABELLED / N3D_CC_REC_PACKED
 PHASES = ("local", "merge", "flatten", "decide_max", "decide_keep", "apply")     # N3D_CC_PHASES launches, in order
 TILED, GLOBAL_ONLY = 0, 1                                                       # N3D_CC_TILED / N3D_CC_GLOBAL_ONLY
 STAT_KEYS = ("n_components", "n_kept", "voxels_in", "voxels_kept", "largest_size", "largest_id", "et_in", "et_kept", "et_relabelled")
