@@ -554,6 +554,37 @@ int n3d_tversky_fwd(const float* p, int64_t psb, int64_t psc, int64_t psv, const
 int n3d_tversky_bwd(const float* t, int64_t tsb, int64_t tsc, int64_t tsv, int B, int C, int64_t N, const float* coef, const float* dloss,
                     float* dp, int64_t dsb, int64_t dsc, int64_t dsv, void* stream);
 
+/* ---- Boundary loss (Kervadec et al., MIDL 2019): loss = base + w * mean_bcv (p * phi), phi the signed distance map of the targets.
+ * Its gradient with respect to p is phi itself: one more sum per row in the head's forward pass, one more term of d logit in its
+ * backward pass.
+ * n3d_target_sdt: phi of B x C binary maps of D0 x D1 x D2 voxels (each extent 1..N3D_SDT_MAX_AXIS, B * C <= 65535; otherwise
+ *   N3D_ERR_UNSUPPORTED).  t: N3D_F32 or N3D_U8 holding {0, 1}, element (b, c, v) at t[b*tsb + c*tsc + v*tsv] with v the C-order
+ *   voxel index (the head's target operand); phi: fp32 with strides of its own.  With d2_fg(v) / d2_bg(v) the smallest squared
+ *   Euclidean index distance from v to a voxel of the same map with t = 1 / t = 0 (exact integers; only voxels of the patch count):
+ *     t(v) = 0:  phi = (float) sqrt((double) d2_fg)
+ *     t(v) = 1:  phi = (float) (-(sqrt((double) d2_bg) - 1.0))
+ *   -- scipy.ndimage.distance_transform_edt under one_hot2dist, bit for bit -- and phi = 0.0f where the wanted distance has no source
+ *   in the patch, so an empty map and a full map are all zero.
+ *   ws: n3d_target_sdt_workspace_bytes(B, C, D0, D1, D2) bytes (two int32 fields per map; 0 on a bad shape), 4-byte aligned, nothing
+ *   in it has to be cleared.  Three launches on the stream, integer minima, one writer per word: no host sync, same bits every run.
+ * n3d_head_bnd_fwd: n3d_head_loss_fwd (same operands, layouts and base loss l) plus phi and the device scalar bnd_weight:
+ *   *loss = base + w * mean_bcv (p * phi), w = *bnd_weight read by the finalize launch -- a schedule changes it between the replays
+ *   of a captured graph.  Co = 3 only (N3D_ERR_UNSUPPORTED otherwise).  The records gain one double at their END, sum p * phi:
+ *   partial: double[B][Co][n3d_head_rows(N)][S + 1], sums: double[B][Co][S + 1] with S of n3d_head_loss_fwd (3, or 4 with
+ *   bce_weight > 0).  coef: float[2 * B * Co + 2]: n3d_head_loss_fwd's 2 * B * Co + 1, then k_phi = w / (B Co N).
+ * n3d_head_bnd_bwd: n3d_head_loss_bwd plus phi: d loss / d z = (k2 t + k0 + k_phi phi) p (1 - p) + kb (p - t).
+ * There is no evaluation form: an evaluation reports the base loss (n3d_head_loss_eval), whose definition does not move. */
+#define N3D_SDT_MAX_AXIS 1024
+size_t n3d_target_sdt_workspace_bytes(int B, int C, int D0, int D1, int D2);
+int n3d_target_sdt(const void* t, int t_dtype, int64_t tsb, int64_t tsc, int64_t tsv, int B, int C, int D0, int D1, int D2, float* phi,
+                   int64_t fsb, int64_t fsc, int64_t fsv, void* ws, size_t ws_bytes, void* stream);
+int n3d_head_bnd_fwd(const n3d_head* h, const n3d_loss* l, float* p, int64_t psb, int64_t psc, int64_t psv, float* logits, const void* t,
+                     int64_t tsb, int64_t tsc, int64_t tsv, const float* phi, int64_t fsb, int64_t fsc, int64_t fsv, const float* bnd_weight,
+                     double* partial, double* sums, float* coef, float* loss, void* stream);
+int n3d_head_bnd_bwd(const n3d_head* h, const void* t, int64_t tsb, int64_t tsc, int64_t tsv, const float* phi, int64_t fsb, int64_t fsc,
+                     int64_t fsv, const float* coef, const float* dloss, void* dx, int64_t dxld, int dx_dtype, int flags, float* dw,
+                     float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred, void* stream);
+
 /* ---- layout: NCDHW <-> NDHWC (caller tensors arrive NCDHW: train.py:118-119) ---------------------- */
 int n3d_ncdhw_to_ndhwc(const float* src, float* dst, int64_t dld, int B, int C, int64_t N, void* stream);
 int n3d_ndhwc_to_ncdhw(const float* src, int64_t sld, float* dst, int B, int C, int64_t N, void* stream);

@@ -245,6 +245,12 @@ PROTOTYPES = {
     "n3d_head_loss_fwd": (_i, [C.POINTER(Head), C.POINTER(Loss), _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "n3d_head_loss_eval": (_i, [C.POINTER(Head), C.POINTER(Loss), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _f, _p, _p, _p, _p, _p, _p]),
     "n3d_head_loss_bwd": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _sz, C.POINTER(FinalJob), _p]),
+    "n3d_target_sdt_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "n3d_target_sdt": (_i, [_p, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _p, _i64, _i64, _i64, _p, _sz, _p]),
+    "n3d_head_bnd_fwd": (_i, [C.POINTER(Head), C.POINTER(Loss), _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p,
+                              _p, _p, _p, _p, _p]),
+    "n3d_head_bnd_bwd": (_i, [C.POINTER(Head), _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _sz,
+                              C.POINTER(FinalJob), _p]),
     "n3d_tversky_fwd": (_i, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i, _i, _i64, C.POINTER(Loss), _p, _p, _p, _p, _p]),
     "n3d_tversky_bwd": (_i, [_p, _i64, _i64, _i64, _i, _i, _i64, _p, _p, _p, _i64, _i64, _i64, _p]),
     "n3d_ncdhw_to_ndhwc": (_i, [_p, _p, _i64, _i, _i, _i64, _p]),

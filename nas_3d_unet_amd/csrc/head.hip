@@ -79,6 +79,10 @@ struct HeadFwdArgs {
   int t_quad;   // byte targets, dense and 4-aligned, whole chunks: a lane fetches FOUR voxels' bytes (head_target_quads)
   double* hpartial; float thr;   // evaluation form (EVAL): hard sums (sum [p >= thr] * t, sum [p >= thr]) per (b, c, row)
 };
+// the boundary form (BND) also reads the signed distance map phi of the targets (n3d_target_sdt), fp32 with strides of its own; the
+// other forms keep the argument record they had
+struct HeadFwdBndArgs : HeadFwdArgs { const float* phi; int64_t fsb, fsc, fsv; };
+template <bool BND> using HeadFwdArgsT = std::conditional_t<BND, HeadFwdBndArgs, HeadFwdArgs>;
 
 // thread = voxel; lanes walk consecutive voxels (x: Ci * sizeof(TX) contiguous bytes per voxel, p / t: strided per channel)
 // NCO: output channels computed per voxel -- 3 = exactly three (the reference's out_channels, config.yml: no fourth channel of zero
@@ -89,11 +93,13 @@ struct HeadFwdArgs {
 // prediction (prediction.py:157-164: p >= thr) per row; two compares and two adds per voxel and channel on an HBM-bound pass
 // BCE: the cross-entropy form (n3d_head_loss_fwd / _eval with bce_weight > 0) -- a FOURTH sum per row, the voxels' binary cross-entropy
 // from the logit, max(z, 0) - z t + log1p(exp(-|z|)); the partial records then hold S = 4 doubles
-template <typename TX, int CIQ, int NCO, typename TT = float, bool EVAL = false, bool BCE = false>
-__global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
+// BND: the boundary form (n3d_head_bnd_fwd) -- one more sum per row, sum p * phi, formed like the cross-entropy sum (fp32 per lane,
+// fp64 across) and stored LAST in the record: S = 4 without the cross-entropy term, 5 with it
+template <typename TX, int CIQ, int NCO, typename TT = float, bool EVAL = false, bool BCE = false, bool BND = false>
+__global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgsT<BND> a) {
   N3D_CHAIN_PRIO();
   constexpr int CI = CIQ * 4;
-  constexpr int S = BCE ? 4 : 3;              // sums per (b, c, row) record
+  constexpr int S = 3 + (BCE ? 1 : 0) + (BND ? 1 : 0);      // sums per (b, c, row) record
   constexpr bool ALL = NCO != HEAD_COMAX;     // every computed channel is a real one
   __shared__ float wsm[HEAD_COMAX][CI];
   __shared__ double red[HEAD_COMAX * S][4];
@@ -117,6 +123,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
 #pragma unroll
   for (int co = 0; co < HEAD_COMAX; ++co) shi[co] = shp[co] = 0.f;
   float sce[HEAD_COMAX] = {0.f, 0.f, 0.f, 0.f};     // BCE: cross-entropy
+  float sbd[HEAD_COMAX] = {0.f, 0.f, 0.f, 0.f};     // BND: p * phi
   const int64_t v0 = (int64_t)blockIdx.x * HEAD_CHUNK;
   // every operand of the workgroup's four voxel rounds is requested before the first use (predicated, no early exit: a `break` in
   // the loop kept each round's loads behind the previous round's stores -- 2.6 TB/s on a 37 MB pass)
@@ -126,6 +133,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
   const bool tquad = TU8 && a.t_quad;     // (uniform)
   float4 xqs[NK][CIQ];
   float tvs[NK][NCO];
+  float phs[BND ? NK : 1][NCO];
   uint32_t tq[NCO];
   if (tquad) head_target_quads_issue<NCO>(a.t, b * a.tsb + v0, a.tsc, tid, tq);
 #pragma unroll
@@ -138,6 +146,10 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
 #pragma unroll
       for (int co = 0; co < NCO; ++co)
         tvs[k][co] = (a.t && (ALL || co < a.Co)) ? (float)reinterpret_cast<const TT*>(a.t)[b * a.tsb + co * a.tsc + vc * a.tsv] : 0.f;
+    }
+    if constexpr (BND) {
+#pragma unroll
+      for (int co = 0; co < NCO; ++co) phs[k][co] = a.phi[b * a.fsb + co * a.fsc + vc * a.fsv];
     }
   }
   if (tquad) head_target_quads_take<NCO, NK>(tq, tql, tid, tvs);
@@ -171,6 +183,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
           shi[co] = fmaf(hard, tv[co], shi[co]); shp[co] += hard;
         }
         if constexpr (BCE) sce[co] += head_bce_voxel(z[co], en, tv[co]);
+        if constexpr (BND) sbd[co] = fmaf(pr, phs[k][co], sbd[co]);
       }
     }
   }
@@ -186,6 +199,10 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) {
     if constexpr (BCE) {
       const double d3 = wave_sum4_d(sce[0], sce[1], sce[2], sce[3]);
       if ((lane & 15) == 0) red[co * S + 3][wave] = d3;
+    }
+    if constexpr (BND) {
+      const double db = wave_sum4_d(sbd[0], sbd[1], sbd[2], sbd[3]);
+      if ((lane & 15) == 0) red[co * S + S - 1][wave] = db;
     }
   }
   __shared__ double hred[EVAL ? HEAD_COMAX * 2 : 1][4];
@@ -254,6 +271,10 @@ __device__ __forceinline__ void head_eval_add(const HeadEvalAcc& ev, int BC, con
 // is the cross-entropy sum), a pair's term is u^gamma + bce_weight * CE / N (tversky_term, n3d_common.h), the loss is the mean of the
 // terms, and the coefficients of the backward pass go to lf.coef: (k2, k0) per pair, then kb = bce_weight / (BC N)
 struct HeadLossFin { TverskySpec tv; double w, inv_n; float* coef; };
+// BND (n3d_head_bnd_fwd): the records end in sum p * phi; the weight is a device scalar read HERE, so a schedule moves it between
+// the replays of a captured step; coef gains k_phi = weight / (BC N) after kb, and the loss is base + k_phi * sum_bc sum p * phi
+struct HeadLossFinBnd : HeadLossFin { const float* bw; double n; };
+template <bool BND> using HeadLossFinT = std::conditional_t<BND, HeadLossFinBnd, HeadLossFin>;
 
 template <int S, bool TV>
 __device__ __forceinline__ double head_pair_term(const double* q, double smooth, const HeadLossFin& lf, int i, int BC) {
@@ -266,14 +287,22 @@ __device__ __forceinline__ double head_pair_term(const double* q, double smooth,
   }
 }
 
-template <bool EVAL = false, int S = 3, bool TV = false>
+template <bool EVAL = false, int S = 3, bool TV = false, bool BND = false>
 __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* __restrict__ partial, int rows, int BC, double smooth,
                                                                  double* __restrict__ sums, float* __restrict__ loss, HeadEvalAcc ev,
-                                                                 HeadLossFin lf) {
+                                                                 HeadLossFinT<BND> lf) {
+  static_assert(!BND || (TV && !EVAL), "head_dice_finalize: the boundary term rides on the loss form, and has no evaluation form");
+  constexpr int SB = BND ? S - 1 : S;     // doubles of the base loss's record
   __shared__ double ratio[256];
+  __shared__ double bsum[BND ? 256 : 1];
   __shared__ double red[64][S][4];
   if constexpr (TV) {
     if (threadIdx.x == 0 && lf.coef) lf.coef[2 * BC] = (float)(lf.w * lf.inv_n / BC);
+  }
+  double kphi = 0;
+  if constexpr (BND) {
+    kphi = (double)*lf.bw / ((double)BC * lf.n);
+    if (threadIdx.x == 0 && lf.coef) lf.coef[2 * BC + 1] = (float)kphi;
   }
   __shared__ double hred[EVAL ? 64 : 1][2][4];
   __shared__ double hs[EVAL ? 256 : 1][2];
@@ -328,7 +357,8 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
       double q[S];
 #pragma unroll
       for (int k = 0; k < S; ++k) { q[k] = (red[t][k][0] + red[t][k][1]) + (red[t][k][2] + red[t][k][3]); sums[t * S + k] = q[k]; }
-      r = head_pair_term<S, TV>(q, smooth, lf, t, BC);
+      r = head_pair_term<SB, TV>(q, smooth, lf, t, BC);
+      if constexpr (BND) bsum[t] = q[S - 1];
       if constexpr (EVAL) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) hs[t][k] = (hred[t][k][0] + hred[t][k][1]) + (hred[t][k][2] + hred[t][k][3]);
@@ -339,13 +369,18 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
     if (t == 0) {
       double a = 0;
       for (int i = 0; i < BC; ++i) a += ratio[i];
+      if constexpr (BND) {
+        double f = 0;
+        for (int i = 0; i < BC; ++i) f += bsum[i];
+        *loss = (float)(a / BC + kphi * f);
+      } else
       *loss = TV ? (float)(a / BC) : (float)(1.0 - a / BC);
       if constexpr (EVAL) head_eval_add<S>(ev, BC, hs, sums, loss);
     }
     return;
   }
   if constexpr (EVAL) head_eval_hard_walk(ev, rows, BC, hs);
-  double acc = 0;
+  double acc = 0, accf = 0;
   for (int i = wave; i < BC; i += 4) {
     double s[S] = {};
     for (int r = lane; r < rows; r += 64)
@@ -356,15 +391,22 @@ __global__ __launch_bounds__(256) void head_dice_finalize_kernel(const double* _
     if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < S; ++k) sums[i * S + k] = s[k];
-      acc += head_pair_term<S, TV>(s, smooth, lf, i, BC);
+      acc += head_pair_term<SB, TV>(s, smooth, lf, i, BC);
+      if constexpr (BND) accf += s[S - 1];
     }
   }
   ratio[t] = acc;
+  if constexpr (BND) bsum[t] = accf;
   __syncthreads();
   if (t == 0) {
     // (only lane 0 of each wave holds a value: the four adds below are the 256-entry sum without its zeros, bit for bit)
     double s = 0;
     for (int i = 0; i < 256; i += 64) s += ratio[i];
+    if constexpr (BND) {
+      double f = 0;
+      for (int i = 0; i < 256; i += 64) f += bsum[i];
+      *loss = (float)(s / BC + kphi * f);
+    } else
     *loss = TV ? (float)(s / BC) : (float)(1.0 - s / BC);
     if constexpr (EVAL) head_eval_add<S>(ev, BC, hs, sums, loss);
   }
@@ -380,13 +422,17 @@ struct HeadBwdArgs {
   float* partial; float* pbias; int chunks_per_sample; int Ci, Co;
   const float* coef;     // COEF: float[2 BC + 1] of the loss finalize (HeadLossFin)
 };
+struct HeadBwdBndArgs : HeadBwdArgs { const float* phi; int64_t fsb, fsc, fsv; };     // BND: coef holds 2 BC + 2 floats (k_phi last)
+template <bool BND> using HeadBwdArgsT = std::conditional_t<BND, HeadBwdBndArgs, HeadBwdArgs>;
 
 // thread = voxel.  d logit = dp * p * (1 - p) with p recomputed from x (no saved activations are read);
 // dx[ci] = gate[ci] * sum_co W[co][ci] * dlogit[co];  dW[co][ci] = gate[ci] * sum_v dlogit[co] * x[ci];  dbias[co] = sum_v dlogit[co]
 // COEF (n3d_head_loss_bwd): d loss / d p = k2 t + k0 with the pair's (k2, k0) as the loss finalize left them, and, when the
 // cross-entropy coefficient kb is not 0, d logit += kb (p - t); targets are given, dp and sums are not
-template <typename TX, typename TD, int CIQ, int NCO, typename TT = float, bool COEF = false>     // NCO, TT: as head_fwd_kernel
-__global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
+// BND (n3d_head_bnd_bwd, with COEF): d loss / d p += k_phi phi -- the boundary term's gradient is the distance map itself
+template <typename TX, typename TD, int CIQ, int NCO, typename TT = float, bool COEF = false, bool BND = false>     // NCO, TT: as head_fwd_kernel
+__global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgsT<BND> a) {
+  static_assert(!BND || COEF, "head_bwd: the boundary term rides on the coefficient form");
   N3D_CHAIN_PRIO();
   constexpr int CI = CIQ * 4, NV = HEAD_COMAX * CI + HEAD_COMAX;
   constexpr bool ALL = NCO != HEAD_COMAX;
@@ -403,6 +449,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
   const bool fusedloss = COEF || a.sums;     // (uniform) the loss gradient is formed here from the targets
   float bias[NCO], k2[NCO], k0[NCO], kb = 0.f;
   if constexpr (COEF) kb = a.coef[2 * a.BC] * (a.dloss ? *a.dloss : 1.f);
+  float kphi = 0.f;
+  if constexpr (BND) kphi = a.coef[2 * a.BC + 1] * (a.dloss ? *a.dloss : 1.f);
 #pragma unroll
   for (int co = 0; co < NCO; ++co) {
     bias[co] = (ALL || co < a.Co) ? a.bias[co] : 0.f;
@@ -443,6 +491,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
   const bool tquad = TU8 && a.t_quad && fusedloss;     // (uniform)
   float4 xqs[NK][CIQ];
   float gin[NK][NCO];
+  float phs[BND ? NK : 1][NCO];
   uint32_t tq[NCO];
   if (tquad) head_target_quads_issue<NCO>(a.t, b * a.tsb + v0, a.tsc, tid, tq);
 #pragma unroll
@@ -459,6 +508,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
           gin[k][co] = fusedloss ? (float)reinterpret_cast<const TT*>(a.t)[b * a.tsb + co * a.tsc + vc * a.tsv] : a.dp[b * a.dsb + co * a.dsc + vc * a.dsv];
       }
     }
+    if constexpr (BND) {
+#pragma unroll
+      for (int co = 0; co < NCO; ++co) phs[k][co] = a.phi[b * a.fsb + co * a.fsc + vc * a.fsv];
+    }
   }
   if (tquad) head_target_quads_take<NCO, NK>(tq, tql, tid, gin);
 #pragma unroll
@@ -471,6 +524,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
     for (int co = 0; co < NCO; ++co) {
       gp[co] = 0.f;
       if (ALL || co < a.Co) gp[co] = fusedloss ? fmaf(k2[co], gin[k][co], k0[co]) : gin[k][co];
+      if constexpr (BND) gp[co] = fmaf(kphi, phs[k][co], gp[co]);
     }
     float4 prevq[CIQ];
     if (a.accumulate) {
@@ -563,6 +617,37 @@ static bool launch_head_fwd(const HeadFwdArgs& a, int B, bool t_u8, hipStream_t 
   return true;
 }
 
+// the boundary forms: the three-channel head only
+template <typename TX, bool BCE>
+static bool launch_head_bnd_fwd(const HeadFwdBndArgs& a, int B, bool t_u8, hipStream_t s) {
+  const dim3 grid((unsigned)a.rows, (unsigned)B), blk(256);
+#define N3D_HEAD_BND_FWD(Q_)                                                                                      \
+  case Q_: if (t_u8) N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, uint8_t, false, BCE, true>), grid, blk, 0, s, a);     \
+           else N3D_LAUNCH((head_fwd_kernel<TX, Q_, 3, float, false, BCE, true>), grid, blk, 0, s, a);            \
+           break;
+  switch (a.Ci / 4) {
+    N3D_HEAD_BND_FWD(1) N3D_HEAD_BND_FWD(2) N3D_HEAD_BND_FWD(3) N3D_HEAD_BND_FWD(4) N3D_HEAD_BND_FWD(6) N3D_HEAD_BND_FWD(8)
+    default: return false;
+  }
+#undef N3D_HEAD_BND_FWD
+  return true;
+}
+
+template <typename TX, typename TD>
+static bool launch_head_bnd_bwd(const HeadBwdBndArgs& a, int B, bool t_u8, hipStream_t s) {
+  const dim3 grid((unsigned)a.chunks_per_sample, (unsigned)B), blk(256);
+#define N3D_HEAD_BND_BWD(Q_)                                                                                      \
+  case Q_: if (t_u8) N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3, uint8_t, true, true>), grid, blk, 0, s, a);       \
+           else N3D_LAUNCH((head_bwd_kernel<TX, TD, Q_, 3, float, true, true>), grid, blk, 0, s, a);              \
+           break;
+  switch (a.Ci / 4) {
+    N3D_HEAD_BND_BWD(1) N3D_HEAD_BND_BWD(2) N3D_HEAD_BND_BWD(3) N3D_HEAD_BND_BWD(4) N3D_HEAD_BND_BWD(6) N3D_HEAD_BND_BWD(8)
+    default: return false;
+  }
+#undef N3D_HEAD_BND_BWD
+  return true;
+}
+
 template <typename TX, typename TD, bool COEF = false>
 static bool launch_head_bwd(const HeadBwdArgs& a, int B, bool t_u8, hipStream_t s) {
   const dim3 grid((unsigned)a.chunks_per_sample, (unsigned)B), blk(256);
@@ -618,11 +703,13 @@ static HeadLossFin head_loss_fin(const n3d_loss* l, int64_t N, float* coef) {
   return HeadLossFin{tversky_spec(l), (double)l->bce_weight, 1.0 / (double)N, coef};
 }
 
-// what n3d_head_bwd (dp, or t and sums) and n3d_head_loss_bwd (t and coef) share: the one backward launch and the weight-gradient job
+// what n3d_head_bwd (dp, or t and sums), n3d_head_loss_bwd (t and coef) and n3d_head_bnd_bwd (t, coef and phi) share: the one backward
+// launch and the weight-gradient job
+struct HeadPhi { const float* phi; int64_t fsb, fsc, fsv; };
 static int head_bwd_run(const n3d_head* h, const char* what, const float* dp, int64_t dsb, int64_t dsc, int64_t dsv, const void* t, int64_t tsb,
                         int64_t tsc, int64_t tsv, float smooth, const double* sums, const float* coef, const float* dloss, void* dx,
                         int64_t dxld, int dx_dtype, int flags, float* dw, float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred,
-                        void* stream) {
+                        void* stream, HeadPhi ph = HeadPhi{}) {
   N3D_CHECK_ARG(dx && dxld >= (h->node_c ? h->node_c : h->Ci) && dxld % 4 == 0 && (!h->node_c || h->dx_node_stride % 4 == 0), "%s: bad dx", what);
   N3D_CHECK_ARG(dx_dtype == N3D_F32 || dx_dtype == N3D_BF16, "%s: unknown dx dtype", what);
   // (the kernel stores a channel quad per st4: 16 bytes, 8 in bf16 -- the alignment check_head asks of x)
@@ -648,7 +735,13 @@ static int head_bwd_run(const n3d_head* h, const char* what, const float* dp, in
   const bool u8 = !dp && h->t_dtype == N3D_U8;
   a.t_quad = u8 && tsv == 1 && h->N % HEAD_CHUNK == 0 && tsb % 4 == 0 && tsc % 4 == 0 && reinterpret_cast<uintptr_t>(t) % 4 == 0;
   const bool xb = h->x_dtype == N3D_BF16, db = dx_dtype == N3D_BF16;
-  if (coef) {
+  if (ph.phi) {
+    HeadBwdBndArgs ab;
+    static_cast<HeadBwdArgs&>(ab) = a;
+    ab.phi = ph.phi; ab.fsb = ph.fsb; ab.fsc = ph.fsc; ab.fsv = ph.fsv;
+    if (xb) ok = db ? launch_head_bnd_bwd<bf16_t, bf16_t>(ab, h->B, u8, s) : launch_head_bnd_bwd<bf16_t, float>(ab, h->B, u8, s);
+    else ok = db ? launch_head_bnd_bwd<float, bf16_t>(ab, h->B, u8, s) : launch_head_bnd_bwd<float, float>(ab, h->B, u8, s);
+  } else if (coef) {
     if (xb) ok = db ? launch_head_bwd<bf16_t, bf16_t, true>(a, h->B, u8, s) : launch_head_bwd<bf16_t, float, true>(a, h->B, u8, s);
     else ok = db ? launch_head_bwd<float, bf16_t, true>(a, h->B, u8, s) : launch_head_bwd<float, float, true>(a, h->B, u8, s);
   } else if (xb) ok = db ? launch_head_bwd<bf16_t, bf16_t>(a, h->B, u8, s) : launch_head_bwd<bf16_t, float>(a, h->B, u8, s);
@@ -772,6 +865,46 @@ int n3d_head_loss_eval(const n3d_head* h, const n3d_loss* l, float* p, int64_t p
   }
   N3D_LAUNCH_CHECK();
   return N3D_OK;
+}
+
+int n3d_head_bnd_fwd(const n3d_head* h, const n3d_loss* l, float* p, int64_t psb, int64_t psc, int64_t psv, float* logits, const void* t,
+                     int64_t tsb, int64_t tsc, int64_t tsv, const float* phi, int64_t fsb, int64_t fsc, int64_t fsv, const float* bnd_weight,
+                     double* partial, double* sums, float* coef, float* loss, void* stream) {
+  if (int e = check_head(h, "head_bnd_fwd")) return e;
+  if (int e = check_loss(l, "head_bnd_fwd")) return e;
+  N3D_CHECK_ARG(t && phi && bnd_weight && partial && sums && coef && loss, "head_bnd_fwd: needs t, phi, bnd_weight, partial, sums, coef and loss");
+  if (h->Co != 3) N3D_UNSUPPORTED("head_bnd_fwd: the boundary term is built for Co = 3 (Co=%d)", h->Co);
+  HeadFwdBndArgs a;
+  static_cast<HeadFwdArgs&>(a) = head_fwd_args(h, h->gate, p, psb, psc, psv, logits, t, tsb, tsc, tsv, partial, nullptr, 0.f);
+  a.phi = phi; a.fsb = fsb; a.fsc = fsc; a.fsv = fsv;
+  hipStream_t s = (hipStream_t)stream;
+  const bool u8 = h->t_dtype == N3D_U8, xb = h->x_dtype == N3D_BF16, bce = l->bce_weight > 0.f;
+  HeadLossFinBnd lf;
+  static_cast<HeadLossFin&>(lf) = head_loss_fin(l, h->N, coef);
+  lf.bw = bnd_weight; lf.n = (double)h->N;
+  const int BC = h->B * h->Co;
+  if (bce) {
+    if (!(xb ? launch_head_bnd_fwd<bf16_t, true>(a, h->B, u8, s) : launch_head_bnd_fwd<float, true>(a, h->B, u8, s)))
+      N3D_UNSUPPORTED("head_bnd_fwd: Ci=%d", h->Ci);
+    N3D_LAUNCH((head_dice_finalize_kernel<false, 5, true, true>), dim3(1), dim3(256), 0, s, partial, a.rows, BC, lf.tv.smooth, sums, loss, HeadEvalAcc{}, lf);
+  } else {
+    if (!(xb ? launch_head_bnd_fwd<bf16_t, false>(a, h->B, u8, s) : launch_head_bnd_fwd<float, false>(a, h->B, u8, s)))
+      N3D_UNSUPPORTED("head_bnd_fwd: Ci=%d", h->Ci);
+    N3D_LAUNCH((head_dice_finalize_kernel<false, 4, true, true>), dim3(1), dim3(256), 0, s, partial, a.rows, BC, lf.tv.smooth, sums, loss, HeadEvalAcc{}, lf);
+  }
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_head_bnd_bwd(const n3d_head* h, const void* t, int64_t tsb, int64_t tsc, int64_t tsv, const float* phi, int64_t fsb, int64_t fsc,
+                     int64_t fsv, const float* coef, const float* dloss, void* dx, int64_t dxld, int dx_dtype, int flags, float* dw,
+                     float* dbias, void* ws, size_t ws_bytes, n3d_final_job* deferred, void* stream) {
+  if (deferred) deferred->nchunks = 0;
+  if (int e = check_head(h, "head_bnd_bwd")) return e;
+  N3D_CHECK_ARG(t && phi && coef, "head_bnd_bwd: needs the targets, their distance map and the coefficients of n3d_head_bnd_fwd");
+  if (h->Co != 3) N3D_UNSUPPORTED("head_bnd_bwd: the boundary term is built for Co = 3 (Co=%d)", h->Co);
+  return head_bwd_run(h, "head_bnd_bwd", nullptr, 0, 0, 0, t, tsb, tsc, tsv, 0.f, nullptr, coef, dloss, dx, dxld, dx_dtype, flags, dw, dbias, ws,
+                      ws_bytes, deferred, stream, HeadPhi{phi, fsb, fsc, fsv});
 }
 
 int n3d_head_bwd(const n3d_head* h, const float* dp, int64_t dsb, int64_t dsc, int64_t dsv, const void* t, int64_t tsb, int64_t tsc,

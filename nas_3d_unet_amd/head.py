@@ -5,6 +5,8 @@ dropout_rate=p, ops_order='weight'), nn.Sigmoid())`, and loss.py:12-14 behind it
 `run_loss(head, x, t, smooth)` additionally forms the Dice sums in the forward pass and the Dice gradient inside the
 backward pass, so the trainers' step has no separate sigmoid / Dice passes over (B, n_out, D, H, W).
 `run_loss(..., loss=TverskyBCELoss(...))` forms the Tversky / focal / cross-entropy loss in the same two passes (n3d_head_loss_fwd / _bwd).
+`run_loss(..., loss=BoundaryLoss(...))` first forms the targets' signed distance map on the current stream (n3d_target_sdt), then the base
+loss plus the boundary term in the same two passes (n3d_head_bnd_fwd / _bwd); `run_eval` with a BoundaryLoss evaluates its base loss.
 `run_eval(head, x, t, acc)` is the evaluation form (n3d_head_eval, no autograd): eval-mode head, Dice loss and the region counts of
 the thresholded prediction in one pass, added into a device accumulator that `eval_figures` turns into an `EvalResult`.
 The modules (and their state-dict names `last_conv.0.conv.*`) stay the reference's; only what runs underneath differs.
@@ -133,18 +135,80 @@ class HeadLossFn(torch.autograd.Function):
         return None, None, dx.t, None, None if inplace else dw, None if inplace else db
 
 
+class HeadBndFn(torch.autograd.Function):
+    """HeadLossFn for a loss.BoundaryLoss `bnd` (n3d_head_bnd_fwd / n3d_head_bnd_bwd) and the distance map phi of t: the same `skip_p`
+    contract"""
+
+    @staticmethod
+    def forward(ctx, gate, bnd, phi, x, t, w, b):
+        global last_logits
+        xv = _feat_view(x)
+        if K._bcv_strides(t) is None:
+            t = t.contiguous()
+        want_p = KEEP_LOGITS or not getattr(ctx, "skip_p", False)
+        p, logits, _, coef, loss = K.head_bnd_fwd(xv, w, b, gate, t, phi, bnd.spec, bnd.weight_tensor(t.device), want_logits=KEEP_LOGITS,
+                                                  want_p=want_p)
+        if KEEP_LOGITS:
+            last_logits = logits
+        ctx.xv, ctx.gate, ctx.w, ctx.b, ctx.t, ctx.phi, ctx.coef = xv, gate, w, b, t, phi, coef
+        if p is not None:
+            ctx.mark_non_differentiable(p)
+        return loss, p
+
+    @staticmethod
+    def backward(ctx, dloss, _dp):
+        xv, w, b = ctx.xv, ctx.w, ctx.b
+        dx = _feat_like(xv)
+        dw, db = K.grad_target(w), K.grad_target(b)
+        K.head_bnd_bwd(xv, w, b, ctx.gate, dx, dw, db, ctx.t, ctx.phi, ctx.coef, dloss=dloss.contiguous())
+        inplace = getattr(w, "_n3d_grad", None) is not None
+        ctx.xv = ctx.t = ctx.phi = None
+        return None, None, None, dx.t, None, None if inplace else dw, None if inplace else db
+
+
+def _is_boundary(loss):
+    from .loss import BoundaryLoss
+    return isinstance(loss, BoundaryLoss)
+
+
+def target_phi(loss, t):
+    """the signed distance map of the targets t for the loss.BoundaryLoss `loss`, on the current stream: the map a trainer formed at the
+    start of its step for this very tensor (loss.prepared), or a new one"""
+    prep = getattr(loss, "prepared", None)
+    if prep is not None and prep[0] is t:
+        loss.prepared = None
+        return prep[1]
+    return K.target_sdt(t)
+
+
+def prepare_phi(loss, t):
+    """trainers: form phi of t now -- at the start of the step, on the main chain -- for the head that runs at its end"""
+    if _is_boundary(loss):
+        loss.prepared = (t, K.target_sdt(t))
+
+
 def _dice_like(loss):
     """is `loss` (None, a loss.WeightedDiceLoss or a loss.TverskyBCELoss) the Dice loss of the existing entry points?"""
-    from .loss import TverskyBCELoss, WeightedDiceLoss
+    from .loss import BoundaryLoss, TverskyBCELoss, WeightedDiceLoss
     if loss is None or isinstance(loss, WeightedDiceLoss):
         return True
-    if not isinstance(loss, TverskyBCELoss):
-        raise K.N3DError("head: loss must be a WeightedDiceLoss or a TverskyBCELoss (got %s)" % type(loss).__name__)
+    if not isinstance(loss, (TverskyBCELoss, BoundaryLoss)):
+        raise K.N3DError("head: loss must be a WeightedDiceLoss, a TverskyBCELoss or a BoundaryLoss (got %s)" % type(loss).__name__)
     return False
 
 
 def check_loss_head(head, loss):
-    """raise unless the head can form `loss`: a cross-entropy term (bce_weight > 0) is built inside the fused three-channel head only"""
+    """raise unless the head can form `loss`: a cross-entropy term (bce_weight > 0) and the boundary term of a BoundaryLoss are built
+    inside the fused three-channel head only"""
+    if _is_boundary(loss):
+        op = head[0]
+        ci, co = op.conv.weight.shape[1], op.conv.weight.shape[0]
+        if co != 3:
+            raise K.N3DError("BoundaryLoss: the boundary kernels are built for a three-channel head (out_channels=%d)" % co)
+        if not fusable(head, torch.empty((1, ci, 1, 1, 1), device="meta")):
+            raise K.N3DError("BoundaryLoss: the boundary term is formed inside the fused head, and this head is not one it takes "
+                             "(1x1x1 conv of 4..32 channels to 3, sigmoid; %d -> %d here)" % (ci, co))
+        return
     if _dice_like(loss) or not loss.bce_weight > 0:
         return
     op = head[0]
@@ -167,7 +231,8 @@ def run(head, x):
 
 def run_loss(head, x, t, smooth=1e-6, loss=None):
     """(loss, probabilities) of the head on features x against the target t.  loss: None or a WeightedDiceLoss -- the Dice loss with
-    `smooth` -- or a TverskyBCELoss, which carries its own smooth.  The probabilities are returned for
+    `smooth` -- or a TverskyBCELoss, which carries its own smooth, or a BoundaryLoss: the signed distance map of t is formed on the
+    current stream first, and the fused head adds weight * mean(p * phi) to the BoundaryLoss's base loss.  The probabilities are returned for
     inspection only and carry NO gradient on either path (the fused kernels form the loss gradient inside the head's backward
     pass): a caller who wants another loss on them uses run() and differentiates through that."""
     fused = fusable(head, x)
@@ -175,6 +240,11 @@ def run_loss(head, x, t, smooth=1e-6, loss=None):
     dice = _dice_like(loss)
     if not dice:
         check_loss_head(head, loss)
+    if _is_boundary(loss):
+        if not fused or not (t.dtype == torch.float32 or byte_ok):
+            raise K.N3DError("BoundaryLoss: the fused three-channel head forms it from float32 or uint8 {0, 1} targets (got %s)" % t.dtype)
+        op = head[0]
+        return HeadBndFn.apply(_gate(op, x), loss, target_phi(loss, t), x, t, op.conv.weight, op.conv.bias)
     if not fused or not (t.dtype == torch.float32 or byte_ok):
         from .loss import WeightedDiceLoss
         if not dice and loss.bce_weight > 0:
@@ -218,8 +288,14 @@ def eval_figures(acc):
 def run_eval(head, x, t, acc, smooth=1e-6, thr=0.5, loss=None):
     """eval-mode head on features x (no Dropout3d, no autograd): the loss against t -- bit for bit run_loss's in eval mode, Dice or
     the TverskyBCELoss `loss` -- with the region counts of p >= thr, both added into acc (kernels.eval_acc).  Returns the batch loss
-    (0-d device tensor).  Only the fused head kernel takes this path: another head shape is an error."""
+    (0-d device tensor).  Only the fused head kernel takes this path: another head shape is an error.
+    A BoundaryLoss is evaluated as its BASE loss: the boundary weight moves during training, so the figure a plateau scheduler steps
+    on, and the one compared between epochs, must be a loss whose definition does not."""
     op = head[0]
+    if _is_boundary(loss):
+        check_loss_head(head, loss)
+        loss = loss.base
+        smooth = getattr(loss, "smooth", smooth)
     if not fusable(head, x):
         raise K.N3DError("evaluate: the head is not one the fused evaluation kernel takes (1x1x1 conv of 4..32 channels to <= 4, sigmoid)")
     if not (t.dtype == torch.float32 or (t.dtype == torch.uint8 and op.conv.weight.shape[0] == 3)):

@@ -1903,6 +1903,87 @@ def head_loss_bwd(x, w, bias, gate, dx, dw, dbias, t, coef, dloss=None, accumula
         _ctx.keep.append(ws)
 
 
+SDT_MAX_AXIS = 1024  # N3D_SDT_MAX_AXIS
+_sdt_ws = {}
+
+
+def target_sdt(t, out=None):
+    """signed distance maps phi of (B, C, D0, D1, D2) targets (n3d_target_sdt; float32 or uint8 {0, 1}, any uniformly strided view):
+    sqrt(d2 to the nearest foreground voxel) on the background, -(sqrt(d2 to the nearest background voxel) - 1) on the foreground, 0
+    where the patch holds no such voxel.  out: a float32 tensor of t's shape (uniformly strided) to write into.  The scratch is kept
+    per (device, shape): the launches of one stream reuse it in order, and a captured graph keeps its address."""
+    lib = _lib.load()
+    if t.dim() != 5 or not t.is_cuda:
+        raise N3DError("target_sdt: (B, C, D0, D1, D2) device targets expected (got %s on %s)" % (tuple(t.shape), t.device))
+    td = _target_dtype(t)
+    if _bcv_strides(t) is None:
+        t = t.contiguous()
+    B, Cc, D0, D1, D2 = (int(v) for v in t.shape)
+    if out is None:
+        out = torch.empty((B, Cc, D0, D1, D2), dtype=torch.float32, device=t.device)
+    if out.shape != t.shape or out.dtype != torch.float32 or out.device != t.device or _bcv_strides(out) is None:
+        raise N3DError("target_sdt: out must be a uniformly strided float32 tensor of the targets' shape on their device")
+    n = int(lib.n3d_target_sdt_workspace_bytes(B, Cc, D0, D1, D2))
+    if n == 0:
+        raise N3DError("target_sdt: B * C <= 65535 maps with extents 1..%d are built (got %s)" % (SDT_MAX_AXIS, tuple(t.shape)))
+    key = (t.device, B, Cc, D0, D1, D2)
+    ws = _sdt_ws.get(key)
+    if ws is None:
+        ws = _sdt_ws[key] = torch.empty(n, dtype=torch.uint8, device=t.device)
+    ts, fs = _bcv_strides(t), _bcv_strides(out)
+    check(lib.n3d_target_sdt(ptr(t), td, ts[0], ts[1], ts[2], B, Cc, D0, D1, D2, ptr(out), fs[0], fs[1], fs[2], ptr(ws), n, stream_ptr()),
+          "n3d_target_sdt")
+    return out
+
+
+def head_bnd_fwd(x, w, bias, gate, t, phi, spec, bnd_weight, want_logits=False, want_p=True):
+    """head_loss_fwd with the boundary term (n3d_head_bnd_fwd): loss = base(spec) + w * mean(p * phi), w the device scalar bnd_weight
+    (float32, one element), phi = target_sdt(t).  Returns (p | None, logits | None, sums (B, Co, S + 1: sum p * phi last),
+    coef (2 B Co + 2 floats for head_bnd_bwd: k_phi last), loss)."""
+    lib = _lib.load()
+    h = _head_desc(x, w, bias, gate, t=t)
+    dev = x.t.device
+    Co, S = int(w.shape[0]), _loss_sums(spec) + 1
+    if want_logits and not want_p:
+        raise N3DError("head_bnd_fwd: the logits are stored next to the probabilities")
+    if phi.dtype != torch.float32 or phi.shape != t.shape or _bcv_strides(phi) is None:
+        raise N3DError("head_bnd_fwd: phi must be a uniformly strided float32 tensor of the targets' shape")
+    if bnd_weight.dtype != torch.float32 or bnd_weight.numel() != 1 or bnd_weight.device != dev:
+        raise N3DError("head_bnd_fwd: bnd_weight is a one-element float32 tensor on the head's device")
+    p = torch.empty((x.B, Co, x.D, x.H, x.W), dtype=torch.float32, device=dev) if want_p else None
+    logits = torch.empty_like(p) if want_logits else None
+    ts, fs = _bcv_strides(t), _bcv_strides(phi)
+    partial = torch.empty((x.B, Co, int(lib.n3d_head_rows(x.N)), S), dtype=torch.float64, device=dev)
+    sums = torch.empty((x.B, Co, S), dtype=torch.float64, device=dev)
+    coef = torch.empty(2 * x.B * Co + 2, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    l = loss_record(spec)
+    check(lib.n3d_head_bnd_fwd(C.byref(h), C.byref(l), ptr(p), Co * x.N, x.N, 1, ptr(logits), ptr(t), ts[0], ts[1], ts[2], ptr(phi), fs[0],
+                               fs[1], fs[2], ptr(bnd_weight), ptr(partial), ptr(sums), ptr(coef), ptr(loss), stream_ptr()), "n3d_head_bnd_fwd")
+    return p, logits, sums, coef, loss
+
+
+def head_bnd_bwd(x, w, bias, gate, dx, dw, dbias, t, phi, coef, dloss=None, accumulate=False):
+    """backward of head_bnd_fwd in one pass (n3d_head_bnd_bwd): dx (+)=, dw, dbias from the targets, phi and the forward's coefficients"""
+    lib = _lib.load()
+    h = _head_desc(x, w, bias, gate, dx if isinstance(x, Planar) else None, t=t)
+    ws = None
+    n = 0
+    job = None
+    if dw is not None or dbias is not None:
+        n = int(lib.n3d_head_workspace_bytes(C.byref(h)))
+        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=x.t.device)
+        job = FinalJob() if _ctx is not None else None
+    ts, fs = _bcv_strides(t), _bcv_strides(phi)
+    check(lib.n3d_head_bnd_bwd(C.byref(h), ptr(t), ts[0], ts[1], ts[2], ptr(phi), fs[0], fs[1], fs[2], ptr(coef), ptr(dloss),
+                               dx.nodes[0].p if isinstance(dx, Planar) else dx.p, dx.cn if isinstance(dx, Planar) else dx.ld, dx.dt,
+                               ACCUMULATE if accumulate else 0, ptr(dw), ptr(dbias), ptr(ws), n,
+                               C.byref(job) if job is not None else None, stream_ptr()), "n3d_head_bnd_bwd")
+    if job is not None and job.nchunks > 0:
+        _ctx.final.append(job)
+        _ctx.keep.append(ws)
+
+
 def tversky_fwd(p, t, spec):
     """Tversky / focal loss on probabilities (n3d_tversky_fwd): (loss, sums (B, C, 3), coef (2 B C floats for tversky_bwd))"""
     lib = _lib.load()

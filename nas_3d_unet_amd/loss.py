@@ -82,6 +82,81 @@ class TverskyBCELoss(nn.Module):
         return _TverskyFn.apply(y_pred, y_truth, self)
 
 
+class BoundaryLoss(nn.Module):
+    """base + weight * mean_{b,c,v} (p * phi): the boundary loss of Kervadec et al. (MIDL 2019) on top of a region loss.  phi is the
+    signed distance map of the targets, formed on the device from every batch (`signed_distance`): the Euclidean distance to the nearest
+    foreground voxel on the background, -(the distance to the nearest background voxel - 1) on the foreground -- scipy's
+    distance_transform_edt under one_hot2dist, bit for bit -- and 0 where the patch holds no voxel of the wanted kind, so an empty map
+    and a full map contribute nothing.
+
+    base: None (WeightedDiceLoss()), a WeightedDiceLoss or a TverskyBCELoss.  weight >= 0 lives in a one-element device tensor that the
+    head's loss launch reads: `set_weight(w)` (or a trainer's `set_boundary_weight(w)`) moves it between the replays of a captured
+    step without a recapture -- the usual schedule raises it as training goes on.
+
+    The term is formed inside the fused three-channel head (Trainer(loss=...), SearchTrainer(loss=...), forward_loss(..., loss=...)).
+    `evaluate()` reports `base` alone: the weight moves during training, and a plateau scheduler must step on a loss whose definition
+    does not.  Called as a module on probabilities it raises N3DError."""
+
+    def __init__(self, base=None, weight=0.01):
+        super().__init__()
+        if base is None:
+            base = WeightedDiceLoss()
+        if not isinstance(base, (WeightedDiceLoss, TverskyBCELoss)):
+            raise TypeError("BoundaryLoss: base must be None, a WeightedDiceLoss or a TverskyBCELoss (got %s)" % type(base).__name__)
+        if not weight >= 0:
+            raise ValueError("BoundaryLoss: weight >= 0 is required (weight=%r)" % (weight,))
+        self.base = base
+        self.weight = float(weight)
+        self._wdev = None
+        self.prepared = None      # (targets, their phi) a trainer formed at the start of its step (head.prepare_phi)
+
+    @property
+    def spec(self):
+        """the base loss as the head's loss kernels take it (a TverskyBCELoss; the Dice loss with smooth s is alpha = beta = 0.5,
+        gamma = 1, smooth = s / 2)"""
+        b = self.base
+        if isinstance(b, TverskyBCELoss):
+            return b
+        sp = getattr(self, "_dice_spec", None)
+        if sp is None or sp.smooth != float(b.smooth) / 2:
+            sp = self._dice_spec = TverskyBCELoss(0.5, 0.5, 1.0, 0.0, float(b.smooth) / 2)
+        return sp
+
+    @property
+    def smooth(self):
+        return self.base.smooth
+
+    def set_weight(self, w):
+        """move the weight: fills the device scalar in place (no recapture of a captured step that reads it)"""
+        if not w >= 0:
+            raise ValueError("BoundaryLoss: weight >= 0 is required (weight=%r)" % (w,))
+        self.weight = float(w)
+        if self._wdev is not None:
+            self._wdev.fill_(self.weight)
+
+    def weight_tensor(self, device):
+        """the device scalar the head reads, created on first use on the targets' device"""
+        if self._wdev is None or self._wdev.device != device:
+            self._wdev = torch.full((1,), self.weight, dtype=torch.float32, device=device)
+        return self._wdev
+
+    @staticmethod
+    def signed_distance(t):
+        """phi of (B, C, D0, D1, D2) targets, float32 or uint8 {0, 1}, on their device (kernels.target_sdt)"""
+        if not t.is_cuda:
+            raise N3DError("BoundaryLoss.signed_distance: targets are on %s; no CPU fallback" % t.device)
+        return K.target_sdt(t)
+
+    def forward(self, y_pred, y_truth):
+        raise N3DError("BoundaryLoss: the boundary term is formed inside the fused head, next to the targets' distance map, and has no "
+                       "form on probabilities: train through Trainer(loss=...) or forward_loss(..., loss=...)")
+
+
+def signed_distance(t):
+    """signed distance maps of (B, C, D0, D1, D2) targets: BoundaryLoss.signed_distance"""
+    return BoundaryLoss.signed_distance(t)
+
+
 class WeightedDiceLoss(nn.Module):
     """1 - mean_{b,c} (2*sum(p*t)+eps) / (sum(p)+sum(t)+eps), sums over the last three dims."""
 

@@ -66,7 +66,7 @@ class ShellNet(nn.Module):
 
     def forward_loss(self, x, t, smooth=1e-6, *, loss=None):
         """(Dice loss, probabilities) with the loss formed inside the head's launches (search.py:224-226,233-235);
-        loss: a loss.TverskyBCELoss to form that loss there instead"""
+        loss: a loss.TverskyBCELoss or loss.BoundaryLoss to form that loss there instead"""
         return self.kernel.forward_loss(x, t, *self._soft(), smooth=smooth, loss=loss)
 
     def get_gene(self):

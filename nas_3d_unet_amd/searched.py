@@ -61,7 +61,7 @@ class SearchedNet(nn.Module):
 
     def forward_loss(self, x, t, smooth=1e-6, *, loss=None):
         """(Dice loss of loss.py:12-14, probabilities) with the loss formed inside the head's launches (train.py:121-124);
-        loss: a loss.TverskyBCELoss to form that loss there instead"""
+        loss: a loss.TverskyBCELoss or loss.BoundaryLoss to form that loss there instead"""
         if self._n3d_padded:
             return unet.run_padded(self, x, None, t, smooth, loss=loss)
         return unet.run_loss(self, x, t, None, smooth, loss=loss)

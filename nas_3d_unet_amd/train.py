@@ -28,7 +28,7 @@ import torch.distributed as dist
 from . import comm as _comm
 from . import fused as _fused
 from . import kernels as K
-from .loss import TverskyBCELoss, WeightedDiceLoss
+from .loss import BoundaryLoss, TverskyBCELoss, WeightedDiceLoss
 
 
 def _loss_of(model, loss_fn, x, t):
@@ -36,22 +36,25 @@ def _loss_of(model, loss_fn, x, t):
     fl = getattr(model, "forward_loss", None)
     if fl is not None and isinstance(loss_fn, WeightedDiceLoss):
         return fl(x, t, loss_fn.smooth)[0]
-    if fl is not None and isinstance(loss_fn, TverskyBCELoss):
+    if fl is not None and isinstance(loss_fn, (TverskyBCELoss, BoundaryLoss)):
         return fl(x, t, loss=loss_fn)[0]
     return loss_fn(model(x), t)
 
 
 def _trainer_loss(loss, kernel):
     """the loss a trainer trains `kernel` with: WeightedDiceLoss() by default, or the caller's WeightedDiceLoss / TverskyBCELoss -- whose
-    cross-entropy term needs the fused three-channel head (head.check_loss_head raises with the reason)"""
+    cross-entropy term needs the fused three-channel head (head.check_loss_head raises with the reason) --, or a BoundaryLoss, whose
+    boundary term needs that head too"""
     if loss is None:
         return WeightedDiceLoss()
-    if not isinstance(loss, (WeightedDiceLoss, TverskyBCELoss)):
-        raise TypeError("loss must be a WeightedDiceLoss or a TverskyBCELoss (got %s)" % type(loss).__name__)
+    if not isinstance(loss, (WeightedDiceLoss, TverskyBCELoss, BoundaryLoss)):
+        raise TypeError("loss must be a WeightedDiceLoss, a TverskyBCELoss or a BoundaryLoss (got %s)" % type(loss).__name__)
     from . import head as _head
     head = getattr(kernel, "last_conv", None)
     if head is not None:
         _head.check_loss_head(head, loss)
+    elif isinstance(loss, BoundaryLoss):
+        raise K.N3DError("BoundaryLoss: the boundary term is formed inside the fused head, and this model has no `last_conv` head")
     elif isinstance(loss, TverskyBCELoss) and loss.bce_weight > 0:
         raise K.N3DError("TverskyBCELoss(bce_weight=%g): the cross-entropy term is formed inside the fused head, and this model has no "
                          "`last_conv` head" % loss.bce_weight)
@@ -1011,6 +1014,8 @@ class _GraphTrainer:
         self.loss_fn = _trainer_loss(loss, kernel if self._twin is None else self._twin.twin)
         self.lr, self.betas, self.eps = lr, betas, eps
         self.device = next(model.parameters()).device
+        if isinstance(self.loss_fn, BoundaryLoss):
+            self.loss_fn.weight_tensor(self.device)     # the device scalar exists before any capture reads it
         # evaluation pass (evaluate / eval_result): its accumulator, weight packing, and captured graph with its input buffers
         self._eval_acc = None
         self._eval_ctx = None
@@ -1097,6 +1102,18 @@ class _GraphTrainer:
             else:
                 sync.header[:1].zero_()
         sync.all_reduce()
+
+    def set_boundary_weight(self, w):
+        """move the weight of the trainer's BoundaryLoss: a device scalar the captured step reads, so nothing is recaptured"""
+        if not isinstance(self.loss_fn, BoundaryLoss):
+            raise K.N3DError("set_boundary_weight: this trainer's loss is a %s, not a BoundaryLoss" % type(self.loss_fn).__name__)
+        self.loss_fn.set_weight(w)
+
+    def _prepare_loss(self, t):
+        """start of a pass, on the main chain: the signed distance map of the targets for a BoundaryLoss (nothing for another loss)"""
+        if isinstance(self.loss_fn, BoundaryLoss):
+            from . import head as _head
+            _head.prepare_phi(self.loss_fn, t)
 
     def _guard(self, loss, sync):
         """UpdateGuard of an optimizer launch on sync's gradients (None without a side schedule: nothing can time out)"""
@@ -1475,6 +1492,7 @@ class Trainer(_GraphTrainer):
     # -- pieces ---------------------------------------------------------------------------------
     def _fwd_bwd(self, x, t):
         with K.step_context(self.ctx):
+            self._prepare_loss(t)
             self.ctx.pack_all()            # one launch packs every conv weight for this step
             loss = _loss_of(self.net, self.loss_fn, x, t)
             with _fused.switched(REUSE_GRAD_OUTPUT=True):   # this backward is all ours (no hooks, no retain)
@@ -1495,6 +1513,7 @@ class Trainer(_GraphTrainer):
             plan = m._net_plan = _fused.net_plan(m, supernet=False)
         op = m.last_conv[0]
         with torch.no_grad(), K.step_context(self.ctx):
+            phi = K.target_sdt(t) if isinstance(self.loss_fn, BoundaryLoss) else None     # at the start of the step, on the main chain
             self.ctx.pack_all()
             nctx = _Ctx((False, False) + (False,) * 4 + (True,) * len(plan.params))
             with _fused.switched(PLANAR_OUT=_fused.PLANAR_LAST):     # (_direct_ok: the head is the fused one)
@@ -1502,7 +1521,12 @@ class Trainer(_GraphTrainer):
             gate = _P.draw_gate(op.dropout, op.training, *_head.feat_shape(body), body.device)
             hctx = _Ctx((False, False, True, False, True, True))
             hctx.skip_p = True        # the step returns the loss only: the head does not write the probabilities
-            if isinstance(self.loss_fn, TverskyBCELoss):
+            if phi is not None:
+                hctx = _Ctx((False, False, False, True, False, True, True))
+                hctx.skip_p = True
+                loss, _ = _head.HeadBndFn.forward(hctx, gate, self.loss_fn, phi, body, t, op.conv.weight, op.conv.bias)
+                dbody = _head.HeadBndFn.backward(hctx, self._one, None)[3]
+            elif isinstance(self.loss_fn, TverskyBCELoss):
                 loss, _ = _head.HeadLossFn.forward(hctx, gate, self.loss_fn, body, t, op.conv.weight, op.conv.bias)
                 dbody = _head.HeadLossFn.backward(hctx, self._one, None)[2]
             else:
@@ -1518,7 +1542,7 @@ class Trainer(_GraphTrainer):
         """can the step run as the autograd-free pipeline (a stems / cells / fusable-head net with a loss the head forms)?"""
         from . import head as _head
         m = self.net
-        return (_fused.WHOLE_NET and isinstance(self.loss_fn, (WeightedDiceLoss, TverskyBCELoss)) and not hasattr(m, "kernel")
+        return (_fused.WHOLE_NET and isinstance(self.loss_fn, (WeightedDiceLoss, TverskyBCELoss, BoundaryLoss)) and not hasattr(m, "kernel")
                 and all(hasattr(m, a) for a in ("stem0", "stem1", "down_cells", "up_cells", "last_conv"))
                 and _head.fusable(m.last_conv, torch.empty((1, m.last_conv[0].conv.weight.shape[1], 1, 1, 1), device="meta")))
 
@@ -1827,6 +1851,7 @@ class SearchTrainer(_GraphTrainer):
         from . import programs as _P
         _P.PASS_TAG = "arch" if arch else "weight"
         with K.step_context(self.ctx):
+            self._prepare_loss(t)
             if pack:
                 self.ctx.pack_all()
             if sided and self.side_forward:

@@ -274,7 +274,7 @@ def run(net, x, alphas=None):
 
 def run_loss(net, x, t, alphas=None, smooth=1e-6, loss=None):
     """(loss, probabilities): forward with the loss formed inside the head's passes (the trainers' path) -- the Dice loss of
-    loss.py:12-14, or the loss.TverskyBCELoss `loss`"""
+    loss.py:12-14, or the loss.TverskyBCELoss / loss.BoundaryLoss `loss`"""
     import torch
     return _head.run_loss(net.last_conv, body(net, x, alphas, planar=_head_takes_planar(net) and t.dtype == torch.float32), t, smooth, loss=loss)
 

@@ -27,7 +27,7 @@ PEAK_HBM_GBS = 8000.0
 HOST_ONLY = {"n3d_conv_workspace_bytes", "n3d_conv_stats_rows", "n3d_conv_pack_info", "n3d_stats_rows", "n3d_fused_max_rows", "n3d_bwd_small2_ok",
              "n3d_head_rows", "n3d_head_workspace_bytes", "n3d_dice_rows", "n3d_last_error", "n3d_version", "n3d_device_ok", "n3d_comm_available",
              "n3d_dropout3d_uniform", "n3d_comm_unique_id", "n3d_comm_init", "n3d_comm_destroy", "n3d_entry_signal_pending",
-             "n3d_entry_signal_counts", "n3d_cc_workspace_bytes"}
+             "n3d_entry_signal_counts", "n3d_cc_workspace_bytes", "n3d_target_sdt_workspace_bytes"}
 
 
 # entry points that are never replayed for timing: they change state the step depends on (weights and moments, the dropout
