@@ -12,7 +12,10 @@ t = 1 / t = 0 -- exact integers, by separable minima, one axis after the other,
     phi = 0 where the wanted distance has no source in the patch (an empty map, a full map).
 
 This is scipy.ndimage.distance_transform_edt under Kervadec's one_hot2dist; tests/test_boundary_ref_host.py holds the statement to
-scipy's recorded distances (tests/golden/boundary.npz) with `==`.
+scipy's recorded distances (tests/golden/boundary.npz) with `==`.  `squared_distances_chunked` is the same statement with a bounded
+temporary (lines of 1024 voxels), and `squared_distances_from_points` a second one -- the brute-force minimum over a short list of
+voxels -- for maps as large as 1024 x 1024 x 1 (`points_case`, `sparse_case`); tests/test_gpu_sdt_extents.py compares the device with
+both.
 
 The loss, in fp64: base (tests/_loss_ref.py) + w * mean_bcv (p * phi), and
     d loss / d z = (k2 t + k0 + k_phi phi) p (1 - p) + kb (p - t),   k_phi = w / (B C N)."""
@@ -43,6 +46,15 @@ def fixture_targets(name):
     k = list(SHAPES).index(name)
     assert len(cases) == shape[0] * shape[1]
     return np.stack([make_case(c, shape[2:], SEED + (0 if c.startswith("nested") else 10 * k + i)) for i, c in enumerate(cases)]).reshape(shape)
+
+
+CORNERS = tuple("corner_%d" % k for k in range(8))
+FACES = tuple("face_%d" % a for a in range(3))
+
+
+def corner(shape, k):
+    """voxel index of corner k of `shape`: the far end of axis a where bit a of k is set"""
+    return tuple(s - 1 if (k >> a) & 1 else 0 for a, s in enumerate(shape))
 
 
 def _ball(shape, centre, radius):
@@ -80,6 +92,19 @@ def make_case(name, shape, seed):
         r = {"nested_wt": 0.42, "nested_tc": 0.3, "nested_et": 0.17}[name] * ext
         g = np.indices(shape)
         t[sum(((g[a] - mid[a]) * (ext / shape[a])) ** 2 for a in range(3)) <= r * r] = 1
+    elif name == "speckle_98":
+        t[:] = rng.uniform(0, 1, shape) < 0.98
+    elif name in CORNERS:                  # one voxel at corner k: bit a of k picks the far end of axis a
+        t[corner(shape, int(name[-1]))] = 1
+    elif name in FACES:                    # the plane index[a] == 0: distances grow to L - 1 along axis a and every parabola survives
+        sel = [slice(None)] * 3
+        sel[int(name[-1])] = 0
+        t[tuple(sel)] = 1
+    elif name == "ramp":                   # a diagonal front: the envelope build pops on almost every step
+        g = np.indices(shape)
+        t[g[0] + g[1] + g[2] < sum(shape) // 3] = 1
+    elif name == "comb":                   # every 7th plane along axis 0
+        t[::7] = 1
     else:
         raise ValueError(name)
     return t
@@ -100,6 +125,89 @@ def squared_distances(t):
             f = np.moveaxis(g, -1, axis)
         out.append(np.where(f >= INF, INF, f))
     return out[0], out[1]
+
+
+def squared_distances_chunked(t, max_bytes=32 << 20):
+    """`squared_distances` with the (rows, L, L) int64 temporary of every axis pass held to max_bytes: the lines of a pass are taken in
+    slabs of max_bytes // (8 L^2) along the leading axis of the (lines, L) view.  Same statement, same integers."""
+    t = np.asarray(t) != 0
+    out = []
+    for src in (t, ~t):
+        f = np.where(src, 0, INF).astype(np.int64)
+        for axis in range(f.ndim):
+            L = f.shape[axis]
+            rows = max_bytes // (8 * L * L)
+            if rows < 1:
+                raise ValueError("a line of %d voxels needs a temporary of %d bytes (max_bytes = %d)" % (L, 8 * L * L, max_bytes))
+            i = np.arange(L)
+            d2 = (i[:, None] - i[None, :]) ** 2                  # [i][j]
+            g = np.ascontiguousarray(np.moveaxis(f, axis, -1))
+            lines = g.reshape(-1, L)
+            for r0 in range(0, lines.shape[0], rows):
+                slab = lines[r0:r0 + rows]
+                slab[:] = (slab[:, None, :] + d2).min(axis=-1)   # (the right side is complete before the slab is written)
+            f = np.moveaxis(g, -1, axis)
+        out.append(np.where(f >= INF, INF, f))
+    return out[0], out[1]
+
+
+MAX_POINTS = 64
+
+
+def squared_distances_from_points(shape, points, max_bytes=32 << 20):
+    """int64 array of `shape`: the smallest squared index distance from every voxel to one of `points` (at most MAX_POINTS index
+    tuples) -- the brute-force minimum over the list, not separated by axis; INF for an empty list.  Voxels are taken in chunks
+    whose (voxels, points) int64 temporary stays under max_bytes."""
+    pts = np.asarray(points, np.int64).reshape(-1, len(shape))
+    assert len(pts) <= MAX_POINTS and all((0 <= pts[:, a]).all() and (pts[:, a] < s).all() for a, s in enumerate(shape))
+    n = int(np.prod(shape))
+    out = np.full(n, INF, np.int64)
+    if len(pts):
+        step = max(1, max_bytes // (8 * len(pts)))
+        for v0 in range(0, n, step):
+            idx = np.unravel_index(np.arange(v0, min(n, v0 + step)), shape)
+            out[v0:v0 + step] = sum((idx[a][:, None] - pts[None, :, a]) ** 2 for a in range(len(shape))).min(axis=1)
+    return out.reshape(shape)
+
+
+def sparse_points(shape, k, seed):
+    """k distinct voxels of `shape`, no two of them 6-neighbours (asserted).  Where the shape has room the first three sit as far
+    apart as the patch allows -- (0, 0, 0), (1, D1 - 1, D2 - 1), (D0 - 1, 0, 0): neighbouring parabolas with very different offsets,
+    the large products of the device's envelope comparison -- and the rest are drawn uniformly."""
+    rng = np.random.default_rng(seed)
+    pts = []
+    cand = [(0, 0, 0), (min(1, shape[0] - 1), shape[1] - 1, shape[2] - 1), (shape[0] - 1, 0, 0)]
+    tries = 0
+    while len(pts) < k:
+        p = cand.pop(0) if cand else tuple(int(rng.integers(0, s)) for s in shape)
+        if all(sum(abs(a - b) for a, b in zip(p, q)) >= 2 for q in pts):
+            pts.append(p)
+        tries += 1
+        assert tries < 100 * k + 100, "no room for %d non-adjacent voxels in %s" % (k, (shape,))
+    assert len(set(pts)) == k and all(sum(abs(a - b) for a, b in zip(p, q)) >= 2 for n, p in enumerate(pts) for q in pts[:n])
+    return pts
+
+
+def points_case(shape, pts, foreground=True):
+    """(t uint8, phi float32) of the map whose foreground (or, with foreground=False, background) is exactly the voxels `pts`, mutually
+    non-adjacent (asserted), by the points statement.  The far side is the brute force over the list.  Each listed voxel has a
+    6-neighbour inside the patch, of the other kind since no two of the list are adjacent: its own squared distance is 1 and its phi is
+    -(1 - 1) as foreground, 1 as background."""
+    assert max(shape) > 1 and 1 <= len(pts) <= MAX_POINTS
+    assert len(set(pts)) == len(pts) and all(sum(abs(a - b) for a, b in zip(p, q)) >= 2 for n, p in enumerate(pts) for q in pts[:n])
+    t = np.zeros(shape, np.uint8)
+    t[tuple(np.array(pts).T)] = 1
+    far = squared_distances_from_points(shape, pts)
+    near = np.where(t != 0, 1, 0).astype(np.int64)          # the few: 1 to a neighbour of the other kind; the many: 0, themselves
+    if foreground:
+        return t, phi_rule(t, far, near)
+    return 1 - t, phi_rule(1 - t, near, far)
+
+
+def sparse_case(name, shape, k, seed):
+    """(t, phi) of `sparse_fg` -- k mutually non-adjacent foreground voxels (sparse_points) -- or of `sparse_bg`, its complement"""
+    assert name in ("sparse_fg", "sparse_bg")
+    return points_case(shape, sparse_points(shape, k, seed), name == "sparse_fg")
 
 
 def phi_rule(t, d2_fg, d2_bg):

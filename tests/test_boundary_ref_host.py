@@ -72,6 +72,71 @@ def test_float_and_byte_targets_give_the_same_map(golden):
     assert np.array_equal(br.signed_distance(t), br.signed_distance(t.astype(np.float32)))
 
 
+# ---- the statements behind tests/test_gpu_sdt_extents.py ---------------------------------------------------------------------------
+ODD = (65, 33, 40)
+NEW_CASES = br.CORNERS + br.FACES + ("ramp", "comb", "speckle_98")
+
+
+@pytest.mark.parametrize("name", list(br.SHAPES))
+def test_chunked_equals_unchunked_on_the_fixture_shapes(golden, name):
+    for t in golden[name + ".t"].reshape((-1,) + br.SHAPES[name][0][2:]):
+        L = max(t.shape)
+        for got, want in zip(br.squared_distances_chunked(t, 3 * 8 * L * L), br.squared_distances(t)):      # slabs of three lines
+            assert got.dtype == want.dtype and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("case", ["speckle_50", "two_blobs", "ramp", "empty"])
+def test_chunked_equals_unchunked_on_odd_extents(case):
+    t = br.make_case(case, ODD, 5)
+    for max_bytes in (8 * 65 * 65, 1 << 20, 1 << 30):      # one line of the longest axis at a time; some; all at once
+        for got, want in zip(br.squared_distances_chunked(t, max_bytes), br.squared_distances(t)):
+            assert np.array_equal(got, want)
+    with pytest.raises(ValueError):
+        br.squared_distances_chunked(t, 8 * 65 * 65 - 1)
+
+
+@pytest.mark.parametrize("k", [1, 7, 64])
+@pytest.mark.parametrize("name", ["sparse_fg", "sparse_bg"])
+@pytest.mark.parametrize("shape", [(16, 16, 16), (8, 12, 20)])
+def test_the_points_statement_equals_the_separable_one(shape, name, k):
+    t, phi = br.sparse_case(name, shape, k, 40 + k)
+    few = t if name == "sparse_fg" else 1 - t
+    assert int(few.sum()) == k and t.dtype == np.uint8
+    pts = [tuple(p) for p in np.argwhere(few)]
+    d2 = br.squared_distances(t)
+    assert np.array_equal(br.squared_distances_from_points(shape, pts, max_bytes=4096), d2[0 if name == "sparse_fg" else 1])
+    assert np.array_equal(phi.view(np.uint32), br.phi_rule(t, *d2).view(np.uint32))
+    assert (br.squared_distances_from_points(shape, []) == br.INF).all()
+
+
+def test_the_new_named_cases_are_what_they_say():
+    for k in range(8):
+        t = br.make_case("corner_%d" % k, ODD, 0)
+        assert t.sum() == 1 and t[tuple(s - 1 if (k >> a) & 1 else 0 for a, s in enumerate(ODD))] == 1
+    for a in range(3):
+        t = br.make_case("face_%d" % a, ODD, 0)
+        assert t.sum() == t.size // ODD[a] and np.take(t, 0, axis=a).all()
+        assert br.squared_distances(t)[0].max() == (ODD[a] - 1) ** 2
+    t = br.make_case("ramp", ODD, 0)
+    assert t[0, 0, 0] == 1 and t[-1, -1, -1] == 0 and t[10, 20, 15] == 1 and t[10, 20, 16] == 0      # 46 = (65 + 33 + 40) // 3
+    t = br.make_case("comb", ODD, 0)
+    assert [i for i in range(65) if t[i].all()] == list(range(0, 65, 7)) and t.sum() == 10 * 33 * 40
+    t = br.make_case("speckle_98", ODD, 0)
+    assert 0.975 < t.mean() < 0.985
+
+
+@pytest.mark.parametrize("case", NEW_CASES)
+def test_new_cases_equal_kervadecs_rule_on_scipy(case):
+    """phi_rule of the separable statement == one_hot2dist on scipy's own float64 distances, rounded once to float32"""
+    edt = pytest.importorskip("scipy.ndimage").distance_transform_edt
+    t = br.make_case(case, ODD, 11)
+    m = t != 0
+    assert m.any() and not m.all()
+    phi = br.phi_rule(t, *br.squared_distances_chunked(t))
+    one_hot2dist = edt(~m) * ~m - (edt(m) - 1) * m
+    assert phi.dtype == np.float32 and np.array_equal(phi, one_hot2dist.astype(np.float32))
+
+
 @pytest.mark.parametrize("spec", [lr.SPECS[2], lr.SPECS[3]])
 def test_closed_form_gradient_is_autograds(spec):
     rng = np.random.default_rng(3)
