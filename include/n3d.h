@@ -830,6 +830,40 @@ int n3d_brain_sqdev(const int16_t* raw, int Cm, int64_t N, const double* mean, d
  * (bx, by, bz) crop in the same launch, or both NULL. */
 int n3d_brain_normalize(const int16_t* raw, int Cm, int X, int Y, int Z, const double* mean_std, const int32_t* rec, const int32_t* lo,
                         const int32_t* hi, float* out, const uint8_t* truth, uint8_t* truth_out, void* stream);
+/* ---- a second normalisation, not the reference's: per subject and per modality, z-scoring over the brain voxels after clipping
+ * the counts to two percentiles (lower < upper, in percent).  Needs no data-set statistics.  Four launches per subject:
+ * n3d_brain_scan (above: the outline for the box, and rec's minimum), n3d_brain_hist, n3d_brain_robust, n3d_brain_zscore.
+ * The rule.  Per modality, a[0..n-1] are its nonzero counts sorted ascending, n >= 2 (the caller refuses count < 2 and std == 0
+ * from the record); every line is ONE correctly rounded fp64 operation (no contraction):
+ *   1. for q in (lower, upper):  vi = (double)(n - 1) * (q / 100.0);  k = floor(vi);  t = vi - k;  A = a[k];
+ *      B = a[min(k + 1, n - 1)];  d = B - A;  bound = A + d * t, or B - d * (1.0 - t) when t >= 0.5  (numpy's linear
+ *      np.percentile in its own order of operations).  The two bounds are L and U.
+ *   2. w(v) = min(max((double)v, L), U).  nL = voxels with v < L, nU = voxels with v > U, S_in = the exact integer sum of the
+ *      others (|S_in| < 2^53: its conversion is exact).
+ *   3. mean = ((nL * L + S_in) + nU * U) / n.
+ *   4. sum of squared deviations, in this fixed order: the 65536 bins (bin b holds value v = b - 32768, h[b] voxels) are cut
+ *      into 1024 runs of 64 consecutive bins; run i starts from 0.0 and adds h * ((v - mean) * (v - mean)) for its bins with
+ *      L <= v <= U and h > 0 in ascending v; the 1024 run sums are then added in adjacent pairs, p[i] = p[2i] + p[2i + 1], ten
+ *      rounds down to one value I;  sum = (nL * ((L - mean) * (L - mean)) + I) + nU * ((U - mean) * (U - mean));
+ *      std = sqrt(sum / n).  No floating-point atomics: two runs give the same bits.
+ *   5. a nonzero voxel stores r = (float)((w(v) - mean) / std), and FLT_MIN (0x00800000) where r == 0.0f; a zero voxel 0.0f:
+ *      the output is nonzero exactly where raw is.
+ * n3d_brain_hist: hist, DEVICE int32 [Cm][N3D_BRAIN_HIST_BINS], 16-byte aligned, is zeroed on the stream and then holds the exact
+ * histogram of each modality's nonzero voxels, value v in bin v + 32768.  rec: as n3d_brain_scan left it for THIS subject (read
+ * on the device): counts in [min, min + n3d_brain_hist_window()) are accumulated in LDS per workgroup, the others with global
+ * integer atomics -- rec decides the speed, never the result.
+ * n3d_brain_robust: one record per modality from hist, out: DEVICE [Cm][N3D_BRAIN_ROBUST_WORDS] 8-byte words:
+ *   int64   0 count n;  1..4 a[kL], a[min(kL + 1, n - 1)], a[kU], a[min(kU + 1, n - 1)];  5 nL;  6 nU;  7 S_in
+ *   double  8 L;  9 U;  10 mean;  11 std;  12 the sum of squared deviations
+ *   13..15 reserved (zero).  count == 0 leaves every other word zero.
+ * n3d_brain_zscore: n3d_brain_normalize's box, output and label crop, with rule 2 and 5 from the DEVICE record `robust`. */
+#define N3D_BRAIN_HIST_BINS 65536
+#define N3D_BRAIN_ROBUST_WORDS 16
+int n3d_brain_hist_window(void);
+int n3d_brain_hist(const int16_t* raw, int Cm, int X, int Y, int Z, const int32_t* rec, int32_t* hist, void* stream);
+int n3d_brain_robust(const int32_t* hist, int Cm, double lower, double upper, int64_t* out, void* stream);
+int n3d_brain_zscore(const int16_t* raw, int Cm, int X, int Y, int Z, const int64_t* robust, const int32_t* lo, const int32_t* hi,
+                     float* out, const uint8_t* truth, uint8_t* truth_out, void* stream);
 
 /* ---- step after the hot path (prediction.py:120-170): stitch the per-patch predictions into the brain-wide volume with
  * mean blending (patches.py:172-207) and fuse the three sigmoid channels into one label volume.

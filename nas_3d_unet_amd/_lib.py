@@ -268,6 +268,10 @@ PROTOTYPES = {
     "n3d_brain_sqdev_rows": (_i, [_i64]),
     "n3d_brain_sqdev": (_i, [_p, _i, _i64, _p, _p, _p, _p]),
     "n3d_brain_normalize": (_i, [_p, _i, _i, _i, _i, _p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _p, _p, _p]),
+    "n3d_brain_hist_window": (_i, []),
+    "n3d_brain_hist": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+    "n3d_brain_robust": (_i, [_p, _i, _d, _d, _p, _p]),
+    "n3d_brain_zscore": (_i, [_p, _i, _i, _i, _i, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _p, _p, _p]),
     "n3d_stitch": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "n3d_tumor_labels": (_i, [_p, _i64, C.c_double, _i, _p, _p]),
     "n3d_stitch_add": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, _p, _p, _p]),

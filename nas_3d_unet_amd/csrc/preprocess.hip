@@ -6,6 +6,10 @@
 // value is a chain of single-rounded fp64 operations, so this file is compiled without contraction: the pragma below states it,
 // and because -ffp-contract=fast makes the backend fuse regardless of it, the Makefile also ends this file's flags with
 // -ffp-contract=off.
+// Next to the reference's rule stands a second one, chosen per call (further down): an exact histogram of each modality's counts,
+// the percentile bounds, mean and std read from it, and z-scoring of the clipped counts fused with the same crop.
+#include <cfloat>
+
 #include "n3d_common.h"
 
 #pragma clang fp contract(off)
@@ -224,6 +228,209 @@ __global__ __launch_bounds__(256) void brain_normalize_kernel(const int16_t* __r
   }
 }
 
+// ---- the second scheme (include/n3d.h, "n3d_brain_hist .. n3d_brain_zscore"): per subject and modality, z-scoring over the brain
+// voxels after clipping to two percentiles.  Every order statistic comes from an exact histogram of the modality's counts.
+
+constexpr int kHistBins = N3D_BRAIN_HIST_BINS;
+// LDS window of brain_hist_kernel: 8192 int32 bins = 32 KiB per workgroup, five workgroups in a CU's 160 KiB (the 256-thread
+// workgroups of this kernel then sit at 20 of the 32 waves a CU takes).  BraTS counts of one modality span a few thousand values
+// above the minimum, so the window takes nearly every voxel; what falls outside goes to global memory one atomic each.
+constexpr int kHistWindow = 8192;
+constexpr int kHistMaxBlocks = 128;   // per modality: each workgroup flushes its nonzero window bins once, so few, long-running workgroups
+
+// grid (blocks, Cm).  hist: int32 [Cm][65536], bin v + 32768, ADDED to (the entry point zeroes it).  Reads as brain_scan_kernel
+// does.  A nonzero voxel v with 0 <= v - min < kHistWindow (min: rec's minimum of the modality, read here) is one LDS atomic; any
+// other one global atomic, so a wrong `min` costs time and never a count.  Integer adds only: the result does not depend on order.
+__global__ __launch_bounds__(256) void brain_hist_kernel(const int16_t* __restrict__ raw, int64_t N, const int* __restrict__ rec,
+                                                         int* __restrict__ hist) {
+  const int c = blockIdx.y;
+  const int16_t* p = raw + (int64_t)c * N;
+  const Span sp = span_of(p, N);
+  const int mn = rec[N3D_BRAIN_REC_WORDS * c];
+  int* gh = hist + (int64_t)c * kHistBins;
+  __shared__ int lh[kHistWindow];
+  for (int i = threadIdx.x; i < kHistWindow; i += 256) lh[i] = 0;
+  __syncthreads();
+  auto one = [&](int v) {
+    if (v != 0) {
+      const uint32_t d = (uint32_t)v - (uint32_t)mn;
+      if (d < (uint32_t)kHistWindow) atomicAdd(&lh[d], 1);
+      else atomicAdd(gh + (v + 32768), 1);          // v is an int16: the bin is inside [0, 65536)
+    }
+  };
+  if (blockIdx.x == 0) {
+    if ((int64_t)threadIdx.x < sp.head) one(p[threadIdx.x]);
+    else if (threadIdx.x >= 64 && sp.tail0 + (threadIdx.x - 64) < N) one(p[sp.tail0 + (threadIdx.x - 64)]);
+  }
+  const int4* body = reinterpret_cast<const int4*>(p + sp.head);
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < sp.groups; g += (int64_t)gridDim.x * 256) {
+    const int4 v = body[g];
+    if ((v.x | v.y | v.z | v.w) == 0) continue;
+    const int w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) one(half_of(w[k >> 1], k & 1));
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kHistWindow; i += 256) {
+    const int h = lh[i];
+    const int64_t b = (int64_t)mn + 32768 + i;      // a bin that was counted is inside the histogram; the test keeps a stray `min` harmless
+    if (h != 0 && b >= 0 && b < kHistBins) atomicAdd(gh + b, h);
+  }
+}
+
+// one record of n3d_brain_robust: N3D_BRAIN_ROBUST_WORDS 8-byte words (include/n3d.h states the layout)
+struct RobustRec {
+  long long count, order[4], n_below, n_above, sum_in;
+  double lower, upper, mean, std, ssd;
+  long long reserved[3];
+};
+static_assert(sizeof(RobustRec) == 8 * N3D_BRAIN_ROBUST_WORDS, "RobustRec is the record of include/n3d.h");
+
+constexpr int kRobustThreads = 1024;
+constexpr int kRobustBins = kHistBins / kRobustThreads;   // 64 consecutive bins per thread
+
+__device__ __forceinline__ long long wave_sum_ll(long long s) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+// numpy's linear percentile from the two order statistics around the virtual index and its fraction t
+__device__ __forceinline__ double lerp_bound(long long a, long long b, double t) {
+  const double A = (double)a, B = (double)b;
+  const double d = B - A;
+  return t >= 0.5 ? B - d * (1.0 - t) : A + d * t;
+}
+
+// grid (Cm), 1024 threads: thread t owns bins [64 t, 64 t + 64).  Integer work (prefix sums, order statistics, nL, nU, S_in) is
+// exact.  Sum of squared deviations: thread t adds its interior bins' h * ((v - mean) * (v - mean)) in ascending v from 0.0, the
+// 1024 partial sums are added in adjacent pairs (p[2i] + p[2i + 1], ten rounds), then (low term + that) + high term.
+__global__ __launch_bounds__(kRobustThreads) void brain_robust_kernel(const int* __restrict__ hist, double lower, double upper,
+                                                                       RobustRec* __restrict__ out) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  const int4* hp = reinterpret_cast<const int4*>(hist + (int64_t)c * kHistBins + t * kRobustBins);
+  __shared__ uint32_t scan[kRobustThreads];
+  __shared__ long long order[4];
+  __shared__ long long red[3][kRobustThreads / 64];
+  __shared__ double part[kRobustThreads];
+  auto bins = [&](auto&& f) {      // f(v, h) over this thread's nonzero bins in ascending v
+    for (int j = 0; j < kRobustBins / 4; ++j) {
+      const int4 q = hp[j];
+      const int h[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (h[k] != 0) f(t * kRobustBins + j * 4 + k - 32768, h[k]);
+    }
+  };
+  uint32_t local = 0;
+  bins([&](int, int h) { local += (uint32_t)h; });
+  scan[t] = local;
+  __syncthreads();
+  for (int d = 1; d < kRobustThreads; d <<= 1) {
+    const uint32_t add = t >= d ? scan[t - d] : 0u;
+    __syncthreads();
+    scan[t] += add;
+    __syncthreads();
+  }
+  const long long n = scan[kRobustThreads - 1];
+  RobustRec r = {};
+  r.count = n;
+  if (n == 0) {                    // (uniform) nothing to rank: the caller refuses count < 2
+    if (t == 0) out[c] = r;
+    return;
+  }
+  long long idx[4];
+  double frac[2];
+  const double qs[2] = {lower, upper};
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const double vi = (double)(n - 1) * (qs[e] / 100.0);
+    const double kf = floor(vi);
+    frac[e] = vi - kf;
+    const long long k = (long long)kf;
+    idx[2 * e] = k;
+    idx[2 * e + 1] = k + 1 < n - 1 ? k + 1 : n - 1;
+  }
+  long long cum = (long long)scan[t] - local;
+  bins([&](int v, int h) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+      if (idx[m] >= cum && idx[m] < cum + h) order[m] = v;
+    cum += h;
+  });
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < 4; ++m) r.order[m] = order[m];
+  const double L = lerp_bound(r.order[0], r.order[1], frac[0]), U = lerp_bound(r.order[2], r.order[3], frac[1]);
+  long long nb = 0, na = 0, s = 0;
+  bins([&](int v, int h) {
+    const double dv = (double)v;
+    if (dv < L) nb += h;
+    else if (dv > U) na += h;
+    else s += (long long)h * v;
+  });
+  nb = wave_sum_ll(nb);
+  na = wave_sum_ll(na);
+  s = wave_sum_ll(s);
+  if ((t & 63) == 0) { red[0][t >> 6] = nb; red[1][t >> 6] = na; red[2][t >> 6] = s; }
+  __syncthreads();
+  nb = na = s = 0;
+  for (int w = 0; w < kRobustThreads / 64; ++w) { nb += red[0][w]; na += red[1][w]; s += red[2][w]; }
+  const double dn = (double)n;
+  const double mean = (((double)nb * L + (double)s) + (double)na * U) / dn;
+  double acc = 0.0;
+  bins([&](int v, int h) {
+    const double dv = (double)v;
+    if (dv >= L && dv <= U) {
+      const double d = dv - mean;
+      acc += (double)h * (d * d);
+    }
+  });
+  part[t] = acc;
+  __syncthreads();
+  for (int d = 1; d < kRobustThreads; d <<= 1) {
+    if ((t & (2 * d - 1)) == 0) part[t] += part[t + d];
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double ssd = ((double)nb * ((L - mean) * (L - mean)) + part[0]) + (double)na * ((U - mean) * (U - mean));
+    r.n_below = nb; r.n_above = na; r.sum_in = s;
+    r.lower = L; r.upper = U; r.mean = mean; r.ssd = ssd;
+    r.std = sqrt(ssd / dn);
+    out[c] = r;
+  }
+}
+
+// brain_normalize_kernel's geometry with the second rule: w = min(max(x, L), U);  stored (float)((w - mean) / std), FLT_MIN where
+// that is zero (x != 0; else 0): the box stays nonzero exactly where raw is.  L, U, mean, std: the device record of the modality.
+__global__ __launch_bounds__(256) void brain_zscore_kernel(const int16_t* __restrict__ raw, int Cm, CropGeom g, const RobustRec* __restrict__ rr,
+                                                           float* __restrict__ out, const uint8_t* __restrict__ truth,
+                                                           uint8_t* __restrict__ truth_out) {
+  const int c = blockIdx.y;
+  const int64_t nb = (int64_t)g.b[0] * g.b[1] * g.b[2];
+  double L = 0.0, U = 0.0, mean = 0.0, sd = 1.0;
+  if (c < Cm) { L = rr[c].lower; U = rr[c].upper; mean = rr[c].mean; sd = rr[c].std; }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.x * 256) {
+    uint32_t q, k, ii, j;
+    g.fbz.divmod((uint32_t)i, q, k);
+    g.fby.divmod(q, ii, j);
+    const int64_t src = ((int64_t)(g.lo[0] + (int)ii) * g.Y + (g.lo[1] + (int)j)) * g.Z + (g.lo[2] + (int)k);
+    if (c == Cm) {
+      truth_out[i] = truth[src];
+      continue;
+    }
+    const int x = raw[(int64_t)c * g.N + src];
+    float r = 0.f;
+    if (x != 0) {
+      const double dx = (double)x;
+      const double w = dx < L ? L : (dx > U ? U : dx);
+      r = (float)((w - mean) / sd);
+      if (r == 0.f) r = FLT_MIN;
+    }
+    out[(int64_t)c * nb + i] = r;
+  }
+}
+
 }  // namespace n3d
 
 using namespace n3d;
@@ -264,30 +471,79 @@ extern "C" int n3d_brain_sqdev(const int16_t* raw, int Cm, int64_t N, const doub
   return N3D_OK;
 }
 
+// the box [lo, hi) of a normalise + crop launch, checked against the image, and the launch's blocks along x
+static int crop_geom(int X, int Y, int Z, const int32_t* lo, const int32_t* hi, const char* what, CropGeom& g, unsigned& blocks) {
+  const int dims[3] = {X, Y, Z};
+  g.N = (int64_t)X * Y * Z;
+  g.Y = Y;
+  g.Z = Z;
+  for (int a = 0; a < 3; ++a) {
+    N3D_CHECK_ARG(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a], "%s: box [%d, %d) on axis %d is not inside the image (%d)", what, lo[a],
+                  hi[a], a, dims[a]);
+    g.lo[a] = lo[a];
+    g.b[a] = hi[a] - lo[a];
+  }
+  g.fby = FastDiv((uint32_t)g.b[1]);
+  g.fbz = FastDiv((uint32_t)g.b[2]);
+  const int64_t b = cdiv((int64_t)g.b[0] * g.b[1] * g.b[2], 256 * 4);
+  blocks = (unsigned)(b > 4096 ? 4096 : b);
+  return N3D_OK;
+}
+
 extern "C" int n3d_brain_normalize(const int16_t* raw, int Cm, int X, int Y, int Z, const double* mean_std, const int32_t* rec,
                                    const int32_t* lo, const int32_t* hi, float* out, const uint8_t* truth, uint8_t* truth_out, void* stream) {
   if (int e = check_raw(raw, Cm, X, Y, Z, "brain_normalize")) return e;
   N3D_CHECK_ARG(mean_std && rec && lo && hi && out && (truth == nullptr) == (truth_out == nullptr), "brain_normalize: bad args");
   N3D_CHECK_ARG((reinterpret_cast<uintptr_t>(mean_std) & 7) == 0 && (reinterpret_cast<uintptr_t>(rec) & 3) == 0 &&
                 (reinterpret_cast<uintptr_t>(out) & 3) == 0, "brain_normalize: mean_std must be 8-byte, rec and out 4-byte aligned");
-  const int dims[3] = {X, Y, Z};
   CropGeom g;
-  g.N = (int64_t)X * Y * Z;
-  g.Y = Y;
-  g.Z = Z;
-  for (int a = 0; a < 3; ++a) {
-    N3D_CHECK_ARG(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a], "brain_normalize: box [%d, %d) on axis %d is not inside the image (%d)",
-                  lo[a], hi[a], a, dims[a]);
-    g.lo[a] = lo[a];
-    g.b[a] = hi[a] - lo[a];
-  }
-  g.fby = FastDiv((uint32_t)g.b[1]);
-  g.fbz = FastDiv((uint32_t)g.b[2]);
-  const int64_t nb = (int64_t)g.b[0] * g.b[1] * g.b[2];
-  int64_t blocks = cdiv(nb, 256 * 4);
-  if (blocks > 4096) blocks = 4096;
-  N3D_LAUNCH(brain_normalize_kernel, dim3((unsigned)blocks, (unsigned)(Cm + (truth ? 1 : 0))), dim3(256), 0, (hipStream_t)stream, raw, Cm, g,
+  unsigned blocks;
+  if (int e = crop_geom(X, Y, Z, lo, hi, "brain_normalize", g, blocks)) return e;
+  N3D_LAUNCH(brain_normalize_kernel, dim3(blocks, (unsigned)(Cm + (truth ? 1 : 0))), dim3(256), 0, (hipStream_t)stream, raw, Cm, g,
              mean_std, rec, out, truth, truth_out);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_brain_hist_window(void) { return kHistWindow; }
+
+extern "C" int n3d_brain_hist(const int16_t* raw, int Cm, int X, int Y, int Z, const int32_t* rec, int32_t* hist, void* stream) {
+  if (int e = check_raw(raw, Cm, X, Y, Z, "brain_hist")) return e;
+  N3D_CHECK_ARG(rec && hist, "brain_hist: bad args");
+  N3D_CHECK_ARG((reinterpret_cast<uintptr_t>(rec) & 3) == 0 && aligned16(hist), "brain_hist: rec must be 4-byte and hist 16-byte aligned");
+  const int64_t N = (int64_t)X * Y * Z;
+  n3d::entry_flush();      // (the memset is no kernel of ours: an armed entry signal goes out in front)
+  hipError_t e = hipMemsetAsync(hist, 0, sizeof(int32_t) * (size_t)Cm * kHistBins, (hipStream_t)stream);
+  if (e != hipSuccess) { set_error("brain_hist: hipMemsetAsync: %s", hipGetErrorString(e)); return N3D_ERR_HIP; }
+  int64_t blocks = cdiv(N >> 3, 256 * 16);
+  blocks = blocks < 1 ? 1 : (blocks > kHistMaxBlocks ? kHistMaxBlocks : blocks);
+  N3D_LAUNCH(brain_hist_kernel, dim3((unsigned)blocks, (unsigned)Cm), dim3(256), 0, (hipStream_t)stream, raw, N, rec, hist);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_brain_robust(const int32_t* hist, int Cm, double lower, double upper, int64_t* out, void* stream) {
+  N3D_CHECK_ARG(hist && out && Cm >= 1, "brain_robust: bad args");
+  N3D_CHECK_ARG(aligned16(hist) && (reinterpret_cast<uintptr_t>(out) & 7) == 0, "brain_robust: hist must be 16-byte and out 8-byte aligned");
+  N3D_CHECK_ARG(0.0 <= lower && lower < upper && upper <= 100.0, "brain_robust: percentiles %g, %g: needs 0 <= lower < upper <= 100", lower,
+                upper);
+  N3D_LAUNCH(brain_robust_kernel, dim3((unsigned)Cm), dim3(kRobustThreads), 0, (hipStream_t)stream, hist, lower, upper,
+             reinterpret_cast<RobustRec*>(out));
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+extern "C" int n3d_brain_zscore(const int16_t* raw, int Cm, int X, int Y, int Z, const int64_t* robust, const int32_t* lo, const int32_t* hi,
+                                float* out, const uint8_t* truth, uint8_t* truth_out, void* stream) {
+  if (int e = check_raw(raw, Cm, X, Y, Z, "brain_zscore")) return e;
+  N3D_CHECK_ARG(robust && lo && hi && out && (truth == nullptr) == (truth_out == nullptr), "brain_zscore: bad args");
+  N3D_CHECK_ARG((reinterpret_cast<uintptr_t>(robust) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
+                "brain_zscore: robust must be 8-byte and out 4-byte aligned");
+  CropGeom g;
+  unsigned blocks;
+  if (int e = crop_geom(X, Y, Z, lo, hi, "brain_zscore", g, blocks)) return e;
+  N3D_LAUNCH(brain_zscore_kernel, dim3(blocks, (unsigned)(Cm + (truth ? 1 : 0))), dim3(256), 0, (hipStream_t)stream, raw, Cm, g,
+             reinterpret_cast<const RobustRec*>(robust), out, truth, truth_out);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }

@@ -273,12 +273,15 @@ class VolumeSet:
         self.records = torch.frombuffer(bytearray(recs), dtype=torch.uint8).to(self.device)
         return len(self.volumes) - 1
 
-    def add_subject(self, raw, truth, mean_std, mods=preprocess.MODS):
+    def add_subject(self, raw, truth, mean_std=None, mods=preprocess.MODS, scheme=None):
         """raw: (Cm, X, Y, Z) int16 scanner counts (numpy or tensor); truth: (X, Y, Z) / (1, X, Y, Z) uint8 or None; mean_std: the
-        dictionary of preprocess.cal_mean_std.  Normalises and crops on the device (preprocess.normalize_subject), add()s the box
+        dictionary of preprocess.cal_mean_std, or scheme: a preprocess.ZScore, which needs no dictionary (one of the two).
+        Normalises and crops on the device (preprocess.normalize_subject), add()s the box
         and notes where it sits: origins[i] (brain_width[0]) and full_shapes[i] are what SubjectPredictor.predict takes as
         origin / full_shape.  Returns the volume's index."""
-        vol, t, brain_width = preprocess.normalize_subject(raw, mean_std, truth, mods, self.device)
+        if mean_std is None and scheme is None:
+            raise N3DError("VolumeSet.add_subject: needs mean_std (preprocess.cal_mean_std) or scheme (preprocess.ZScore)")
+        vol, t, brain_width = preprocess.normalize_subject(raw, mean_std, truth, mods, self.device, scheme)
         i = self.add(vol, t)
         self.origins[i] = tuple(int(v) for v in brain_width[0])
         self.full_shapes[i] = tuple(int(v) for v in raw.shape[-3:])

@@ -64,15 +64,27 @@ def _ratio(num, den):
     return float(np.float64(num) / np.float64(den)) if den else float("nan")
 
 
-def hd_from_order(n, d2_lo, d2_hi):
-    """np.percentile(sqrt(D), 95) (linear interpolation) from n = len(D) > 0 and the order statistics d2_lo = D[k],
-    d2_hi = D[min(k + 1, n - 1)] of the sorted squared distances, k = floor((n - 1) * 0.95): numpy's own operations in its order
-    (virtual index (n - 1) * q, gamma = index - floor, then its lerp with the t >= 0.5 form)."""
-    vi = np.float64(n - 1) * np.float64(0.95)
-    t = vi - np.floor(vi)
-    lo, hi = np.sqrt(np.float64(d2_lo)), np.sqrt(np.float64(d2_hi))
+def percentile_index(n, q):
+    """(k, t) of np.percentile's linear method over n > 0 sorted values: virtual index (n - 1) * (q / 100), k its floor,
+    t = index - k (numpy's gamma)"""
+    vi = np.float64(n - 1) * (np.float64(q) / np.float64(100.0))
+    k = np.floor(vi)
+    return int(k), vi - k
+
+
+def percentile_from_order(n, q, lo, hi):
+    """np.percentile(a, q) (linear interpolation) from n = len(a) > 0 and the order statistics lo = a[k], hi = a[min(k + 1, n - 1)]
+    of the sorted values, (k, t) = percentile_index(n, q): numpy's own operations in its order (its lerp with the t >= 0.5 form)"""
+    t = percentile_index(n, q)[1]
+    lo, hi = np.float64(lo), np.float64(hi)
     diff = hi - lo
     return float(hi - diff * (1 - t)) if t >= 0.5 else float(lo + diff * t)
+
+
+def hd_from_order(n, d2_lo, d2_hi):
+    """np.percentile(sqrt(D), 95) from n = len(D) > 0 and the order statistics d2_lo = D[k], d2_hi = D[min(k + 1, n - 1)] of the
+    sorted squared distances, k = floor((n - 1) * 0.95) (95 / 100 rounds to the double 0.95)"""
+    return percentile_from_order(n, 95, np.sqrt(np.float64(d2_lo)), np.sqrt(np.float64(d2_hi)))
 
 
 def finish(counts, n_voxels, order):

@@ -13,7 +13,16 @@ The reference's normalize writes its fp64 result into nibabel's int16 array, so 
 integer 10..110 (background 0); the networks were trained on those values, and this module reproduces them bit for bit.
 float32 raw data is refused: the reference's sums are then fp32 pairwise sums whose order cannot be pinned.
 
-Host logic only; the kernels are n3d_brain_scan, n3d_brain_sqdev and n3d_brain_normalize (include/n3d.h)."""
+A second scheme stands next to it for nets trained from scratch, chosen per call with scheme=ZScore(lower, upper): each
+modality's brain voxels are clipped to two of their own percentiles and z-scored (include/n3d.h states the rule operation by
+operation).  It needs no dictionary; the box and brain_width are the same; a brain voxel never stores 0 (FLT_MIN stands in), so
+the box is nonzero exactly where raw is, which is what every consumer takes as "brain".
+  * normalize_subject(raw, None, truth, scheme=ZScore()): n3d_brain_scan, n3d_brain_hist (exact histogram of the counts),
+    n3d_brain_robust (order statistics, bounds, mean, std: one record per modality), ONE host sync for the outlines and the
+    record, then n3d_brain_zscore writes the box.  subject_stats(raw, scheme) returns what the record holds.
+
+Host logic only; the kernels are n3d_brain_scan, n3d_brain_sqdev, n3d_brain_normalize and n3d_brain_hist, n3d_brain_robust,
+n3d_brain_zscore (include/n3d.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,6 +42,16 @@ _REC_INIT = [_I32_MAX, _I32_MIN, _I32_MAX, _I32_MAX, _I32_MAX, -1, -1, -1]
 
 # count, sum: int64 (Cm,); mean, std: UNROUNDED float64 (Cm,)
 DatasetStats = namedtuple("DatasetStats", "count sum mean std")
+
+HIST_BINS = 65536   # N3D_BRAIN_HIST_BINS
+ROBUST_WORDS = 16   # N3D_BRAIN_ROBUST_WORDS
+# one record of n3d_brain_robust, word for word as include/n3d.h lays it out
+ROBUST_DTYPE = np.dtype([("count", "<i8"), ("order", "<i8", (4,)), ("n_below", "<i8"), ("n_above", "<i8"), ("sum_in", "<i8"),
+                         ("lower", "<f8"), ("upper", "<f8"), ("mean", "<f8"), ("std", "<f8"), ("ssd", "<f8"), ("reserved", "<i8", (3,))])
+assert ROBUST_DTYPE.itemsize == 8 * ROBUST_WORDS
+# one modality of subject_stats: order = (a[kL], a[kL + 1], a[kU], a[kU + 1]) of the sorted brain counts (indices clamped to n - 1);
+# lower_bound, upper_bound, mean, std: np.float64
+SubjectStats = namedtuple("SubjectStats", "count order lower_bound upper_bound n_below n_above mean std")
 
 
 def _device(device):
@@ -108,24 +127,117 @@ def cal_mean_std(subjects, mods=MODS, device=None):
     return out
 
 
-def normalize_subject(raw, mean_std, truth=None, mods=MODS, device=None):
+class ZScore:
+    """The second normalisation scheme (include/n3d.h, "a second normalisation"): per subject and per modality, the brain voxels'
+    counts are clipped to their `lower` and `upper` percentiles (in percent, numpy's linear np.percentile) and z-scored with the
+    mean and std of the clipped counts.  ZScore(0, 100) clips nothing: plain z-scoring.  Needs no data-set statistics."""
+
+    def __init__(self, lower=0.5, upper=99.5):
+        try:
+            lo, hi = float(lower), float(upper)
+        except (TypeError, ValueError):
+            raise N3DError("ZScore: lower and upper are percentiles in percent (got %r, %r)" % (lower, upper)) from None
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo < hi <= 100):
+            raise N3DError("ZScore: needs finite percentiles 0 <= lower < upper <= 100 (got %r, %r)" % (lower, upper))
+        self.lower, self.upper = lo, hi
+
+    def __repr__(self):
+        return "ZScore(lower=%r, upper=%r)" % (self.lower, self.upper)
+
+
+def _truth(truth, X, Y, Z, dev):
+    if truth is None:
+        return None
+    t = torch.from_numpy(np.ascontiguousarray(truth)) if isinstance(truth, np.ndarray) else truth
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) in ((X, Y, Z), (1, X, Y, Z))):
+        raise N3DError("normalize_subject: truth must be a (X, Y, Z) or (1, X, Y, Z) uint8 label volume matching raw")
+    return t.reshape(X, Y, Z).to(dev).contiguous()
+
+
+def _box(h, shape):
+    """create_h5's brain_width (2, 3) and the high corner of the box the reference reads back, from the host copy of the scan's
+    records h (Cm, REC_WORDS) int64"""
+    start = np.maximum(h[:, 2:5] - 1, 0).min(axis=0)
+    end = np.minimum(h[:, 5:8] + 1, shape).max(axis=0)
+    return np.vstack((start, end)), np.minimum(end + 1, shape)
+
+
+def _robust(lib, r, scheme, mods, dev, what):
+    """n3d_brain_scan, n3d_brain_hist and n3d_brain_robust of one subject and ONE host sync -> (rec int64 (Cm, REC_WORDS) on the
+    host, the records as a ROBUST_DTYPE array (Cm,), the device tensor that holds the records for n3d_brain_zscore)"""
+    if not isinstance(scheme, ZScore):
+        raise N3DError("%s: scheme must be a preprocess.ZScore (got %r)" % (what, scheme))
+    Cm, X, Y, Z = (int(s) for s in r.shape)
+    if Cm != len(mods):
+        raise N3DError("%s: raw has %d modalities, mods names %d" % (what, Cm, len(mods)))
+    # one buffer, one copy each way: Cm robust records, then the scan's records (two int32 per word)
+    init = np.zeros(Cm * (ROBUST_WORDS + REC_WORDS // 2), np.int64)
+    init[Cm * ROBUST_WORDS:].view(np.int32)[:] = np.tile(np.array(_REC_INIT, np.int32), Cm)
+    buf = torch.from_numpy(init).to(dev)
+    rob, rec = buf[:Cm * ROBUST_WORDS], buf[Cm * ROBUST_WORDS:].view(torch.int32).view(Cm, REC_WORDS)
+    hist = torch.empty((Cm, HIST_BINS), dtype=torch.int32, device=dev)
+    _scan(lib, r, torch.zeros((Cm, 2), dtype=torch.int64, device=dev), rec)
+    check(lib.n3d_brain_hist(K.ptr(r), Cm, X, Y, Z, K.ptr(rec), K.ptr(hist), K.stream_ptr()), "n3d_brain_hist")
+    check(lib.n3d_brain_robust(K.ptr(hist), Cm, scheme.lower, scheme.upper, K.ptr(rob), K.stream_ptr()), "n3d_brain_robust")
+    host = buf.cpu().numpy()                                   # the one sync
+    h = host[Cm * ROBUST_WORDS:].view(np.int32).reshape(Cm, REC_WORDS).astype(np.int64)
+    for c, m in enumerate(mods):
+        if h[c, 5] < 0:
+            raise N3DError("%s: modality %s has no nonzero voxel" % (what, m))
+    return h, host[:Cm * ROBUST_WORDS].view(ROBUST_DTYPE), rob
+
+
+def subject_stats(raw, scheme, mods=MODS, device=None):
+    """what ZScore normalisation of this subject rests on, per modality (a tuple of SubjectStats in the order of mods): the brain
+    voxels' count, the four order statistics around the two percentiles, the bounds, the voxels clipped at either end and the mean
+    and std of the clipped counts, as n3d_brain_robust formed them.  One host sync."""
+    dev, lib = _device(device), _lib.load()
+    r = _raw(raw, dev, "subject_stats")
+    _, rr, _ = _robust(lib, r, scheme, mods, dev, "subject_stats")
+    return tuple(SubjectStats(int(q["count"]), tuple(int(v) for v in q["order"]), np.float64(q["lower"]), np.float64(q["upper"]),
+                              int(q["n_below"]), int(q["n_above"]), np.float64(q["mean"]), np.float64(q["std"])) for q in rr)
+
+
+def _normalize_zscore(lib, r, t, scheme, mods, dev):
+    Cm, X, Y, Z = (int(s) for s in r.shape)
+    h, rr, rob = _robust(lib, r, scheme, mods, dev, "normalize_subject")
+    for c, m in enumerate(mods):
+        if rr[c]["count"] < 2:
+            raise N3DError("normalize_subject: modality %s has %d nonzero voxel: z-scoring needs at least two" % (m, rr[c]["count"]))
+        if not rr[c]["std"] > 0:
+            raise N3DError("normalize_subject: modality %s has a single value (%g) after clipping to [%g, %g]: std == 0, the z-score "
+                           "is 0 / 0" % (m, rr[c]["mean"], rr[c]["lower"], rr[c]["upper"]))
+    brain_width, hi = _box(h, np.array([X, Y, Z], np.int64))
+    b = [int(v) for v in hi - brain_width[0]]
+    out = torch.empty((Cm, *b), dtype=torch.float32, device=dev)
+    t_out = torch.empty(b, dtype=torch.uint8, device=dev) if t is not None else None
+    check(lib.n3d_brain_zscore(K.ptr(r), Cm, X, Y, Z, K.ptr(rob), (C.c_int32 * 3)(*[int(v) for v in brain_width[0]]),
+                               (C.c_int32 * 3)(*[int(v) for v in hi]), K.ptr(out), K.ptr(t), K.ptr(t_out), K.stream_ptr()),
+          "n3d_brain_zscore")
+    return out, t_out, brain_width
+
+
+def normalize_subject(raw, mean_std, truth=None, mods=MODS, device=None, scheme=None):
     """raw (Cm, X, Y, Z) int16, truth (X, Y, Z) or (1, X, Y, Z) uint8 or None -> (box_volume, box_truth, brain_width):
     box_volume (Cm, bx, by, bz) fp32 device tensor, the normalised modalities (create_h5:58-60) cropped to the box the reference
     reads back (patches.py:140-142: start : end + 1, clipped to the image); box_truth the same crop of truth (None without);
     brain_width the (2, 3) int64 array create_h5:63-65 stores -- its end row equals the image size on an axis where the brain
-    touches the high face.  One host sync (the outlines decide the size of the box)."""
+    touches the high face.  One host sync (the outlines decide the size of the box).
+    scheme: None -- the reference's rule with the dictionary mean_std; a ZScore -- that rule from the subject alone (mean_std must
+    be None), same box, same brain_width, nonzero exactly where raw is."""
     dev, lib = _device(device), _lib.load()
     r = _raw(raw, dev, "normalize_subject")
     Cm, X, Y, Z = (int(s) for s in r.shape)
+    if scheme is not None:
+        if mean_std is not None:
+            raise N3DError("normalize_subject: a scheme takes its statistics from the subject: give mean_std or scheme, not both")
+        return _normalize_zscore(lib, r, _truth(truth, X, Y, Z, dev), scheme, mods, dev)
+    if mean_std is None:
+        raise N3DError("normalize_subject: needs the mean / std dictionary of cal_mean_std, or a scheme (preprocess.ZScore)")
     if Cm != len(mods):
         raise N3DError("normalize_subject: raw has %d modalities, mods names %d" % (Cm, len(mods)))
     ms = np.array([[np.float64(mean_std["%s_mean" % m]), np.float64(mean_std["%s_std" % m])] for m in mods], np.float64)
-    t = None
-    if truth is not None:
-        t = torch.from_numpy(np.ascontiguousarray(truth)) if isinstance(truth, np.ndarray) else truth
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) in ((X, Y, Z), (1, X, Y, Z))):
-            raise N3DError("normalize_subject: truth must be a (X, Y, Z) or (1, X, Y, Z) uint8 label volume matching raw")
-        t = t.reshape(X, Y, Z).to(dev).contiguous()
+    t = _truth(truth, X, Y, Z, dev)
     ms_d = torch.from_numpy(ms).to(dev)
     rec = _records(1, Cm, dev)[0]
     _scan(lib, r, torch.zeros((Cm, 2), dtype=torch.int64, device=dev), rec)
@@ -139,10 +251,8 @@ def normalize_subject(raw, mean_std, truth=None, mods=MODS, device=None):
         if not z[1] > z[0]:
             raise N3DError("normalize_subject: modality %s has a single nonzero value (%d): zmax == zmin, the min-max quotient "
                            "is 0 / 0" % (m, h[c, 0]))
-    start = np.maximum(h[:, 2:5] - 1, 0).min(axis=0)
-    end = np.minimum(h[:, 5:8] + 1, shape).max(axis=0)
-    brain_width = np.vstack((start, end))
-    hi = np.minimum(end + 1, shape)
+    brain_width, hi = _box(h, shape)
+    start = brain_width[0]
     b = [int(v) for v in hi - start]
     out = torch.empty((Cm, *b), dtype=torch.float32, device=dev)
     t_out = torch.empty(b, dtype=torch.uint8, device=dev) if t is not None else None
