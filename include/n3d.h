@@ -629,6 +629,59 @@ typedef struct n3d_patch_volume {
  * volume and for a volume index outside [0, nvol). */
 int n3d_patch_qualify(const n3d_patch_volume* vols, int nvol, const int32_t* cand, int64_t N, int P, uint8_t* flags, void* stream);
 
+/* ---- random and foreground-centred crops, drawn on the device (none of it the reference's: nnU-Net's oversampled foreground,
+ * MONAI's RandCropByPosNegLabel / RandCropByLabelClasses, TorchIO's LabelSampler).  Instead of the fixed candidate grid, an epoch's
+ * candidate table is drawn: each sample is a uniformly random corner, or -- with probability fg_threshold / 2^32 -- the corner that
+ * centres the patch on a uniformly random voxel of a mask.  The table has n3d_patch_qualify's format and goes through it unchanged.
+ *
+ * Masks (N3D_SAMPLE_MASKS of them; mask m is bit m of `masks`): 0 brain = some channel is nonzero ("nonzero" as above: -0.0 is
+ * zero, NaN / inf / denormals are not), 1 tumour = label != 0, 2 = label 1, 3 = label 2, 4 = label 4.
+ *
+ * Line index of a volume: index is (N3D_SAMPLE_MASKS, X*Y + 1) int32.  A line is one (x, y), l = x*Y + y, its Z voxels in C order.
+ * index[m][l] = the number of mask-m voxels in the lines before l; index[m][X*Y] = the mask's total: the exclusive prefix sum
+ * np.concatenate(([0], np.cumsum(mask.reshape(X*Y, Z).sum(1)))).  With truth NULL rows 1 to 4 are zero.  X * Y * Z < 2^31.  Exact
+ * integers (ballots and popcounts, an integer scan: no floating point, no atomics), so two runs give the same bits.  Two launches:
+ * one wave per line, then one workgroup per mask.  index: 20 * (X*Y + 1) bytes of device memory. */
+#define N3D_SAMPLE_MASKS 5
+int n3d_volume_line_index(const float* vol, int Cv, const uint8_t* truth, int X, int Y, int Z, int32_t* index, void* stream);
+
+/* N samples in ONE launch (one wave per sample; no sample waits for another).  vols: the DEVICE table of nvol records; index: a DEVICE
+ * array of nvol pointers, entry v the line index of volume v (every volume named in ids must have one); ids: a DEVICE array of the
+ * n_ids volume indices to draw from; cand: DEVICE (N, 4) int32, 16-byte aligned, rows (volume index, corner x, y, z); mode: DEVICE
+ * uint8 (N).  P: the patch edge.  (key0, key1): the epoch's Philox key.  For sample n, 0 <= n < N <= N3D_SAMPLE_MAX = 2^24:
+ *   draws:       w0..w3 = Philox4x32-10 (the constants and rounds of n3d_appear_desc's noise stage) of the counter (n, 2, 0, 0) and
+ *                u0..u3 of the counter (n, 3, 0, 0), both under the key (key0, key1).  (Counter words 0 and 1 in the second place are
+ *                the appearance noise's and the elastic lattice's.)
+ *   reduction:   reduce(q, R) = (uint32_t)(((uint64_t)q * R) >> 32), in [0, R) for R >= 1; value i is taken by floor or ceil of
+ *                2^32 / R words, so the bias of any value is below R / 2^32 relative.
+ *   volume:      v = ids[reduce(u0, n_ids)], its dims D[3] = (X, Y, Z).
+ *   foreground:  the sample is foreground-centred iff (uint64_t)u1 < fg_threshold; fg_threshold in [0, 2^32] (0: never; 2^32: always;
+ *                the host passes round(p * 2^32)).
+ *   mask:        of the masks whose bit is set in `masks`, those with index[m][X*Y] > 0 in volume v, in ascending m: k of them.
+ *                k > 0: the mask is the reduce(u2, k)-th of them (from 0).  k == 0: the sample falls back to a uniform corner.
+ *   voxel:       T = index[m][X*Y], r = reduce(w0, T); the line l is the largest with index[m][l] <= r (binary search:
+ *                np.searchsorted(row, r, side="right") - 1); the voxel is the (r - index[m][l])-th mask voxel of line l (from 0) in
+ *                ascending z.  That is voxel r of np.argwhere(mask): uniform over the mask's voxels.  (x, y) = (l / Y, l % Y).
+ *   corner:      per axis a: D[a] >= P: lo = 0, hi = D[a] - P; else lo = hi = -((P - D[a]) / 2) (a box smaller than the patch is
+ *                centred; the gather zero-pads it); integer division.  Foreground: c[a] = min(max(voxel[a] - P / 2, lo), hi) --
+ *                unclamped, the voxel sits at patch index P / 2.  Uniform and fallback: c[a] = lo + reduce(w[1 + a], hi - lo + 1).
+ *   outputs:     cand[n] = (v, c[0], c[1], c[2]);  mode[n] = the mask m for a foreground sample, N3D_SAMPLE_MODE_UNIFORM for a
+ *                uniform one, N3D_SAMPLE_MODE_FALLBACK for the fallback.
+ * An id outside [0, nvol) cannot be refused on the host (ids lives on the device): such a sample writes cand[n] = (id, 0, 0, 0) and
+ * mode[n] = N3D_SAMPLE_MODE_BAD_ID and touches no volume; n3d_patch_qualify flags it 0.  A volume whose index pointer is NULL is
+ * treated the same way.
+ * The decision is per sample: there is no per-batch guarantee such as nnU-Net's "the last third of every batch is forced".
+ * N3D_ERR_INVALID before any launch: masks == 0 with fg_threshold > 0, or bits beyond the five masks; fg_threshold > 2^32; n_ids,
+ * P, nvol or Cv < 1; N < 0 or N > N3D_SAMPLE_MAX; a NULL table; cand not 16-byte aligned (vols, index: 8; ids: 4).  N == 0 (with
+ * legal scalars) returns N3D_OK without a launch and reads no table. */
+#define N3D_SAMPLE_MAX 16777216
+#define N3D_SAMPLE_MODE_UNIFORM 255
+#define N3D_SAMPLE_MODE_FALLBACK 254
+#define N3D_SAMPLE_MODE_BAD_ID 253
+int n3d_patch_sample(const n3d_patch_volume* vols, const int32_t* const* index, int nvol, int Cv, const int32_t* ids, int n_ids,
+                     int64_t N, int P, uint32_t key0, uint32_t key1, uint64_t fg_threshold, int masks, int32_t* cand, uint8_t* mode,
+                     void* stream);
+
 /* n3d_patch_batch for a batch whose patches come from different volumes of a set: descriptor = n3d_patch_desc + volume index.
  * Output bit-identical to n3d_patch_batch on each patch's own volume.  vols: the DEVICE table of nvol records; descs: HOST array
  * of at most N3D_PATCH_MAX_BATCH (perm and volume index checked here).  With t_out, a record without truth gives label 0. */

@@ -258,6 +258,8 @@ PROTOTYPES = {
     "n3d_patch_batch": (_i, [_p, _i, _p, _i, _i, _i, C.POINTER(PatchDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_volume_sat": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
     "n3d_patch_qualify": (_i, [_p, _i, _p, _i64, _i, _p, _p]),
+    "n3d_volume_line_index": (_i, [_p, _i, _p, _i, _i, _i, _p, _p]),
+    "n3d_patch_sample": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, C.c_uint32, C.c_uint32, C.c_uint64, _i, _p, _p, _p]),
     "n3d_patch_gather": (_i, [_p, _i, _i, C.POINTER(GatherDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_aug": (_i, [_p, _i, _i, C.POINTER(AugDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_warp": (_i, [_p, _i, _i, C.POINTER(WarpDesc), _i, _i, _i, _p, _i64, _p, _p]),

@@ -28,8 +28,12 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
   * augment_appearance (appearance.Appearance; not the reference's either) adds Gaussian noise, Gaussian blur, contrast and gamma of
     the brain voxels, applied to the gathered batch in place by n3d_patch_appearance (1 to 10 launches, no host sync).
 
+  * sampling (sampling.RandomCrop; not the reference's either) replaces the candidate grid by crops drawn on the device, uniformly
+    or centred on a random voxel of a mask (n3d_volume_line_index once per volume, ONE n3d_patch_sample launch per epoch); the
+    drawn table takes the grid's place, so qualification, the epoch's order and every gather above are what they were.
+
 Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather, n3d_patch_gather_aug,
-n3d_patch_gather_warp, n3d_patch_gather_elastic and n3d_patch_appearance (include/n3d.h).
+n3d_patch_gather_warp, n3d_patch_gather_elastic, n3d_patch_appearance, n3d_volume_line_index and n3d_patch_sample (include/n3d.h).
 """
 from __future__ import annotations
 
@@ -42,6 +46,7 @@ import torch
 
 from . import _lib, appearance, datastep, predict, preprocess
 from . import elastic as elastic_mod
+from . import sampling as sampling_mod
 from . import kernels as K
 from ._lib import AugDesc, ElasticDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, WarpDesc, check
 
@@ -233,6 +238,9 @@ class VolumeSet:
         self.channels = None
         self.has_truth = None
         self.records = None        # device table of n3d_patch_volume records (rebuilt by add)
+        self.line_indexes = []     # per volume: its n3d_volume_line_index table, built by line_index(i) when first asked for
+        self.index_ptrs = None     # device array of their addresses, 0 where none is built (rebuilt by index_table)
+        self._index_ptrs_of = None
 
     def __len__(self):
         return len(self.volumes)
@@ -315,6 +323,54 @@ class VolumeSet:
             check(_lib.load().n3d_patch_qualify(K.ptr(self.records), len(self), K.ptr(cand), N, int(patch), K.ptr(flags),
                                                 K.stream_ptr()), "n3d_patch_qualify")
         return flags
+
+    def line_index(self, i):
+        """volume i's line index: (5, X*Y + 1) int32, row m the exclusive prefix counts of mask m's voxels per (x, y) line
+        (include/n3d.h, n3d_volume_line_index; masks: sampling.MASKS).  Built on first use (two launches), then kept."""
+        if not 0 <= int(i) < len(self):
+            raise N3DError("VolumeSet.line_index: no volume %r in a set of %d" % (i, len(self)))
+        i = int(i)
+        self.line_indexes += [None] * (len(self) - len(self.line_indexes))
+        if self.line_indexes[i] is None:
+            X, Y, Z = self.boxes[i]
+            index = torch.empty((len(sampling_mod.MASKS), X * Y + 1), dtype=torch.int32, device=self.device)
+            check(_lib.load().n3d_volume_line_index(K.ptr(self.volumes[i]), self.channels, K.ptr(self.truths[i]), X, Y, Z, K.ptr(index),
+                                                    K.stream_ptr()), "n3d_volume_line_index")
+            self.line_indexes[i] = index
+        return self.line_indexes[i]
+
+    def index_table(self):
+        """the device array of the set's line-index addresses (0: not built), rebuilt when a volume or an index was added"""
+        have = [t.data_ptr() if t is not None else 0 for t in self.line_indexes] + [0] * (len(self) - len(self.line_indexes))
+        if self._index_ptrs_of != have:
+            self.index_ptrs = torch.tensor(have, dtype=torch.int64).to(self.device)
+            self._index_ptrs_of = have
+        return self.index_ptrs
+
+    def sample(self, ids, n, patch, key, foreground=1 / 3, masks=("tumour",)):
+        """n crops of edge `patch` from the volumes `ids` (an index may repeat: it is drawn that much more often), by the rule of
+        include/n3d.h, n3d_patch_sample: a uniform corner, or with probability `foreground` the corner centring the patch on a
+        uniformly random voxel of one of `masks` (sampling.MASKS).  key: the Philox key (k0, k1).  Returns (cand, mode): the device
+        (n, 4) int32 table qualify_table / patch_batch understand and the device uint8 modes (the mask 0..4, 255 uniform, 254 no
+        requested mask in the volume).  Builds the missing line indexes, then ONE n3d_patch_sample launch and no sync."""
+        ids = [int(i) for i in ids]
+        if not ids or not all(0 <= i < len(self) for i in ids):
+            raise N3DError("VolumeSet.sample: ids are indices of the set's %d volumes, at least one (got %r)" % (len(self), ids))
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= sampling_mod.MAX_SAMPLES:
+            raise N3DError("VolumeSet.sample: n is an integer in 0 .. %d (N3D_SAMPLE_MAX; got %r)" % (sampling_mod.MAX_SAMPLES, n))
+        bits, thr = sampling_mod.mask_bits(masks, "VolumeSet.sample"), sampling_mod.fg_threshold(foreground, "VolumeSet.sample")
+        if thr and bits & ~1 and not self.has_truth:
+            raise N3DError("VolumeSet.sample: a set without truth has the mask \"brain\" only (got %r)" % (masks,))
+        for i in sorted(set(ids)):
+            self.line_index(i)
+        n = int(n)
+        cand = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        mode = torch.empty(n, dtype=torch.uint8, device=self.device)
+        dev_ids = torch.tensor(ids, dtype=torch.int32).to(self.device)
+        check(_lib.load().n3d_patch_sample(K.ptr(self.records), K.ptr(self.index_table()), len(self), self.channels, K.ptr(dev_ids),
+                                           len(ids), n, int(patch), int(key[0]), int(key[1]), thr, bits, K.ptr(cand), K.ptr(mode),
+                                           K.stream_ptr()), "n3d_patch_sample")
+        return cand, mode
 
     def fits(self, out, B, patch, target_dtype):
         """out = (x, t) can take a batch of B patches in place: x (B, Cv, P, P, P) fp32 in NDHWC storage on the set's device, t
@@ -527,6 +583,16 @@ class Generator:
     A batch with a deformed patch is ONE n3d_patch_gather_elastic launch, any other batch the launch it was without the option.  It
     composes with every option above; left None, the generator makes the calls, draws, launches and bits it made without it.
 
+    sampling=sampling.RandomCrop(patches_per_epoch, foreground, masks): the epoch's candidates are not the grid's but crops drawn on
+    the device (include/n3d.h, n3d_patch_sample): patches_per_epoch of them over indices_list, each a uniformly random corner or,
+    with probability `foreground`, the corner centring the patch on a uniformly random voxel of one of `masks`.  patch_overlap and
+    both_ps describe the grid and raise N3DError with it, and so does a mask other than "brain" on a set without truth.
+    epoch_init() then draws the epoch's key from np_rng -- randint(0, 2**32, 2, dtype=np.uint32), ahead of every other draw of the
+    epoch --, builds the line indexes that are missing, makes ONE n3d_patch_sample launch, copies the table and the modes to the
+    host (candidates, sample_modes, sample_key) and qualifies the table as it does the grid's: skip_health and the empty-patch
+    filter keep their meaning, n_patches and steps_per_epoch follow from the flags.  epoch() calls epoch_init() after its last
+    batch, so every epoch has fresh crops.  Left None, the generator makes the calls, draws, launches and bits it made without it.
+
     epoch_init(): one n3d_patch_qualify launch and one device -> host copy of the candidates' flag bytes.
     epoch(out=None): a generator of (x, t) device tensors (t None without truth), one n3d_patch_gather launch per batch
     (n3d_patch_gather_aug with augment) on the current stream.  out: a tuple (x, t) or a zero-argument callable returning one (e.g. trainer.input_buffers), evaluated per
@@ -537,7 +603,7 @@ class Generator:
                  shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None,
                  augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None, augment_rotation=None,
                  augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None, augment_appearance=None,
-                 augment_elastic=None):
+                 augment_elastic=None, sampling=None):
         if labels is not None and list(labels) != LABELS:
             raise N3DError("Generator: labels must be None or [1, 2, 4] (the three BraTS regions the kernels expand)")
         ps = [patch_shape] * 3 if isinstance(patch_shape, int) else [int(p) for p in patch_shape]
@@ -588,6 +654,19 @@ class Generator:
                 raise N3DError("Generator: batch_size must be 1..%d with augment_elastic (N3D_PATCH_ELASTIC_MAX_BATCH)" % ELASTIC_MAX_BATCH)
             augment_elastic.check(ps[0])
         self.augment_elastic = augment_elastic
+        if sampling is not None:
+            if not isinstance(sampling, sampling_mod.RandomCrop):
+                raise N3DError("Generator: sampling is a sampling.RandomCrop (got %r)" % (sampling,))
+            if patch_overlap is not None or both_ps:
+                raise N3DError("Generator: patch_overlap and both_ps describe the candidate grid, which sampling replaces")
+            if not callable(getattr(volumes, "sample", None)):
+                raise NotImplementedError("Generator: sampling needs a volume set that draws crops on the device (VolumeSet.sample); "
+                                          "%s has none" % type(volumes).__name__)
+            if sampling.needs_truth() and not getattr(volumes, "has_truth", False):
+                raise N3DError("Generator: sampling from the masks %r needs a volume set with truth (without it there is \"brain\" only)"
+                               % (sampling.masks,))
+        self.sampling = sampling
+        self.sample_key = self.sample_modes = None
         self.affine = check_affine(affine) if augment else affine
         if augment:
             # fail here, not in the middle of an epoch with draws already consumed: the batches are made by volumes.patch_batch,
@@ -633,6 +712,8 @@ class Generator:
 
     def epoch_init(self):
         """generator.py:118-168: draw the epoch's overlap, list the candidates, qualify them on the device, count the kept ones"""
+        if self.sampling is not None:
+            return self._sampled_epoch_init()
         ov = draw_overlap(self.patch_overlap, self.rng)
         if ov is not None and ov >= self.patch:
             raise N3DError("Generator: drawn overlap %d >= patch %d -- the reference divides by zero here (patches.py:59-67: the "
@@ -640,6 +721,19 @@ class Generator:
         self.overlap = ov
         self.candidates = candidate_table([self.volumes.box(i) for i in range(len(self.volumes))], self.indices_list, self.patch,
                                           ov, self.both_ps)
+        self.flags = self.volumes.qualify_table(self.candidates, self.patch).cpu().numpy()
+        self.n_patches = int(kept_mask(self.flags, self._skip_health()).sum())
+        self.steps_per_epoch = -(-self.n_patches // self.batch_size)
+
+    def _sampled_epoch_init(self):
+        """epoch_init() with sampling: the epoch's key, one n3d_patch_sample launch over indices_list, the table and the modes to the
+        host, then the grid's qualification"""
+        c = self.sampling
+        self.overlap = None
+        self.sample_key = c.draw(self.np_rng)
+        cand, mode = self.volumes.sample(self.indices_list, c.patches_per_epoch, self.patch, self.sample_key, c.foreground, c.masks)
+        self.candidates = cand.cpu().numpy()
+        self.sample_modes = mode.cpu().numpy()
         self.flags = self.volumes.qualify_table(self.candidates, self.patch).cpu().numpy()
         self.n_patches = int(kept_mask(self.flags, self._skip_health()).sum())
         self.steps_per_epoch = -(-self.n_patches // self.batch_size)
@@ -663,7 +757,7 @@ class Generator:
             fit = o if self.volumes.fits(o, B, self.patch, self.target_dtype) else None
             yield self._appear(self.volumes.patch_batch(refs, self.patch, self.inclusive_label, self.target_dtype, out=fit, augment=aug,
                                                         **self._elastic_entries(batch, 3)), batch)
-        if self.patch_overlap:
+        if self.patch_overlap or self.sampling is not None:
             self.epoch_init()
 
     def _appearance_draws(self):
@@ -706,5 +800,5 @@ class Generator:
             fit = o if self.volumes.fits(o, B, P, self.target_dtype) else None
             yield self._appear(self.volumes.patch_batch(refs, P, self.inclusive_label, self.target_dtype, out=fit, augment=aug, warp=warp,
                                                         **self._elastic_entries(batch, 4)), batch)
-        if self.patch_overlap:
+        if self.patch_overlap or self.sampling is not None:
             self.epoch_init()
