@@ -858,6 +858,59 @@ int n3d_patch_appearance(void* x, int64_t ld, int B, int Cv, int P, const n3d_ap
                          void* stream);
 size_t n3d_patch_appearance_scratch(int B, int Cv, int P);
 
+/* ---- acquisition artefacts of a gathered batch, in place (none of it the reference's): simulated low resolution (nnU-Net v2's
+ * SimulateLowResolutionTransform), a multiplicative bias field (TorchIO's RandomBiasField) and modality dropout (the BraTS
+ * missing-modality recipes).  x, ld, B, Cv, P: as for n3d_patch_appearance -- DEVICE fp32 (B, Cv, P, P, P) in NDHWC storage with
+ * channel pitch ld >= Cv, the lanes between Cv and ld never touched; B <= N3D_APPEAR_MAX_BATCH, Cv <= 4, 2 <= P <=
+ * N3D_APPEAR_MAX_PATCH.  The descriptors are HOST arrays, one row per patch (plain arrays, not a record type: a caller fills only
+ * the ones whose stage it uses; an array whose stage no patch asks for may be NULL):
+ *   stages  int32 [B][3]   != 0: {low resolution, bias field, dropout} acts on this patch
+ *   n       int32 [B][4]   low resolution: the extent the channel is sampled down to, 1 <= n[c] <= P; n[c] == P: untouched
+ *   order   int32 [B][4]   bias field: the polynomial's order, 0 .. N3D_ARTEFACT_MAX_ORDER
+ *   range   double [B][4]  bias field: the coefficients are uniform in [-range, range); finite, >= 0
+ *   key     uint32 [B][2]  bias field: the patch's Philox key
+ *   drop    int32 [B][4]   dropout: != 0: the channel is zeroed
+ *
+ * The brain mask of a (patch, channel) is x != 0 on entry (-0.0 is zero), taken ONCE before the first stage.  The stages run in the
+ * fixed order low resolution, bias field, dropout, each only on the patches whose flag is set, each on the values the earlier
+ * stages left.  Low resolution and the bias field write only masked voxels: the background stays exactly 0.0f.  All arithmetic is
+ * fp64 on fp32 loads, every product, sum, quotient and library call rounded on its own in the association written; "fp32(..)" is
+ * the one rounding to fp32 where a stage stores.  (i, j, k) is the voxel's index in its patch, k fastest.
+ *
+ *   low resolution  nearest-exact down-sampling of the channel's whole P^3 patch to n^3 followed by trilinear up-sampling back
+ *             (align_corners = False), composed into eight taps of the patch itself.  Per axis, for the output index o:
+ *               src = max(fma((double)n / (double)P, (double)o + 0.5, -0.5), 0.0);  i0 = min((int)src, n - 1);  i1 = i0 + (i0 < n - 1);
+ *               l1 = src - (double)i0;  l0 = 1.0 - l1;  a0 = N(i0), a1 = N(i1) with the INTEGER N(i) = min(((2 i + 1) * P) / (2 n), P - 1)
+ *             (N is what nearest-exact reads: floor((i + 0.5) * P / n), exactly.  The fma is the rule's ONE fused operation: the
+ *             quotient is rounded, then quotient * (o + 0.5) - 0.5 is rounded once, which is how torch's fp64 interpolate
+ *             evaluates its source coordinate.  Rounded in two steps the coordinate errs by up to an ulp of n, and the result
+ *             drifts from torch's with the extent: 6.4e-15 at P = 21 and 2.6e-14 at P = 50 on values in +-3, against 4.4e-15 and
+ *             1.8e-15 fused);
+ *               y = fp32(sum over the taps (ti, tj, tk) = 000, 001, .. 111 (tk fastest), from +0.0, of
+ *                        ((l_ti * l_tj) * l_tk) * x[a_ti, a_tj, a_tk])   (first the product, then acc = acc + product).
+ *             Background zeros take part as taps.  The result does not depend on any read / write order: the launch writes to
+ *             scratch and a second one lands the masked voxels in x.
+ *   bias field  the terms t = 0, 1, .. are (pa, pb, pc) for pa in 0 .. order, pb in 0 .. order - pa, pc in 0 .. order - pa - pb, in
+ *             that nesting (TorchIO's; 20 terms at order 3).  coef_t = (((double)w0 * 2^-32) * 2 - 1) * range[c], w0 the first word
+ *             of Philox4x32-10 (the constants and rounds of n3d_appear_desc's noise stage) of the counter (t, 3, c, 0) under the
+ *             patch's key.  (The second counter word keeps this stream apart from the appearance noise's 0, the elastic lattice's 1
+ *             and the crop sampler's 2.)  X = (double)(2 i - P + 1) / (double)(P - 1), Y and Z the same of j and k (TorchIO's
+ *             (arange(-P/2, P/2) + 0.5) / max); powers by repeated multiplication from 1.0: X^0 = 1, X^e = X^(e-1) * X;
+ *               poly = sum in t order, from +0.0, of coef_t * ((X^pa * Y^pb) * Z^pc);   y = fp32(x * exp(poly)).
+ *   dropout   drop[c] != 0: every voxel of the channel becomes 0.0f.
+ *
+ * How the parameters travel: repacked into the launch arguments of the stage's kernel; nothing is copied to the device and nothing
+ * synchronises.  A stage with nothing to do launches nothing; with nothing to do at all (no flag set, or only n == P and drop == 0)
+ * the call launches nothing and does not look at the scratch.  Launches otherwise: the mask 1, low resolution 2, bias field and
+ * dropout together 1.  No atomics: two runs on the same input give the same bits.  Bad arguments (B, Cv or P out of range, n outside
+ * 1 .. P, an order beyond N3D_ARTEFACT_MAX_ORDER, a range that is negative or not finite, a scratch that is too small) return
+ * N3D_ERR_INVALID before any launch.  scratch: DEVICE, 16-byte aligned, n3d_patch_artefact_scratch(B, Cv, P) bytes (0 for
+ * arguments out of range): a mask byte per voxel and the low-resolution stage's fp32 output, 16 bytes per voxel. */
+#define N3D_ARTEFACT_MAX_ORDER 3
+int n3d_patch_artefact(void* x, int64_t ld, int B, int Cv, int P, const int32_t* stages, const int32_t* n, const int32_t* order,
+                       const double* range, const uint32_t* key, const int32_t* drop, void* scratch, size_t scratch_bytes, void* stream);
+size_t n3d_patch_artefact_scratch(int B, int Cv, int P);
+
 /* ---- the step before the data step (preprocess.py:77-144, create_h5:58-66): raw scanner counts to the statistics of the data
  * set and to each subject's normalised brain-wise box.  raw: DEVICE int16 (Cm, X, Y, Z) contiguous, 2-byte aligned (a modality's
  * base need not be 16-byte aligned: X * Y * Z may be odd); X * Y * Z < 2^31.  "Brain" = the voxels with raw != 0, per modality.

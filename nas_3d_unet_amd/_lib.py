@@ -266,6 +266,9 @@ PROTOTYPES = {
     "n3d_patch_gather_elastic": (_i, [_p, _i, _i, C.POINTER(ElasticDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_appearance": (_i, [_p, _i64, _i, _i, _i, C.POINTER(AppearDesc), _p, _sz, _p]),
     "n3d_patch_appearance_scratch": (_sz, [_i, _i, _i]),
+    "n3d_patch_artefact": (_i, [_p, _i64, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                C.POINTER(C.c_uint32), C.POINTER(C.c_int32), _p, _sz, _p]),
+    "n3d_patch_artefact_scratch": (_sz, [_i, _i, _i]),
     "n3d_brain_scan": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "n3d_brain_sqdev_rows": (_i, [_i64]),
     "n3d_brain_sqdev": (_i, [_p, _i, _i64, _p, _p, _p, _p]),

@@ -30,31 +30,7 @@ struct ApChan { double p[AP_B][4]; uint32_t active; };
 // chunk partials in scratch, each [B][nchunk][4]
 struct ApPart { double *S, *Q, *S2, *Q2; float *lo, *hi; int32_t* n; };
 
-// A voxel's channels.  V4: Cv == 4 on a 16-byte aligned batch with ld % 4 == 0 -- one 16-byte access per voxel; four 4-byte ones
-// make every wave touch the same kilobyte four times.  A V4 store writes the channels outside the mask back with the bits they were
-// loaded with (the voxel belongs to this thread alone).
-template <bool V4>
-__device__ __forceinline__ void ld_vox(const float* __restrict__ p, int Cv, float (&f)[4]) {
-  if (V4) {
-    const float4 q = ld4(p);
-    f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) f[c] = 0.f;
-    N3D_EACH_CHANNEL(c, Cv) f[c] = p[c];
-  }
-}
-template <bool V4>
-__device__ __forceinline__ void st_vox(float* __restrict__ p, int Cv, int m, const float (&f)[4]) {
-  if (V4) {
-    if (m) st4(p, make_float4(f[0], f[1], f[2], f[3]));
-  } else {
-    N3D_EACH_CHANNEL(c, Cv) {
-      if ((m >> c) & 1) p[c] = f[c];
-    }
-  }
-}
-
+// a voxel's channels: ld_vox / st_vox (n3d_common.h)
 template <bool V4>
 __global__ __launch_bounds__(256) void appear_mask_kernel(const float* __restrict__ x, int64_t ld, int Cv, uint32_t nvox, uint8_t* __restrict__ mask) {
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
@@ -64,6 +40,13 @@ __global__ __launch_bounds__(256) void appear_mask_kernel(const float* __restric
   int m = 0;
   N3D_EACH_CHANNEL(c, Cv) m |= nonzero_f32(f[c]) << c;
   mask[v] = (uint8_t)m;
+}
+
+int launch_brain_mask(const float* x, int64_t ld, int Cv, uint32_t nvox, uint8_t* mask, hipStream_t s) {
+  if (Cv == 4 && ld % 4 == 0 && aligned16(x)) N3D_LAUNCH(appear_mask_kernel<true>, dim3((unsigned)cdiv(nvox, 256)), dim3(256), 0, s, x, ld, Cv, nvox, mask);
+  else N3D_LAUNCH(appear_mask_kernel<false>, dim3((unsigned)cdiv(nvox, 256)), dim3(256), 0, s, x, ld, Cv, nvox, mask);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
 }
 
 // ---- noise (philox4x32_10: n3d_common.h)
@@ -551,8 +534,7 @@ extern "C" int n3d_patch_appearance(void* x, int64_t ld, int B, int Cv, int P, c
     else N3D_LAUNCH(kernel_<false>, __VA_ARGS__);     \
   } while (0)
   const dim3 gv((unsigned)cdiv(P3, 256), (unsigned)B), gc((unsigned)L.nchunk, (unsigned)B);
-  AP_LAUNCH_V(appear_mask_kernel, dim3((unsigned)cdiv(nvox, 256)), dim3(256), 0, s, xf, ld, Cv, nvox, mask);
-  N3D_LAUNCH_CHECK();
+  if (int rc = launch_brain_mask(xf, ld, Cv, nvox, mask, s)) return rc;
   if (an.active) {
     AP_LAUNCH_V(appear_noise_kernel, gv, dim3(256), 0, s, xf, ld, Cv, P3, mask, an);
     N3D_LAUNCH_CHECK();

@@ -102,6 +102,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 }
 #endif
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the brain mask of a gathered fp32 batch of nvox voxels at pitch ld: mask[v] bit c = (channel c of voxel v != 0); one launch
+// (appearance.hip; n3d_patch_appearance and n3d_patch_artefact take it once, before their first stage).  N3D_OK or N3D_ERR_HIP.
+int launch_brain_mask(const float* x, int64_t ld, int Cv, uint32_t nvox, uint8_t* mask, hipStream_t s);
 // a stitch chunk's bounding box [lo, hi) on the brain-wide grid, clipped to the box `dims`: its corner b0 and sizes bs inside the
 // box; false: wholly outside (n3d_stitch_add, n3d_stitch_add_w: the launch covers the clipped box and nothing else)
 static inline bool stitch_clip_box(const int32_t* lo, const int32_t* hi, const int (&dims)[3], int (&b0)[3], int (&bs)[3]) {
@@ -242,6 +245,30 @@ __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return __builtin_bit_cast(float, (uint32_t)*p << 16); }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = (bf16_t)(pack_bf16x2(v, 0.f) & 0xffffu); }
+// A voxel's channels of a gathered fp32 batch (appearance.hip, artefact.hip).  V4: Cv == 4 on a 16-byte aligned batch with
+// ld % 4 == 0 -- one 16-byte access per voxel; four 4-byte ones make every wave touch the same kilobyte four times.  A V4 store
+// writes the channels outside the mask m back with the bits they were loaded with (the voxel belongs to this thread alone).
+template <bool V4>
+__device__ __forceinline__ void ld_vox(const float* __restrict__ p, int Cv, float (&f)[4]) {
+  if (V4) {
+    const float4 q = ld4(p);
+    f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) f[c] = 0.f;
+    N3D_EACH_CHANNEL(c, Cv) f[c] = p[c];
+  }
+}
+template <bool V4>
+__device__ __forceinline__ void st_vox(float* __restrict__ p, int Cv, int m, const float (&f)[4]) {
+  if (V4) {
+    if (m) st4(p, make_float4(f[0], f[1], f[2], f[3]));
+  } else {
+    N3D_EACH_CHANNEL(c, Cv) {
+      if ((m >> c) & 1) p[c] = f[c];
+    }
+  }
+}
 #endif
 
 #ifdef __HIPCC__

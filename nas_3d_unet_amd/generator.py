@@ -28,12 +28,17 @@ generator.py:195-217), once to count the epoch's steps and once more during the 
   * augment_appearance (appearance.Appearance; not the reference's either) adds Gaussian noise, Gaussian blur, contrast and gamma of
     the brain voxels, applied to the gathered batch in place by n3d_patch_appearance (1 to 10 launches, no host sync).
 
+  * augment_artefact (artefact.Artefact; not the reference's either) adds simulated low resolution, a multiplicative bias field and
+    modality dropout, applied to the gathered batch in place by n3d_patch_artefact after the appearance transforms (1 to 4
+    launches, no host sync).
+
   * sampling (sampling.RandomCrop; not the reference's either) replaces the candidate grid by crops drawn on the device, uniformly
     or centred on a random voxel of a mask (n3d_volume_line_index once per volume, ONE n3d_patch_sample launch per epoch); the
     drawn table takes the grid's place, so qualification, the epoch's order and every gather above are what they were.
 
 Host logic only; the kernels are n3d_volume_sat, n3d_patch_qualify, n3d_patch_gather, n3d_patch_gather_aug,
-n3d_patch_gather_warp, n3d_patch_gather_elastic, n3d_patch_appearance, n3d_volume_line_index and n3d_patch_sample (include/n3d.h).
+n3d_patch_gather_warp, n3d_patch_gather_elastic, n3d_patch_appearance, n3d_patch_artefact, n3d_volume_line_index and n3d_patch_sample
+(include/n3d.h).
 """
 from __future__ import annotations
 
@@ -45,6 +50,7 @@ import numpy as np
 import torch
 
 from . import _lib, appearance, datastep, predict, preprocess
+from . import artefact as artefact_mod
 from . import elastic as elastic_mod
 from . import sampling as sampling_mod
 from . import kernels as K
@@ -188,7 +194,7 @@ def draw_warp(np_rng, rotation=None, intensity_scale=None, intensity_shift=None,
 
 
 def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=False, augment=None, warp=None, appearance=None,
-                elastic=None):
+                elastic=None, artefact=None):
     """generator.py:170-217 on qualification flags: yields each batch as a list of (candidate index, isometry key or None).
     The candidate order is shuffled at the first next() (rng.shuffle, if `shuffle`), then pop()ped from the end; a kept candidate
     draws its key (rng.choice over KEYS, if `permute`) when it is popped; a batch is yielded when full, or when the list is empty.
@@ -201,13 +207,18 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
     after draw_warp's (after draw_augment's without warp) and before its key, and the entries gain a last element, that draw.
     elastic: None, or (np_rng, an elastic.Elastic): a kept candidate then makes Elastic.draw(np_rng)'s calls right after draw_warp's
     (after draw_augment's without warp) and before Appearance.draw's and its key, and the entries gain one element ahead of the
-    appearance one: the drawn key (k0, k1), or None for a patch that is not deformed."""
+    appearance one: the drawn key (k0, k1), or None for a patch that is not deformed.
+    artefact: None, or (np_rng, an artefact.Artefact, Cv): a kept candidate then makes Artefact.draw(np_rng, Cv)'s calls right after
+    Appearance.draw's (after whatever precedes those without appearance) and before its key, and the entries gain one element at
+    the very end, that draw -- behind the appearance one."""
     if warp is not None and augment is None:
         raise N3DError("epoch_order: the warp draws follow draw_augment's: warp needs augment")
     if appearance is not None and augment is None:
         raise N3DError("epoch_order: the appearance draws follow draw_augment's: appearance needs augment")
     if elastic is not None and augment is None:
         raise N3DError("epoch_order: the elastic draws follow draw_augment's: elastic needs augment")
+    if artefact is not None and augment is None:
+        raise N3DError("epoch_order: the artefact draws follow draw_augment's: artefact needs augment")
     keep = kept_mask(flags, skip_health).tolist()
     order = list(range(len(keep)))
     if shuffle:
@@ -219,8 +230,9 @@ def epoch_order(flags, batch_size, rng, skip_health=True, shuffle=True, permute=
             aug = (draw_augment(*augment),) if augment is not None else ()      # drawn before the key
             wrp = (draw_warp(*warp),) if warp is not None else ()               # ... and these between the two
             ela = (elastic[1].draw(elastic[0]),) if elastic is not None else ()  # ... then these
-            app = (appearance[1].draw(appearance[0], appearance[2]),) if appearance is not None else ()      # ... and these last
-            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp + ela + app)
+            app = (appearance[1].draw(appearance[0], appearance[2]),) if appearance is not None else ()      # ... then these
+            art = (artefact[1].draw(artefact[0], artefact[2]),) if artefact is not None else ()              # ... and these last
+            batch.append((i, rng.choice(KEYS) if permute else None) + aug + wrp + ela + app + art)
         if len(batch) == batch_size or (not order and batch):
             yield batch
             batch = []
@@ -574,6 +586,13 @@ class Generator:
     kept patch right after draw_warp's and before rng's key draw.  It composes with every option above; left None, the generator
     makes the calls, draws, launches and bits it made without it.
 
+    augment_artefact=artefact.Artefact(...): simulated low resolution, a multiplicative bias field and modality dropout of the
+    gathered data (include/n3d.h, n3d_patch_artefact), applied in place by n3d_patch_artefact after the appearance transforms and
+    before the batch is yielded -- in the trainer's input buffers when the batch went there; the truth is never touched.  Also only
+    with augment=True (else N3DError); batch_size at most 16 (N3D_APPEAR_MAX_BATCH), at most 4 channels, patches of 2 to 256 voxels
+    an edge.  np_rng sees Artefact.draw's calls per kept patch right after Appearance.draw's and before rng's key draw.  It composes
+    with every option above; left None, the generator makes the calls, draws, launches and bits it made without it.
+
     augment_elastic=elastic.Elastic(...): a non-rigid displacement of the crop, added to the coordinate the options above give
     (include/n3d.h, n3d_patch_edesc): a cubic B-spline free-form deformation on a lattice of cells + 3 control points per axis whose
     values the device generates from a key drawn per patch; data and truth move alike.  Also only with augment=True (else N3DError);
@@ -603,7 +622,7 @@ class Generator:
                  shuffle_index_list=True, skip_health=True, inclusive_label=False, both_ps=False, target_dtype=torch.float32, rng=None,
                  augment_flip=True, augment_distortion_factor=0.25, affine=None, np_rng=None, augment_rotation=None,
                  augment_interpolation="nearest", augment_intensity_scale=None, augment_intensity_shift=None, augment_appearance=None,
-                 augment_elastic=None, sampling=None):
+                 augment_artefact=None, augment_elastic=None, sampling=None):
         if labels is not None and list(labels) != LABELS:
             raise N3DError("Generator: labels must be None or [1, 2, 4] (the three BraTS regions the kernels expand)")
         ps = [patch_shape] * 3 if isinstance(patch_shape, int) else [int(p) for p in patch_shape]
@@ -645,6 +664,21 @@ class Generator:
                 raise N3DError("Generator: augment_appearance supports at most %d channels (the set has %d)" % (
                     appearance.MAX_CHANNELS, channels))
         self.augment_appearance = augment_appearance
+        if augment_artefact is not None:
+            if not isinstance(augment_artefact, artefact_mod.Artefact):
+                raise N3DError("Generator: augment_artefact is an artefact.Artefact (got %r)" % (augment_artefact,))
+            if not augment:
+                raise N3DError("Generator: augment_artefact acts only with augment=True")
+            if int(batch_size) > artefact_mod.MAX_BATCH:
+                raise N3DError("Generator: batch_size must be 1..%d with augment_artefact (N3D_APPEAR_MAX_BATCH)" % artefact_mod.MAX_BATCH)
+            if not 2 <= ps[0] <= artefact_mod.MAX_PATCH:
+                raise N3DError("Generator: augment_artefact supports patches of 2..%d voxels an edge (N3D_APPEAR_MAX_PATCH; got %d)" % (
+                    artefact_mod.MAX_PATCH, ps[0]))
+            channels = getattr(volumes, "channels", None)
+            if channels is not None and channels > artefact_mod.MAX_CHANNELS:
+                raise N3DError("Generator: augment_artefact supports at most %d channels (the set has %d)" % (
+                    artefact_mod.MAX_CHANNELS, channels))
+        self.augment_artefact = augment_artefact
         if augment_elastic is not None:
             if not isinstance(augment_elastic, elastic_mod.Elastic):
                 raise N3DError("Generator: augment_elastic is an elastic.Elastic (got %r)" % (augment_elastic,))
@@ -749,7 +783,7 @@ class Generator:
             yield from self._warped_epoch(out, draws)
             return
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
-                                 augment=draws, appearance=self._appearance_draws(), **self._elastic_draws()):
+                                 augment=draws, appearance=self._appearance_draws(), **self._elastic_draws(), **self._artefact_draws()):
             o = out() if callable(out) else out
             B = len(batch)
             refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
@@ -764,6 +798,11 @@ class Generator:
         a = self.augment_appearance
         return (self.np_rng, a, self.volumes.channels) if a is not None else None
 
+    def _artefact_draws(self):
+        """epoch_order's `artefact` argument: absent without the option, so that a stand-in epoch_order sees today's call"""
+        a = self.augment_artefact
+        return {"artefact": (self.np_rng, a, self.volumes.channels)} if a is not None else {}
+
     def _elastic_draws(self):
         """epoch_order's `elastic` argument: absent without the option, so that a stand-in epoch_order sees today's call"""
         return {"elastic": (self.np_rng, self.augment_elastic)} if self.augment_elastic is not None else {}
@@ -775,10 +814,14 @@ class Generator:
         return {"elastic": [self.augment_elastic.entry(e[at]) for e in batch]}
 
     def _appear(self, xt, batch):
-        """the batch's appearance draws (the last element of its entries) applied to the gathered x where it lies -- the trainer's
-        input buffers when the batch went there; the truth is never touched"""
+        """the batch's appearance draws and then its artefact draws applied to the gathered x where it lies -- the trainer's input
+        buffers when the batch went there; the truth is never touched.  The artefact draw is the last element of an entry; the
+        appearance draw is the last one without it and the one before it with it."""
+        art = self.augment_artefact is not None
         if self.augment_appearance is not None:
-            self.augment_appearance.apply(xt[0], [e[-1] for e in batch])
+            self.augment_appearance.apply(xt[0], [e[-2 if art else -1] for e in batch])
+        if art:
+            self.augment_artefact.apply(xt[0], [e[-1] for e in batch])
         return xt
 
     def _warped_epoch(self, out, draws):
@@ -787,7 +830,8 @@ class Generator:
         order = 1 if self.augment_interpolation == "linear" else 0
         wdraws = (self.np_rng, self.augment_rotation, self.augment_intensity_scale, self.augment_intensity_shift, self.volumes.channels)
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
-                                 augment=draws, warp=wdraws, appearance=self._appearance_draws(), **self._elastic_draws()):
+                                 augment=draws, warp=wdraws, appearance=self._appearance_draws(), **self._elastic_draws(),
+                                 **self._artefact_draws()):
             o = out() if callable(out) else out
             B = len(batch)
             refs = [(cand[e[0], 0], cand[e[0], 1:], e[1]) for e in batch]
