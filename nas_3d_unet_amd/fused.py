@@ -577,7 +577,8 @@ def _run_backward_nodes(plan, st, dnodes, alpha1, alpha2, need_x0, need_x1, want
         # C <= 8 (two data-gradient launches per node) with a weight-gradient stream of its own: every data gradient into ONE of
         # the two preprocess gradients -- the one with more writers -- runs on the side stream, behind a flag per node; the chain
         # keeps the gradients into the nodes (and into the other preprocess output) and joins once, in front of the preprocess
-        # backward.  All writers of a buffer stay on one stream, in program order: same accumulation order, same bits.
+        # backward.  All writers of a buffer stay on one stream, in program order: same accumulation order, same bits -- except a node
+        # whose terms do not pair: it writes that preprocess gradient on the chain, behind a join of the side stream's writes (below).
         sb = SIDE_BWD
         side_idx, side_tok = None, None
         if sb is not None and SIDE_PAIRS_BWD and cn <= 8 and getattr(sb, "split", False):
@@ -599,6 +600,12 @@ def _run_backward_nodes(plan, st, dnodes, alpha1, alpha2, need_x0, need_x1, want
             if side_idx is not None and side_idx in (i0, i1):
                 items = P.pair_backward_epilogue(seg0, s0, seg1, s1, dnodes[node], (True, t0, a0), (True, t1, a1))
             if items is None:
+                if side_tok is not None and side_idx in (i0, i1):
+                    # the terms of this node do not pair (a pool, an identity, an SE gate): its gradient into the side stream's preprocess
+                    # buffer is written HERE, on the chain -- behind whatever the side stream has accumulated into that buffer so far.
+                    # (Side work issued later starts behind a fork of the chain, so that direction is ordered already.)
+                    sb.join(side_tok)
+                    side_tok = None
                 (_, g0), (_, g1) = P.pair_backward(seg0, s0, seg1, s1, dnodes[node], (True, t0, a0), (True, t1, a1),
                                                    fold_data=FOLD_SMALL_PAIRS and cn <= 8)
             else:
