@@ -1307,6 +1307,71 @@ int n3d_adabound_step_guarded(float* param, const float* grad, float* exp_avg, f
                               const float* coef, int32_t* step_ptr, int inc_step, const void* timeouts, const void* acked,
                               const float* peer_flag, float* loss, void* host_word, void* stream);
 
+/* ---- flat SGD (torch.optim.SGD, maximize=False) and AdamW (torch.optim.AdamW, amsgrad=False) -------------------------
+ * The same flat buffers, step counter (inc_step 0 / 1 / 2), device learning rate, guard and clip coefficient as the Adam entry
+ * points.  momentum, dampening, weight_decay, betas and eps are doubles -- torch's Python floats --, each rounded to fp32 once;
+ * 1 - dampening and 1 - beta are taken in double before that rounding.  No floating-point atomics.
+ * n3d_sgd_step, per element in fp32, with t = *step_ptr + 1 and lr the device rate:
+ *   1. g' = coef * grad_scale * g          (coef, when given, is folded into grad_scale once per launch)
+ *   2. weight_decay != 0:  g' = g' + wd * p
+ *   3. momentum != 0:  buf = g' when t == 1 (torch clones the first gradient, whatever the dampening),
+ *                      otherwise buf = momentum * buf + (1 - dampening) * g'
+ *   4. nesterov: g' = g' + momentum * buf;  otherwise (momentum != 0) g' = buf
+ *   5. p = p - lr * g'
+ * buf is the momentum buffer (NULL allowed when momentum == 0; then nothing but p is written).  nesterov needs momentum > 0 and
+ * dampening == 0, momentum and weight_decay must not be negative (N3D_ERR_INVALID).  Traffic per element: 12 B in + 8 B out.
+ * n3d_adamw_step, per element in fp32:
+ *   1. p = p * (1 - lr * wd)               (the factor is formed in fp64 once per launch and rounded to fp32 once)
+ *   2. g' = coef * grad_scale * g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2
+ *   3. p = p - (lr / (1 - b1^t)) * (m / (sqrt(v) / sqrt(1 - b2^t) + eps))       (n3d_adam_step's order; no coupled decay term)
+ * Traffic per element: 16 B in + 12 B out. */
+int n3d_sgd_step(float* param, const float* grad, float* buf, int64_t n, float lr, const float* lr_ptr, double momentum,
+                 double dampening, double weight_decay, int nesterov, float grad_scale, const float* coef, int32_t* step_ptr,
+                 int inc_step, void* stream);
+int n3d_sgd_step_guarded(float* param, const float* grad, float* buf, int64_t n, float lr, const float* lr_ptr, double momentum,
+                         double dampening, double weight_decay, int nesterov, float grad_scale, const float* coef,
+                         int32_t* step_ptr, int inc_step, const void* timeouts, const void* acked, const float* peer_flag,
+                         float* loss, void* host_word, void* stream);
+int n3d_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_ptr,
+                   double beta1, double beta2, double eps, double weight_decay, float grad_scale, const float* coef,
+                   int32_t* step_ptr, int inc_step, void* stream);
+int n3d_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                           const float* lr_ptr, double beta1, double beta2, double eps, double weight_decay, float grad_scale,
+                           const float* coef, int32_t* step_ptr, int inc_step, const void* timeouts, const void* acked,
+                           const float* peer_flag, float* loss, void* host_word, void* stream);
+
+/* ---- learning-rate schedule on the device: linear warm-up, then polynomial or cosine decay -------------------------
+ * One lane, fp64, issued on the step's stream anywhere in front of the optimiser launch that reads *lr_out as its lr_ptr: a
+ * captured step follows a per-step schedule with no host call.  s = *step_ptr is the number of updates applied so far (a
+ * withheld update does not advance it).  rec: N3D_LR_REC_LEN device doubles, 8-byte aligned,
+ *   rec[0] kind (N3D_LR_POLY / N3D_LR_COSINE), rec[1] base_lr, rec[2] min_lr, rec[3] warmup_steps W, rec[4] warmup_start a,
+ *   rec[5] total_steps T (> W), rec[6] power (poly only)
+ *   s < W:      lr = base * (a + (1 - a) * s / W)
+ *   otherwise:  u = min(s - W, T - W), n = T - W
+ *     poly:     lr = max(min_lr, base * (1 - u / n)^power)
+ *     cosine:   lr = min_lr + (base - min_lr) * (1 + cos(pi * u / n)) / 2        (u == n: the cosine is taken as -1)
+ *   *lr_out = (float)lr
+ * The closed forms of torch's SequentialLR([LinearLR(start_factor=a, total_iters=W), PolynomialLR | CosineAnnealingLR]) up to
+ * s = T; past T the rate stays at its end value.  A new base rate is one 8-byte write to rec[1] between launches. */
+#define N3D_LR_REC_LEN 7
+#define N3D_LR_POLY 0
+#define N3D_LR_COSINE 1
+int n3d_lr_schedule(const int32_t* step_ptr, const double* rec, float* lr_out, void* stream);
+
+/* ---- exponential moving average of the weights, and the exchange of two flat buffers ----------------------------------
+ * n3d_ema_step is torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)).update_parameters over one flat
+ * buffer, issued behind an optimiser launch.  state: N3D_EMA_STATE_WORDS device int32 {n_averaged, last_step, ticket}, the ticket
+ * zero between launches, last_step the value *step_ptr had when the average last moved (at the start: when it was set up).
+ *   *step_ptr == last_step: the optimiser launch in front was withheld -> nothing is touched
+ *   n_averaged == 0:        ema = p
+ *   otherwise:              ema = ema + w * (p - ema),  w = (float)(1.0 - decay)       (lerp's weight < 0.5 branch: 0.5 < decay < 1)
+ *   then n_averaged += 1, last_step = *step_ptr   (every workgroup reads state before it draws its ticket; the last ticket writes)
+ * n3d_swap_f32 exchanges the contents of two flat buffers that do not overlap.  Both use the float4 layout of the update kernels,
+ * with an element-wise tail and an element-wise path for buffers off a 16-byte boundary. */
+#define N3D_EMA_STATE_WORDS 3
+int n3d_ema_step(float* ema, const float* param, int64_t n, double decay, const int32_t* step_ptr, int32_t* state, void* stream);
+int n3d_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* ---- global gradient norm and clip coefficient (config.yml:49 grad_clip; train.py:126-127, search.py:236-237) --------
  * torch.nn.utils.clip_grad_norm_(params, max_norm) with norm_type 2 and error_if_nonfinite=False over ONE flat buffer, in one
  * launch and without a host sync:  out[0] = || grad_scale * grad ||_2 (fp64 sums, rounded to fp32 once),

@@ -313,6 +313,13 @@ PROTOTYPES = {
     "n3d_adabound_step": (_i, [_p, _p, _p, _p, _p, _i64, _f, _p, _f, _d, _d, _d, _d, _d, _d, _i, _f, _p, _p, _i, _p]),
     "n3d_adabound_step_guarded": (_i, [_p, _p, _p, _p, _p, _i64, _f, _p, _f, _d, _d, _d, _d, _d, _d, _i, _f, _p, _p, _i,
                                        _p, _p, _p, _p, _p, _p]),
+    "n3d_sgd_step": (_i, [_p, _p, _p, _i64, _f, _p, _d, _d, _d, _i, _f, _p, _p, _i, _p]),
+    "n3d_sgd_step_guarded": (_i, [_p, _p, _p, _i64, _f, _p, _d, _d, _d, _i, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "n3d_adamw_step": (_i, [_p, _p, _p, _p, _i64, _f, _p, _d, _d, _d, _d, _f, _p, _p, _i, _p]),
+    "n3d_adamw_step_guarded": (_i, [_p, _p, _p, _p, _i64, _f, _p, _d, _d, _d, _d, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "n3d_lr_schedule": (_i, [_p, _p, _p, _p]),
+    "n3d_ema_step": (_i, [_p, _p, _i64, _d, _p, _p, _p]),
+    "n3d_swap_f32": (_i, [_p, _p, _i64, _p]),
     "n3d_grad_clip_scratch_bytes": (_sz, []),
     "n3d_grad_clip_coef": (_i, [_p, _i64, _f, _d, _p, _p, _p]),
     "n3d_host_word_alloc": (_i, [C.POINTER(C.c_void_p)]),

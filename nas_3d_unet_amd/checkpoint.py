@@ -8,7 +8,10 @@ What does need one is the optimizer: the trainers keep Adam's moments in flat bu
 Adam keeps per-parameter tensors -- `adam_state_dict` / `load_adam_state_dict` translate both ways, and the plateau
 schedulers export / import torch's ReduceLROnPlateau field names.  A trainer built with optimizer="adabound" / "adaboundw" writes the
 state_dict() layout of the reference's adabound.py classes instead (`adabound_state_dict`) and records its optimiser's name under
-"optimizer" ("optimizer_kernel" in a search checkpoint); loading state another optimiser wrote raises ValueError.
+"optimizer" ("optimizer_kernel" in a search checkpoint); loading state another optimiser wrote raises ValueError.  A trainer built
+with optimizer=train.SGD(...) / train.AdamW(...) writes torch.optim.SGD's / AdamW's own state_dict() layout and records its name
+the same way; with ema= the dictionary gains "ema" (n_averaged and the averaged parameters in model_param's layout), with schedule=
+the "scheduler" entry holds the schedule's fields.  Files of trainers built without these arguments are key for key what they were.
 """
 from __future__ import annotations
 
@@ -142,16 +145,82 @@ def load_adabound_state_dict(fp, optim, sd, twin=None, real=None):
     return float(group["lr"])
 
 
+# ------------------------------------------------------------------------------------------------ SGD / AdamW
+def _plain(x):
+    """torch writes 0 for a default it was given as the int 0"""
+    return int(x) if x == 0 else x
+
+
+def sgd_state_dict(fp, optim, lr, twin=None, real=None):
+    """torch.optim.SGD(params).state_dict() for a train.FlatParams under a train.SGD spec: per parameter `momentum_buffer` (the
+    flat exp_avg; no state before the first step or without momentum), group keys lr, momentum, dampening, weight_decay, nesterov
+    and torch's flags.  torch's SGD counts no steps; the trainer's counter travels next to the optimiser's name (_record_optimizer)."""
+    step = int(fp.step.item())
+    state = {}
+    ents = _entries(fp, twin, real)
+    if step > 0 and optim.momentum != 0:
+        for i, (o, shape, name) in enumerate(ents):
+            n = int(torch.Size(shape).numel())
+            b = fp.exp_avg[o:o + n].view(shape)
+            state[i] = {"momentum_buffer": (twin.extract(name, b) if name is not None else b).clone()}
+    group = {"lr": lr, "momentum": _plain(optim.momentum), "dampening": _plain(optim.dampening), "weight_decay": _plain(optim.weight_decay),
+             "nesterov": optim.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None,
+             "params": list(range(len(ents)))}
+    return {"state": state, "param_groups": [group]}
+
+
+def load_sgd_state_dict(fp, optim, sd, step=None, twin=None, real=None):
+    """inverse of sgd_state_dict; returns the learning rate stored in the checkpoint.  step: the update count recorded next to the
+    state; a file torch's own SGD wrote has none: 1 when it holds momentum buffers (all the kernel asks is whether a first step was
+    taken), else 0.  momentum, dampening, weight_decay and nesterov stay the trainer's."""
+    group = sd["param_groups"][0]
+    if "momentum" not in group or "betas" in group:
+        raise ValueError("checkpoint's optimizer state is not SGD's (param group keys: %s)" % sorted(group))
+    fp.exp_avg.zero_()
+    have = False
+    for i, (o, shape, name) in enumerate(_entries(fp, twin, real)):
+        b = sd["state"].get(i, {}).get("momentum_buffer")
+        if b is None:
+            continue
+        have = True
+        n = int(torch.Size(shape).numel())
+        b = b.to(fp.exp_avg.device)
+        if name is not None:
+            b = twin.embed_tensor(name, b, shape)
+        fp.exp_avg[o:o + n].copy_(b.reshape(-1))
+    fp.step.fill_(int(step) if step is not None else (1 if have else 0))
+    return float(group["lr"])
+
+
+def adamw_state_dict(fp, optim, lr, twin=None, real=None):
+    """torch.optim.AdamW(params).state_dict() for a train.FlatParams under a train.AdamW spec: Adam's per-parameter layout (step,
+    exp_avg, exp_avg_sq), the group with the spec's weight_decay and decoupled_weight_decay = True"""
+    sd = adam_state_dict(fp, lr, optim.betas, optim.eps, twin, real)
+    sd["param_groups"][0].update(weight_decay=_plain(optim.weight_decay), decoupled_weight_decay=True)
+    return sd
+
+
+def load_adamw_state_dict(fp, optim, sd, twin=None, real=None):
+    group = sd["param_groups"][0]
+    if "betas" not in group or "final_lr" in group:
+        raise ValueError("checkpoint's optimizer state is not AdamW's (param group keys: %s)" % sorted(group))
+    return load_adam_state_dict(fp, sd, twin, real)
+
+
 def _optim_state_dict(trainer, fp, lr, twin, real):
     optim = _optim_of(trainer)
     if optim is None or optim.name == "adam":
         return adam_state_dict(fp, lr, trainer.betas, trainer.eps, twin, real)
+    if optim.name == "sgd":
+        return sgd_state_dict(fp, optim, lr, twin, real)
+    if optim.name == "adamw":
+        return adamw_state_dict(fp, optim, lr, twin, real)
     return adabound_state_dict(fp, optim, lr, twin, real)
 
 
-def _load_optim_state_dict(trainer, fp, sd, written_by, twin, real):
+def _load_optim_state_dict(trainer, fp, sd, written_by, twin, real, step=None):
     """written_by: the optimiser name the checkpoint records (files from before the record, and the reference's own Adam
-    checkpoints, carry none: "adam")"""
+    checkpoints, carry none: "adam"); step: the update count an SGD checkpoint records next to the name"""
     optim = _optim_of(trainer)
     mine = "adam" if optim is None else optim.name
     if written_by != mine:
@@ -159,6 +228,10 @@ def _load_optim_state_dict(trainer, fp, sd, written_by, twin, real):
                          "(or load with new_lr=True to take the weights only)" % (written_by, mine, written_by))
     if mine == "adam":
         return load_adam_state_dict(fp, sd, twin, real)
+    if mine == "sgd":
+        return load_sgd_state_dict(fp, optim, sd, step, twin, real)
+    if mine == "adamw":
+        return load_adamw_state_dict(fp, optim, sd, twin, real)
     return load_adabound_state_dict(fp, optim, sd, twin, real)
 
 
@@ -198,18 +271,87 @@ def _twin_of(trainer, real):
 
 def _record_optimizer(sd, key, trainer):
     """which optimiser wrote the kernel weights' state: AdaBound and AdaBoundW share one layout, so the name goes next to it.  An Adam
-    checkpoint stays key for key the reference's (train.py:85-93; search.py:166-176) and carries no record"""
+    checkpoint stays key for key the reference's (train.py:85-93; search.py:166-176) and carries no record.  SGD's state counts no
+    steps (torch's does not), so the trainer's update count goes next to the name, under key + "_step"."""
     optim = _optim_of(trainer)
     if optim is not None and optim.name != "adam":
         sd[key] = optim.name
+        if optim.name == "sgd":
+            sd[key + "_step"] = int(trainer.fp.step.item())
     return sd
+
+
+# ------------------------------------------------------------------------------------------------ device schedule / averaged weights
+def _trainer_scheduler_state_dict(trainer):
+    """the plateau scheduler's fields, or -- a trainer built with schedule= has none -- the schedule's own as a plain dict"""
+    sched = getattr(trainer, "schedule", None)
+    return scheduler_state_dict(trainer.scheduler) if sched is None else sched.state_dict()
+
+
+def _check_scheduler_kind(trainer, d):
+    """a checkpoint of another schedule kind (a plateau file into a PolyLR trainer, a cosine file into a plateau trainer ..) raises,
+    before anything of the optimiser's state is touched"""
+    sched = getattr(trainer, "schedule", None)
+    mine, theirs = ("plateau" if sched is None else sched.name), d.get("kind", "plateau")
+    if mine != theirs:
+        raise ValueError("checkpoint's scheduler state is of kind %r, this trainer runs %r (load with new_lr=True to take the weights only)"
+                         % (theirs, mine))
+
+
+def _load_trainer_scheduler(trainer, d):
+    """the plateau scheduler's fields; a device schedule has no state beyond its constructor arguments and the step counter"""
+    if getattr(trainer, "schedule", None) is None:
+        load_scheduler_state_dict(trainer.scheduler, d)
+
+
+def _flat_views(trainer, buf):
+    """{parameter name: the part of `buf` (a flat buffer laid out like trainer.fp.flat) that belongs to it, in the module's shape}"""
+    fp = trainer.fp
+    tw, _ = _twin_of(trainer, trainer.model)
+    off = {id(p): (o, p.shape) for p, o in zip(fp.params, fp.offsets)}
+    src = dict((tw.twin if tw is not None else trainer.model).named_parameters())
+    out = {}
+    for n, _ in trainer.model.named_parameters():
+        q = src.get(n)
+        if q is not None and id(q) in off:
+            o, shape = off[id(q)]
+            v = buf[o:o + int(torch.Size(shape).numel())].view(shape)
+            out[n] = (tw.extract(n, v) if tw is not None else v, o, shape)
+    return out
+
+
+def ema_state_dict(trainer):
+    """{"n_averaged", "params"}: the averaged weights in model_param's layout (the module's state_dict() with every trained
+    parameter replaced by its average), loadable into a module of the same net"""
+    params = {k: v.clone() for k, v in trainer.model.state_dict().items()}
+    for n, (v, _, _) in _flat_views(trainer, trainer.fp.ema).items():
+        params[n] = v.clone()
+    return {"n_averaged": int(trainer.fp.ema_state[0].item()), "params": params}
+
+
+def load_ema_state_dict(trainer, d):
+    """inverse of ema_state_dict; d None (a checkpoint without averaged weights): averaging starts over at the next update"""
+    fp = trainer.fp
+    tw, _ = _twin_of(trainer, trainer.model)
+    fp.ema.zero_()
+    n_averaged = 0
+    if d is not None:
+        n_averaged = int(d["n_averaged"])
+        for n, (_, o, shape) in _flat_views(trainer, fp.ema).items():
+            t = d["params"][n].to(fp.ema.device)
+            if tw is not None:
+                t = tw.embed_tensor(n, t, shape)
+            fp.ema[o:o + t.numel()].copy_(t.reshape(-1))
+    fp.ema_state.copy_(torch.tensor([n_averaged, int(fp.step.item()), 0], dtype=torch.int32))
 
 
 def train_state_dicts(trainer, epoch, history, best_loss):
     _checked(trainer)
     sd = {"epoch": epoch, "history": history, "model_param": trainer.model.state_dict(),
           "optim": _optim_state_dict(trainer, trainer.fp, trainer.lr, *_twin_of(trainer, trainer.model)),
-          "scheduler": scheduler_state_dict(trainer.scheduler), "best_loss": best_loss}
+          "scheduler": _trainer_scheduler_state_dict(trainer), "best_loss": best_loss}
+    if getattr(trainer, "ema", None) is not None:
+        sd["ema"] = ema_state_dict(trainer)
     return _record_optimizer(sd, "optimizer", trainer)
 
 
@@ -218,8 +360,12 @@ def load_train_state_dicts(trainer, sd, new_lr=False):
     trainer.model.load_state_dict(sd["model_param"])   # parameters are views of the flat buffer: copied in place
     getattr(trainer, "sync_from_module", lambda: None)()   # (a padded twin re-embeds the loaded parameters)
     if not new_lr:
-        trainer.set_lr(_load_optim_state_dict(trainer, trainer.fp, sd["optim"], sd.get("optimizer", "adam"), *_twin_of(trainer, trainer.model)))
-        load_scheduler_state_dict(trainer.scheduler, sd["scheduler"])
+        _check_scheduler_kind(trainer, sd["scheduler"])
+        trainer.set_lr(_load_optim_state_dict(trainer, trainer.fp, sd["optim"], sd.get("optimizer", "adam"), *_twin_of(trainer, trainer.model),
+                                              step=sd.get("optimizer_step")))
+        _load_trainer_scheduler(trainer, sd["scheduler"])
+    if getattr(trainer, "ema", None) is not None:
+        load_ema_state_dict(trainer, sd.get("ema"))
     return sd["epoch"] + 1, sd["history"], sd["best_loss"]
 
 
@@ -243,7 +389,7 @@ def load_search_state_dicts(trainer, sd, new_lr=False):
     if not new_lr:
         trainer.set_shell_lr(load_adam_state_dict(trainer.afp, sd["optim_shell"]))
         trainer.set_kernel_lr(_load_optim_state_dict(trainer, trainer.fp, sd["optim_kernel"], sd.get("optimizer_kernel", "adam"),
-                                                     *_twin_of(trainer, trainer.model.kernel)))
+                                                     *_twin_of(trainer, trainer.model.kernel), step=sd.get("optimizer_kernel_step")))
         load_scheduler_state_dict(trainer.shell_scheduler, sd["shell_scheduler"])
         load_scheduler_state_dict(trainer.kernel_scheduler, sd["kernel_scheduler"])
     return sd["epoch"] + 1, sd["geno_count"], sd["history"], sd["best_loss"]

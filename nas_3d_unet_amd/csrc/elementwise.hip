@@ -2470,6 +2470,244 @@ __global__ __launch_bounds__(256) void adabound_kernel(float* __restrict__ p, co
 }
 
 // ------------------------------------------------------------------------------------------------
+// SGD (torch.optim.SGD, maximize=False) and AdamW (torch.optim.AdamW, amsgrad=False), flat like Adam above: the same guard, the
+// same ticketed step count, the same float4 path (two loads in flight per array) with an element-wise tail and an element-wise
+// path for views off a 16-byte boundary.  The guard preamble and the ticket are adam_kernel's, stated once for the kernels here.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool update_withheld(const AdamGuard& gd) {
+  bool skip = false;
+  if (gd.timeouts) skip = __hip_atomic_load(gd.timeouts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != *gd.acked;
+  if (gd.peer_flag) skip = skip || (*gd.peer_flag != 0.f);
+  if (skip && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (gd.loss) *gd.loss = __builtin_nanf("");
+    if (gd.host_word) __hip_atomic_store(gd.host_word, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  return skip;
+}
+// every workgroup has read the step before it draws its ticket: the one that draws the last may count the step and clear the counter
+__device__ __forceinline__ void count_step_ticketed(int32_t* step_ptr, int step) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(step_ptr + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk == gridDim.x - 1) {
+      __hip_atomic_store(reinterpret_cast<unsigned*>(step_ptr + 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(step_ptr, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+__device__ __forceinline__ bool aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+struct SgdArgs {
+  double momentum, dampening, wd;            // torch's Python floats: rounded to fp32 once each, 1 - dampening taken in double first
+  float lr_imm, gscale;
+  int nesterov;
+};
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                                  const float* __restrict__ lr_ptr, SgdArgs a, const float* __restrict__ coef,
+                                                  int32_t* __restrict__ step_ptr, int ticketed, AdamGuard gd) {
+  if (update_withheld(gd)) return;
+  const int step = *step_ptr + 1;
+  const float lr = lr_ptr ? *lr_ptr : a.lr_imm;
+  const float mom = (float)a.momentum, omd = (float)(1.0 - a.dampening), wd = (float)a.wd;
+  const float gs = coef ? a.gscale * *coef : a.gscale;
+  const bool first = step == 1, nesterov = a.nesterov != 0;
+  auto upd = [&](float& pi, float gi, float& bi) {
+    gi *= gs;
+    if (wd != 0.f) gi = fmaf(wd, pi, gi);
+    if (MOM) {
+      bi = first ? gi : fmaf(mom, bi, omd * gi);     // (torch clones the first gradient, whatever the dampening)
+      gi = nesterov ? fmaf(mom, bi, gi) : bi;
+    }
+    pi = fmaf(-lr, gi, pi);       // (stated as fma: the float4 path and the element-wise paths round alike)
+  };
+  constexpr int U = 2;
+  const int64_t n4 = aligned16(p, g, MOM ? buf : nullptr) ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 p4[U], g4[U], b4[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      const int64_t ic = i < n4 ? i : i0;
+      p4[u] = reinterpret_cast<const float4*>(p)[ic]; g4[u] = reinterpret_cast<const float4*>(g)[ic];
+      b4[u] = MOM ? reinterpret_cast<const float4*>(buf)[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < n4) {
+        upd(p4[u].x, g4[u].x, b4[u].x); upd(p4[u].y, g4[u].y, b4[u].y); upd(p4[u].z, g4[u].z, b4[u].z); upd(p4[u].w, g4[u].w, b4[u].w);
+        if (MOM) reinterpret_cast<float4*>(buf)[i] = b4[u];
+        reinterpret_cast<float4*>(p)[i] = p4[u];
+      }
+    }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], bi = MOM ? buf[i] : 0.f;
+    upd(pi, g[i], bi);
+    if (MOM) buf[i] = bi;
+    p[i] = pi;
+  }
+  if (ticketed) count_step_ticketed(step_ptr, step);
+}
+
+struct AdamWArgs {
+  double b1, b2, eps, wd;                    // torch's Python floats: rounded to fp32 once each, 1 - beta taken in double first
+  float lr_imm, gscale;
+};
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                    int64_t n, const float* __restrict__ lr_ptr, AdamWArgs a, const float* __restrict__ coef,
+                                                    int32_t* __restrict__ step_ptr, int ticketed, AdamGuard gd) {
+  if (update_withheld(gd)) return;
+  const int step = *step_ptr + 1;
+  const double lr = (double)(lr_ptr ? *lr_ptr : a.lr_imm);
+  const double bc1 = 1.0 - pow(a.b1, (double)step);
+  const double bc2 = 1.0 - pow(a.b2, (double)step);
+  const float step_size = (float)(lr / bc1);
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const float keep = (float)(1.0 - lr * a.wd);        // param.mul_(1 - lr * weight_decay): formed in fp64, rounded once
+  const float b1 = (float)a.b1, b2 = (float)a.b2, omb1 = (float)(1.0 - a.b1), omb2 = (float)(1.0 - a.b2), eps = (float)a.eps;
+  const float gs = coef ? a.gscale * *coef : a.gscale;
+  auto upd = [&](float& pi, float gi, float& mi, float& vi) {
+    gi *= gs;
+    pi = pi * keep;
+    mi = fmaf(b1, mi, omb1 * gi);
+    vi = fmaf(b2, vi, omb2 * gi * gi);
+    const float denom = fmaf(sqrtf(vi), inv_sqrt_bc2, eps);
+    pi = fmaf(-step_size, mi / denom, pi);
+  };
+  constexpr int U = 2;
+  const int64_t n4 = aligned16(p, g, m, v) ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 p4[U], g4[U], m4[U], v4[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      const int64_t ic = i < n4 ? i : i0;
+      p4[u] = reinterpret_cast<const float4*>(p)[ic]; g4[u] = reinterpret_cast<const float4*>(g)[ic];
+      m4[u] = reinterpret_cast<const float4*>(m)[ic]; v4[u] = reinterpret_cast<const float4*>(v)[ic];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < n4) {
+        upd(p4[u].x, g4[u].x, m4[u].x, v4[u].x); upd(p4[u].y, g4[u].y, m4[u].y, v4[u].y);
+        upd(p4[u].z, g4[u].z, m4[u].z, v4[u].z); upd(p4[u].w, g4[u].w, m4[u].w, v4[u].w);
+        reinterpret_cast<float4*>(m)[i] = m4[u]; reinterpret_cast<float4*>(v)[i] = v4[u]; reinterpret_cast<float4*>(p)[i] = p4[u];
+      }
+    }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    upd(pi, g[i], mi, vi);
+    m[i] = mi; v[i] = vi; p[i] = pi;
+  }
+  if (ticketed) count_step_ticketed(step_ptr, step);
+}
+
+// ------------------------------------------------------------------------------------------------
+// learning-rate schedule on the device (include/n3d.h, n3d_lr_schedule): one lane, fp64, in front of the optimiser launch
+// ------------------------------------------------------------------------------------------------
+__global__ void lr_schedule_kernel(const int32_t* __restrict__ step_ptr, const double* __restrict__ rec, float* __restrict__ lr_out) {
+  const double s = (double)*step_ptr;
+  const int kind = (int)rec[0];
+  const double base = rec[1], min_lr = rec[2], W = rec[3], a = rec[4], T = rec[5], power = rec[6];
+  double lr;
+  if (s < W) {
+    lr = base * (a + (1.0 - a) * s / W);
+  } else {
+    const double nn = T - W;
+    const double u = fmin(s - W, nn);
+    if (kind == N3D_LR_POLY) {
+      lr = base * pow(1.0 - u / nn, power);
+      lr = lr < min_lr ? min_lr : lr;
+    } else {
+      const double c = u < nn ? cos(3.14159265358979323846 * u / nn) : -1.0;   // (cos(pi) is -1: the end value is min_lr exactly)
+      lr = min_lr + (base - min_lr) * (1.0 + c) / 2.0;
+    }
+  }
+  *lr_out = (float)lr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exponential moving average of the weights (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay)) behind an
+// optimiser launch, and the exchange of two flat buffers.  The float4 layout and tails of the update kernels; no guard: the EMA
+// launch sees a withheld update by the step counter that did not move.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, float w,
+                                                  const int32_t* __restrict__ step_ptr, int32_t* __restrict__ state) {
+  // state = {n_averaged, last_step, ticket}: every workgroup reads it before it draws its ticket, the last ticket writes it
+  const int step = __hip_atomic_load(step_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int n_avg = __hip_atomic_load(state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int last = __hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (step == last) return;          // the optimiser launch in front was withheld: nothing is touched
+  const bool copy = n_avg == 0;
+  auto upd = [&](float& ei, float pi) { ei = copy ? pi : fmaf(w, pi - ei, ei); };
+  constexpr int U = 2;
+  const int64_t n4 = aligned16(ema, p) ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 e4[U], p4[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      const int64_t ic = i < n4 ? i : i0;
+      e4[u] = reinterpret_cast<const float4*>(ema)[ic]; p4[u] = reinterpret_cast<const float4*>(p)[ic];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < n4) {
+        upd(e4[u].x, p4[u].x); upd(e4[u].y, p4[u].y); upd(e4[u].z, p4[u].z); upd(e4[u].w, p4[u].w);
+        reinterpret_cast<float4*>(ema)[i] = e4[u];
+      }
+    }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float ei = ema[i];
+    upd(ei, p[i]);
+    ema[i] = ei;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned tk = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(state + 2), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk == gridDim.x - 1) {
+      __hip_atomic_store(reinterpret_cast<unsigned*>(state + 2), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(state, n_avg + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(state + 1, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+  constexpr int U = 2;
+  const int64_t n4 = aligned16(a, b) ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 a4[U], b4[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      const int64_t ic = i < n4 ? i : i0;
+      a4[u] = reinterpret_cast<const float4*>(a)[ic]; b4[u] = reinterpret_cast<const float4*>(b)[ic];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < n4) { reinterpret_cast<float4*>(a)[i] = b4[u]; reinterpret_cast<float4*>(b)[i] = a4[u]; }
+    }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float x = a[i];
+    a[i] = b[i];
+    b[i] = x;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // global gradient norm -> clip coefficient (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite=False), one launch.
 // The grid depends on n alone and every workgroup adds a fixed set of elements in a fixed order (lane-strided fp64 sums, then a
 // fixed tree over the 256 lanes), so partial b is the same on every launch; the workgroup that draws the last ticket adds the
@@ -3400,6 +3638,82 @@ int n3d_adabound_step_guarded(float* param, const float* grad, float* exp_avg, f
     N3D_LAUNCH(adabound_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq,
                n, lr_ptr, a, coef, step_ptr, inc_step == 2 ? 1 : 0, gd);
   if (inc_step == 1) N3D_LAUNCH(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+static unsigned flat_blocks(int64_t n) {      // as n3d_adam_step_coef: 8192 elements per workgroup, at most 2048 workgroups
+  int64_t blocks = cdiv(n, 8192);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
+int n3d_sgd_step(float* param, const float* grad, float* buf, int64_t n, float lr, const float* lr_ptr, double momentum, double dampening,
+                 double weight_decay, int nesterov, float grad_scale, const float* coef, int32_t* step_ptr, int inc_step, void* stream) {
+  return n3d_sgd_step_guarded(param, grad, buf, n, lr, lr_ptr, momentum, dampening, weight_decay, nesterov, grad_scale, coef, step_ptr, inc_step,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
+int n3d_sgd_step_guarded(float* param, const float* grad, float* buf, int64_t n, float lr, const float* lr_ptr, double momentum, double dampening,
+                         double weight_decay, int nesterov, float grad_scale, const float* coef, int32_t* step_ptr, int inc_step,
+                         const void* timeouts, const void* acked, const float* peer_flag, float* loss, void* host_word, void* stream) {
+  N3D_CHECK_ARG(param && grad && step_ptr && n > 0 && (buf || momentum == 0.0), "sgd_step: bad args (momentum != 0 needs a buffer)");
+  N3D_CHECK_ARG(momentum >= 0.0 && weight_decay >= 0.0 && (!nesterov || (momentum > 0.0 && dampening == 0.0)),
+                "sgd_step: negative momentum or weight decay, or Nesterov without momentum / with dampening");
+  N3D_CHECK_ARG((timeouts == nullptr) == (acked == nullptr), "sgd_step_guarded: timeouts and acked come together");
+  N3D_CHECK_ARG(inc_step != 1 || (!timeouts && !peer_flag), "sgd_step_guarded: a guarded update counts its own step (inc_step 0 or 2)");
+  const AdamGuard gd{(const unsigned*)timeouts, (const unsigned*)acked, peer_flag, loss, (unsigned*)host_word};
+  const SgdArgs a{momentum, dampening, weight_decay, lr, grad_scale, nesterov ? 1 : 0};
+  if (momentum != 0.0)
+    N3D_LAUNCH(sgd_kernel<true>, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, buf, n, lr_ptr, a, coef, step_ptr,
+               inc_step == 2 ? 1 : 0, gd);
+  else
+    N3D_LAUNCH(sgd_kernel<false>, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, buf, n, lr_ptr, a, coef, step_ptr,
+               inc_step == 2 ? 1 : 0, gd);
+  if (inc_step == 1) N3D_LAUNCH(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_ptr, double beta1,
+                   double beta2, double eps, double weight_decay, float grad_scale, const float* coef, int32_t* step_ptr, int inc_step,
+                   void* stream) {
+  return n3d_adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, n, lr, lr_ptr, beta1, beta2, eps, weight_decay, grad_scale, coef, step_ptr,
+                                inc_step, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
+int n3d_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, const float* lr_ptr,
+                           double beta1, double beta2, double eps, double weight_decay, float grad_scale, const float* coef, int32_t* step_ptr,
+                           int inc_step, const void* timeouts, const void* acked, const float* peer_flag, float* loss, void* host_word,
+                           void* stream) {
+  N3D_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step_ptr && n > 0, "adamw_step: bad args");
+  N3D_CHECK_ARG((timeouts == nullptr) == (acked == nullptr), "adamw_step_guarded: timeouts and acked come together");
+  N3D_CHECK_ARG(inc_step != 1 || (!timeouts && !peer_flag), "adamw_step_guarded: a guarded update counts its own step (inc_step 0 or 2)");
+  const AdamGuard gd{(const unsigned*)timeouts, (const unsigned*)acked, peer_flag, loss, (unsigned*)host_word};
+  const AdamWArgs a{beta1, beta2, eps, weight_decay, lr, grad_scale};
+  N3D_LAUNCH(adamw_kernel, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr_ptr, a, coef,
+             step_ptr, inc_step == 2 ? 1 : 0, gd);
+  if (inc_step == 1) N3D_LAUNCH(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_lr_schedule(const int32_t* step_ptr, const double* rec, float* lr_out, void* stream) {
+  N3D_CHECK_ARG(step_ptr && rec && lr_out && (reinterpret_cast<uintptr_t>(rec) & 7) == 0, "lr_schedule: bad args");
+  N3D_LAUNCH(lr_schedule_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_ptr, rec, lr_out);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_ema_step(float* ema, const float* param, int64_t n, double decay, const int32_t* step_ptr, int32_t* state, void* stream) {
+  N3D_CHECK_ARG(ema && param && ema != param && step_ptr && state && n > 0 && decay > 0.5 && decay < 1.0, "ema_step: bad args (0.5 < decay < 1)");
+  N3D_LAUNCH(ema_kernel, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, ema, param, n, (float)(1.0 - decay), step_ptr, state);
+  N3D_LAUNCH_CHECK();
+  return N3D_OK;
+}
+
+int n3d_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  N3D_CHECK_ARG(a && b && n > 0 && (a + n <= b || b + n <= a), "swap_f32: bad args (the buffers must not overlap)");
+  N3D_LAUNCH(swap_f32_kernel, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, n);
   N3D_LAUNCH_CHECK();
   return N3D_OK;
 }

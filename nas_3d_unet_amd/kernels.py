@@ -1595,6 +1595,62 @@ def adabound_step(param, grad, exp_avg, exp_avg_sq, step_t, lr=1e-3, beta1=0.9, 
         check(_lib.load().n3d_adabound_step_guarded(*args, *_guard_args(guard), stream_ptr()), "n3d_adabound_step_guarded")
 
 
+def sgd_step(param, grad, buf, step_t, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0,
+             inc_step=True, lr_dev=None, guard=None, coef=None):
+    """torch.optim.SGD over flat buffers (include/n3d.h, "flat SGD"); buf: the momentum buffer (None allowed with momentum == 0);
+    step_t, lr_dev, guard, coef as adam_step / adam_step_coef"""
+    inc = 0 if not inc_step else (2 if getattr(step_t, "_n3d_ticketed", False) else 1)
+    args = (ptr(param), ptr(grad), ptr(buf), param.numel(), lr, ptr(lr_dev), momentum, dampening, weight_decay, 1 if nesterov else 0,
+            grad_scale, ptr(coef), ptr(step_t), inc)
+    if guard is None:
+        check(_lib.load().n3d_sgd_step(*args, stream_ptr()), "n3d_sgd_step")
+    else:
+        check(_lib.load().n3d_sgd_step_guarded(*args, *_guard_args(guard), stream_ptr()), "n3d_sgd_step_guarded")
+
+
+def adamw_step(param, grad, exp_avg, exp_avg_sq, step_t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
+               inc_step=True, lr_dev=None, guard=None, coef=None):
+    """torch.optim.AdamW over flat buffers (include/n3d.h, "flat SGD ... and AdamW"); the arguments of adam_step_coef"""
+    inc = 0 if not inc_step else (2 if getattr(step_t, "_n3d_ticketed", False) else 1)
+    args = (ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, ptr(lr_dev), beta1, beta2, eps, weight_decay,
+            grad_scale, ptr(coef), ptr(step_t), inc)
+    if guard is None:
+        check(_lib.load().n3d_adamw_step(*args, stream_ptr()), "n3d_adamw_step")
+    else:
+        check(_lib.load().n3d_adamw_step_guarded(*args, *_guard_args(guard), stream_ptr()), "n3d_adamw_step_guarded")
+
+
+LR_REC_LEN = 7   # N3D_LR_REC_LEN
+LR_POLY, LR_COSINE = 0, 1   # N3D_LR_POLY / N3D_LR_COSINE
+EMA_STATE_WORDS = 3   # N3D_EMA_STATE_WORDS
+
+
+def lr_schedule_record(kind, base_lr, min_lr, warmup_steps, warmup_start, total_steps, power, device):
+    """the device record n3d_lr_schedule reads (float64: kind, base_lr, min_lr, W, a, T, power)"""
+    return torch.tensor([kind, base_lr, min_lr, warmup_steps, warmup_start, total_steps, power], dtype=torch.float64, device=device)
+
+
+def lr_schedule(step_t, rec, lr_out):
+    """*lr_out = the schedule's rate at the *step_t updates applied so far: one launch in front of the optimiser launch that reads
+    lr_out as its lr_dev (include/n3d.h, "learning-rate schedule on the device")"""
+    check(_lib.load().n3d_lr_schedule(ptr(step_t), ptr(rec), ptr(lr_out), stream_ptr()), "n3d_lr_schedule")
+
+
+def ema_state(device, step=0):
+    """{n_averaged, last_step, ticket} of n3d_ema_step: nothing averaged yet, the step counter standing at `step`"""
+    return torch.tensor([0, int(step), 0], dtype=torch.int32, device=device)
+
+
+def ema_step(ema, param, decay, step_t, state):
+    """one update of the averaged weights behind an optimiser launch; skipped on the device when that launch was withheld"""
+    check(_lib.load().n3d_ema_step(ptr(ema), ptr(param), param.numel(), float(decay), ptr(step_t), ptr(state), stream_ptr()), "n3d_ema_step")
+
+
+def swap_f32(a, b):
+    """exchange the contents of two flat fp32 buffers in place, one launch"""
+    check(_lib.load().n3d_swap_f32(ptr(a), ptr(b), a.numel(), stream_ptr()), "n3d_swap_f32")
+
+
 def grad_clip_scratch(device):
     """zeroed scratch of one grad_clip_coef call site (ticket word + fp64 partial sums)"""
     return torch.zeros(int(_lib.load().n3d_grad_clip_scratch_bytes()) // 8, dtype=torch.float64, device=device)

@@ -97,6 +97,15 @@ class FlatParams:
         K.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step, lr, betas[0], betas[1], eps,
                     weight_decay, grad_scale, True, lr_dev, guard)
 
+    ema = None          # averaged weights (flat fp32) and their n3d_ema_step state: ensure_ema
+    ema_state = None
+
+    def ensure_ema(self):
+        """the averaged copy of the weights (train.EMA): allocated only for a trainer that asks for it"""
+        if self.ema is None:
+            self.ema = torch.zeros_like(self.flat)
+            self.ema_state = K.ema_state(self.flat.device, int(self.step.item()))
+
     def ensure_amsbound(self):
         """the AMSBound buffer (adabound.py:79-81, max_exp_avg_sq): allocated only for an optimiser that asks for it"""
         if self.max_exp_avg_sq is None:
@@ -105,7 +114,13 @@ class FlatParams:
     def update(self, optim, lr, grad_scale=1.0, lr_dev=None, guard=None, coef=None):
         """one step of `optim` (an OptimSpec) on the flat buffers; coef: 1-element device tensor holding the clip coefficient
         (K.grad_clip_coef), None = no clipping.  Adam without a coefficient is `adam()`, launch for launch."""
+        if optim.name == "sgd":       # (the momentum buffer is exp_avg: torch's momentum_buffer)
+            return K.sgd_step(self.flat, self.grad, self.exp_avg if optim.momentum != 0 else None, self.step, lr, optim.momentum,
+                              optim.dampening, optim.weight_decay, optim.nesterov, grad_scale, True, lr_dev, guard, coef)
         b1, b2 = optim.betas
+        if optim.name == "adamw":
+            return K.adamw_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step, lr, b1, b2, optim.eps, optim.weight_decay,
+                                grad_scale, True, lr_dev, guard, coef)
         if optim.name == "adam":
             if coef is None:
                 return self.adam(lr, optim.betas, optim.eps, optim.weight_decay, grad_scale, lr_dev, guard)
@@ -153,6 +168,111 @@ class OptimSpec:
         self.final_lr, self.gamma = float(args["final_lr"]), float(args["gamma"])
         self.weight_decay, self.amsbound = float(args["weight_decay"]), bool(args["amsbound"])
         self.base_lr = float(torch.tensor(float(lr), dtype=torch.float32))
+
+
+class SGD:
+    """`optimizer=SGD(momentum=0.99, nesterov=True, weight_decay=3e-5)`: torch.optim.SGD (maximize=False) on the flat buffers, one
+    guarded launch (n3d_sgd_step).  Validation as torch's class; the learning rate is the trainer's `lr`."""
+
+    name = "sgd"
+    amsbound = False
+
+    def __init__(self, momentum=0.0, nesterov=False, dampening=0.0, weight_decay=0.0):
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: {}".format(momentum))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.momentum, self.dampening, self.weight_decay, self.nesterov = float(momentum), float(dampening), float(weight_decay), bool(nesterov)
+
+    def bound(self, lr):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        return self
+
+
+class AdamW:
+    """`optimizer=AdamW(betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)`: torch.optim.AdamW (amsgrad=False) on the flat buffers,
+    one guarded launch (n3d_adamw_step).  Validation as torch's class; the learning rate is the trainer's `lr`."""
+
+    name = "adamw"
+    amsbound = False
+
+    def __init__(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+
+    bound = SGD.bound
+
+
+def _optim_spec(optimizer, lr, betas, eps, optim_args):
+    """a trainer's optimiser: one of OptimSpec's three names with optim_args, or an SGD / AdamW spec object (which carries its
+    own constants: optim_args do not apply)"""
+    if isinstance(optimizer, (SGD, AdamW)):
+        if optim_args:
+            raise ValueError("optim_args do not apply to optimizer=%s(...): pass them to the spec object" % type(optimizer).__name__)
+        return optimizer.bound(lr)
+    return OptimSpec(optimizer, lr, betas, eps, optim_args)
+
+
+class _LRSchedule:
+    """A per-update learning-rate rule evaluated ON THE DEVICE from the device step counter, inside the captured step
+    (n3d_lr_schedule): linear warm-up from warmup_start * lr to lr over warmup_steps updates, then the subclass's decay until
+    total_steps, then its end value.  The closed form of torch's SequentialLR([LinearLR, PolynomialLR | CosineAnnealingLR])."""
+
+    kind = None
+    FIELDS = ("total_steps", "power", "warmup_steps", "warmup_start", "min_lr")
+
+    def __init__(self, total_steps, power=1.0, warmup_steps=0, warmup_start=0.1, min_lr=0.0):
+        if int(total_steps) != total_steps or int(warmup_steps) != warmup_steps or not 0 <= warmup_steps < total_steps:
+            raise ValueError("schedule: total_steps and warmup_steps are integers with 0 <= warmup_steps < total_steps (got %r, %r)"
+                             % (total_steps, warmup_steps))
+        if not 0.0 <= warmup_start <= 1.0:
+            raise ValueError("schedule: warmup_start is a factor in [0, 1] (got %r)" % (warmup_start,))
+        if min_lr < 0.0 or power <= 0.0:
+            raise ValueError("schedule: min_lr >= 0 and power > 0 (got %r, %r)" % (min_lr, power))
+        self.total_steps, self.warmup_steps = int(total_steps), int(warmup_steps)
+        self.power, self.warmup_start, self.min_lr = float(power), float(warmup_start), float(min_lr)
+
+    def state_dict(self):
+        return dict(kind=self.name, **{k: getattr(self, k) for k in self.FIELDS})
+
+    def record(self, base_lr, device):
+        return K.lr_schedule_record(self.kind, base_lr, self.min_lr, self.warmup_steps, self.warmup_start, self.total_steps, self.power, device)
+
+
+class PolyLR(_LRSchedule):
+    """`schedule=PolyLR(total_steps=T, power=0.9)`: lr * (1 - u / n)^power floored at min_lr (nnU-Net's rule with no warm-up)"""
+    name, kind = "poly", K.LR_POLY
+
+    def __init__(self, total_steps, power=0.9, warmup_steps=0, warmup_start=0.1, min_lr=0.0):
+        super().__init__(total_steps, power, warmup_steps, warmup_start, min_lr)
+
+
+class CosineLR(_LRSchedule):
+    """`schedule=CosineLR(total_steps=T, warmup_steps=W)`: min_lr + (lr - min_lr) (1 + cos(pi u / n)) / 2"""
+    name, kind = "cosine", K.LR_COSINE
+
+    def __init__(self, total_steps, warmup_steps=0, warmup_start=0.1, min_lr=0.0):
+        super().__init__(total_steps, 1.0, warmup_steps, warmup_start, min_lr)
+
+
+class EMA:
+    """`ema=EMA(decay=0.999)`: an exponential moving average of the weights (torch's AveragedModel with get_ema_multi_avg_fn(decay)),
+    one launch behind every optimiser launch; Trainer.averaged_weights() evaluates and predicts with it"""
+
+    def __init__(self, decay=0.999):
+        if not 0.5 < decay < 1.0:
+            raise ValueError("EMA: 0.5 < decay < 1 (got %r)" % (decay,))
+        self.decay = float(decay)
 
 
 class _GradClip:
@@ -1352,7 +1472,11 @@ class _GraphTrainer:
     def _state(self):
         """optimizer-visible state the schedule timing must leave as it found it"""
         ams = [self.fp.max_exp_avg_sq] if self.fp.max_exp_avg_sq is not None else []
-        return [self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full] + ams
+        # (the averaged weights with their counters, and the rate word a device schedule writes in every step)
+        extra = [] if self.fp.ema is None else [self.fp.ema, self.fp.ema_state]
+        if getattr(self, "_sched_rec", None) is not None:
+            extra.append(self.lr_dev)
+        return [self.fp.flat, self.fp.exp_avg, self.fp.exp_avg_sq, self.fp.step, self.fp.grad_full] + ams + extra
 
     def _choose_schedule(self):
         """time the two captured schedules on the real step (state saved and restored around it) and keep the faster one.  Data
@@ -1373,6 +1497,34 @@ class _GraphTrainer:
             self._retire_side_graphs()     # the plain graph won: the side graphs (and their raw HIP executables) are released
 
 
+class _AveragedWeights:
+    """Trainer.averaged_weights(): fp.flat <-> fp.ema exchanged around the block (n3d_swap_f32), host-visible points on both sides"""
+
+    def __init__(self, trainer):
+        self.tr = trainer
+
+    def _swap(self):
+        tr = self.tr
+        K.swap_f32(tr.fp.flat, tr.fp.ema)
+        tr._averaged = not tr._averaged
+
+    def __enter__(self):
+        tr = self.tr
+        if tr._averaged:
+            raise K.N3DError("averaged_weights(): already inside the block")
+        tr.check_sync()
+        if int(tr.fp.ema_state[0].item()) == 0:
+            raise K.N3DError("averaged_weights(): no update has been averaged yet")
+        self._swap()
+        tr.sync_to_module()       # (padded twin: the user's module sees the averaged parameters too)
+        return tr
+
+    def __exit__(self, *exc):
+        self._swap()
+        self.tr.check_sync()
+        return False
+
+
 class Trainer(_GraphTrainer):
     """One searched-net (or any model built from nas_3d_unet_amd ops) training step.
 
@@ -1382,8 +1534,14 @@ class Trainer(_GraphTrainer):
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph=True, process_group=None,
                  n_buckets=None, params=None, comm=None, storage=None, side_wgrad=None, optimizer="adam", optim_args=None,
-                 grad_clip=None, loss=None):
-        self.optim = OptimSpec(optimizer, lr, betas, eps, optim_args)
+                 grad_clip=None, loss=None, schedule=None, ema=None):
+        self.optim = _optim_spec(optimizer, lr, betas, eps, optim_args)
+        if schedule is not None and not isinstance(schedule, _LRSchedule):
+            raise TypeError("schedule must be a PolyLR or a CosineLR (got %s)" % type(schedule).__name__)
+        if ema is not None and not isinstance(ema, EMA):
+            raise TypeError("ema must be an EMA (got %s)" % type(ema).__name__)
+        self.schedule, self.ema = schedule, ema
+        self._averaged = False       # inside averaged_weights(): fp.flat holds the averaged model, fp.ema the training weights
         super().__init__(model, model, lr, betas, eps, graph, process_group, side_wgrad, loss)
         self.net = model      # the module whose kernels run (the model itself, or its padded twin)
         if self._twin is not None:
@@ -1425,6 +1583,14 @@ class Trainer(_GraphTrainer):
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=self.device)  # read by the Adam kernel
         self._one = torch.ones((), dtype=torch.float32, device=self.device)
         self.scheduler = _plateau_for(self, "lr", "set_lr")  # train.py:50: ReduceLROnPlateau(factor=0.5)
+        self._sched_rec = None
+        if self.schedule is not None:
+            # a per-update rule computed on the device in front of every optimiser launch (it writes lr_dev): the plateau rule
+            # and a per-update rule would fight over that one word, so there is no plateau scheduler
+            self.scheduler = None
+            self._sched_rec = self.schedule.record(float(lr), self.device)
+        if self.ema is not None:
+            self.fp.ensure_ema()
         # (a weight-gradient stream of its own lets the side stream run data gradients of the C <= 8 cells inline: fused.SIDE_PAIRS_BWD)
         self._init_side(comm, wgrad_stream=_fused.SIDE_PAIRS_BWD)
         # the bucketed, overlapped exchange rides on the side-stream schedule (a closed bucket is reduced and sent from the
@@ -1599,7 +1765,11 @@ class Trainer(_GraphTrainer):
             self.fp.grad.mul_(self._pad_mask)
         # grad_clip: the norm of the gradient the optimiser is about to see (slabs reduced, padded entries masked, ranks averaged)
         coef = self._clip.launch(self.fp.grad, 1.0 / self.world) if self._clip is not None else None
+        if self._sched_rec is not None:
+            K.lr_schedule(self.fp.step, self._sched_rec, self.lr_dev)      # the rate of THIS update, from the updates applied so far
         self.fp.update(self.optim, self.lr, 1.0 / self.world, self.lr_dev, self._guard(loss, self.sync), coef)
+        if self.ema is not None:
+            K.ema_step(self.fp.ema, self.fp.flat, self.ema.decay, self.fp.step, self.fp.ema_state)    # (a withheld update: skipped on the device)
 
     @property
     def grad_norm(self):
@@ -1608,9 +1778,27 @@ class Trainer(_GraphTrainer):
         return self._clip.out[0] if self._clip is not None else None
 
     def set_lr(self, lr):
-        """new learning rate for the following steps (also inside an already captured graph)"""
+        """new learning rate for the following steps (also inside an already captured graph).  With a schedule: its BASE rate (one
+        device fill of the schedule record, between replays); lr_dev keeps the rate of the last issued step"""
         self.lr = float(lr)
-        self.lr_dev.fill_(self.lr)
+        if self._sched_rec is not None:
+            self._sched_rec[1:2].fill_(self.lr)
+        else:
+            self.lr_dev.fill_(self.lr)
+
+    def _step(self, *batch):
+        if self._averaged:
+            raise K.N3DError("step() inside averaged_weights(): the flat buffer holds the averaged model, not the training weights")
+        return super()._step(*batch)
+
+    def averaged_weights(self):
+        """`with tr.averaged_weights():` -- evaluate(), predictor(...).predict(...), metrics.score_set(...) and model.state_dict()
+        see the averaged model (train.EMA): the contents of fp.flat and fp.ema are exchanged in place on entry (one launch, no
+        allocation; every captured graph packs the weights from fp.flat at replay) and exchanged back on exit, so the training
+        weights return bit for bit.  check_sync() on entry and on exit; step() inside the block raises."""
+        if self.ema is None:
+            raise K.N3DError("averaged_weights(): this trainer was built without ema=EMA(...)")
+        return _AveragedWeights(self)
 
     def _eager(self, x, t, allow_side=True):
         """allow_side=False: single stream whatever the trainer was built with.  The side-stream schedule ties its streams together
@@ -1769,7 +1957,7 @@ class SearchTrainer(_GraphTrainer):
         # loss: both passes, the architecture pass and the weight pass (search.py:224-226,233-235 call one loss function)
         # optimizer / optim_args / grad_clip: the weight pass (search.py:236-238: the commented clip line sits in front of
         # optim_kernel.step()); the alphas stay on Adam (search.py:103)
-        self.optim = OptimSpec(optimizer, lr, betas, eps, optim_args)
+        self.optim = _optim_spec(optimizer, lr, betas, eps, optim_args)     # (an SGD / AdamW spec object: the weight pass, as well)
         super().__init__(shell, shell.kernel, lr, betas, eps, graph, process_group, side_wgrad, loss)
         # a kernel net with channel counts that are not multiples of 4: the shell's own alphas around its zero-padded twin
         self.net = shell if self._twin is None else _TwinShell(shell, self._twin.twin)
