@@ -740,7 +740,7 @@ typedef struct n3d_patch_wdesc {
   n3d_patch_gdesc g;
   int32_t aflip[3];
   int32_t mode;        /* 0: zoom-shift rule, 1: matrix rule */
-  int32_t order;       /* 0: nearest, 1: linear -- the data only */
+  int32_t order;       /* 0: nearest, 1: linear -- the data only (3: cubic B-spline, taken by n3d_patch_gather_spline alone) */
   int32_t intensity;   /* != 0: gain and bias are applied to the nonzero voxels */
   double k[12];
   float gain[4];
@@ -799,6 +799,41 @@ typedef struct n3d_patch_edesc {
 } n3d_patch_edesc;
 int n3d_patch_gather_elastic(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_edesc* descs, int B, int P, int flags,
                              float* x_out, int64_t xld, void* t_out, void* stream);
+
+/* n3d_patch_gather_elastic with the DATA interpolated by a cubic B-spline (order 3): what scipy.ndimage.map_coordinates(order=3,
+ * mode="constant", cval=0) makes of the crop -- the default resampler of nnU-Net / batchgenerators / TorchIO; none of it the
+ * reference's.  Every descriptor has w.order == 3; coordinate (mode 0 / 1, plus the displacement with `elastic`), bounds test, aflip,
+ * labels (the nearest voxel) and the intensity map are n3d_patch_gather_elastic's.  Per patch b and channel c:
+ *   crop:        raw[q] = volume voxel corner_a + (aflip[a] ? P-1-q_a : q_a), 0.0f outside the volume: fp32, P^3 per (b, c).
+ *   prefilter:   coef = n3d_spline_prefilter(raw) (below): fp64, P^3 per (b, c).
+ *   taps:        a voxel whose c_a lies outside [0, P-1] on some axis is 0 (the bounds test).  Otherwise per axis f = floor(c_a),
+ *                t = c_a - f, the four weights b[0..3] of t as n3d_patch_edesc's evaluation forms them (g = 1.0 - t, ...), for the
+ *                taps q = f-1, f, f+1, f+2, each mirrored into the crop: q < 0 -> -q, q > P-1 -> 2 (P-1) - q (hence P >= 4).
+ *                acc = 0.0, then over the 64 taps in the order 16 i0 + 4 i1 + i2:  acc = acc + ((b0[i0] * b1[i1]) * b2[i2]) * coef[tap],
+ *                every product and sum rounded to fp64 on its own;  y = (float)acc.
+ *   mask:        the filter is recursive, so y is nonzero in the background too.  The voxel is stored as 0.0f when the NEAREST crop
+ *                voxel raw[floor(c_a + 0.5)] of that channel is 0 (-0.0 is zero) -- the voxel order 0 reads; otherwise y is stored,
+ *                and a y that rounded to +-0 is stored as FLT_MIN, so that x != 0 still says "brain".  No clamping: the spline
+ *                overshoots at edges as scipy's does.
+ *   intensity:   on the voxels the mask keeps, * gain[c] then + bias[c] in fp32, as n3d_patch_wdesc.
+ * scratch: DEVICE, 8-byte aligned, n3d_patch_spline_scratch_bytes(B, Cv, P) = 12 bytes per voxel and channel (coef, then raw);
+ * overwritten by every call, holds nothing between calls.  Five launches whatever the data (crop, three prefilter passes, gather),
+ * no host synchronisation, no atomics: capturable.  B <= N3D_PATCH_ELASTIC_MAX_BATCH, P >= 4, P^3 < 2^31, order == 3 everywhere, a
+ * scratch that is not null and large enough, and all n3d_patch_gather_elastic checks, else N3D_ERR_INVALID before any launch.
+ *
+ * n3d_spline_prefilter: scipy.ndimage.spline_filter(order=3, mode="mirror") of n contiguous P^3 fp32 cubes into n fp64 cubes (raw
+ * and coef may not overlap), P >= 4: the lines along axis 0 are filtered first, then axis 1, then axis 2.  With z = sqrt(3.0) - 2.0
+ * and, all computed on the host in fp64, gain = (1.0 - z) * (1.0 - 1.0 / z), zn = z * z * .. * z (P-1 factors, multiplied up one by
+ * one), inv0 = 1.0 / (1.0 - zn * zn), anti = z / (z * z - 1.0), one line c[0..P-1] becomes, every operation rounded on its own:
+ *   c[i] = c[i] * gain for every i  (the first pass converts the fp32 sample to fp64 first);
+ *   s = c[0] + zn * c[P-1];  zi = z;  for i = 1 .. P-2:  s = s + zi * (c[i] + zn * c[P-1-i]),  zi = zi * z;   c[0] = s * inv0;
+ *   for i = 1 .. P-1:  c[i] = c[i] + z * c[i-1];
+ *   c[P-1] = (z * c[P-2] + c[P-1]) * anti;
+ *   for i = P-2 .. 0:  c[i] = z * (c[i+1] - c[i]). */
+size_t n3d_patch_spline_scratch_bytes(int B, int Cv, int P);
+int n3d_spline_prefilter(const float* raw, int64_t n, int P, double* coef, void* stream);
+int n3d_patch_gather_spline(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_edesc* descs, int B, int P, int flags,
+                            void* scratch, size_t scratch_bytes, float* x_out, int64_t xld, void* t_out, void* stream);
 
 /* ---- appearance augmentation of a gathered batch, in place (none of it the reference's: the four transforms of batchgenerators /
  * nnU-Net that the BraTS recipes train with).  x: DEVICE fp32 batch (B, Cv, P, P, P) in NDHWC storage with channel pitch ld >= Cv,

@@ -264,6 +264,9 @@ PROTOTYPES = {
     "n3d_patch_gather_aug": (_i, [_p, _i, _i, C.POINTER(AugDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_warp": (_i, [_p, _i, _i, C.POINTER(WarpDesc), _i, _i, _i, _p, _i64, _p, _p]),
     "n3d_patch_gather_elastic": (_i, [_p, _i, _i, C.POINTER(ElasticDesc), _i, _i, _i, _p, _i64, _p, _p]),
+    "n3d_patch_spline_scratch_bytes": (_sz, [_i, _i, _i]),
+    "n3d_spline_prefilter": (_i, [_p, _i64, _i, _p, _p]),
+    "n3d_patch_gather_spline": (_i, [_p, _i, _i, C.POINTER(ElasticDesc), _i, _i, _i, _p, _sz, _p, _i64, _p, _p]),
     "n3d_patch_appearance": (_i, [_p, _i64, _i, _i, _i, C.POINTER(AppearDesc), _p, _sz, _p]),
     "n3d_patch_appearance_scratch": (_sz, [_i, _i, _i]),
     "n3d_patch_artefact": (_i, [_p, _i64, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),

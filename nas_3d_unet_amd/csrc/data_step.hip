@@ -12,42 +12,12 @@
 // 4 * Cv + 1 loaded, against 3 fp64 adds + 3 multiplies + 3 floors -- 2 x 4 x 64^3 writes 14.7 MB (fp32 targets) and reads at most
 // 8.9 MB, 3 us at 8 TB/s.  A scale > 1 (A < 1) repeats source voxels and reads fewer source bytes; a scale < 1 (A > 1) reads lines strided along z
 // and leaves a border of zeros.
-#include "n3d_common.h"
-
-#include <cmath>
+#include "patch_gather.h"
 
 namespace n3d {
 
 struct PatchDescs { n3d_patch_desc d[N3D_PATCH_MAX_BATCH]; };
 struct GatherDescs { n3d_patch_gdesc d[N3D_PATCH_MAX_BATCH]; };
-
-// the Cv data values of output voxel v of patch b, value(c) for channel c: one float4 for Cv == 4 on an aligned pitch
-template <typename F>
-__device__ __forceinline__ void patch_data_store(int Cv, int b, uint32_t v, uint32_t P3, float* __restrict__ x_out, int64_t xld, F value) {
-  float* xo = x_out + ((int64_t)b * P3 + v) * xld;
-  if (Cv == 4 && (xld & 3) == 0) {
-    float4 q;
-    q.x = value(0); q.y = value(1); q.z = value(2); q.w = value(3);
-    *reinterpret_cast<float4*>(xo) = q;
-  } else {
-    for (int c = 0; c < Cv; ++c) xo[c] = value(c);
-  }
-}
-
-// the three target maps of output voxel v of patch b from its label voxel sv (in = false: no source, label 0)
-template <typename TT>
-__device__ __forceinline__ void patch_label_store(const uint8_t* __restrict__ truth, bool in, int64_t sv, int b, uint32_t v, uint32_t P3,
-                                                  int inclusive, TT* __restrict__ t_out) {
-  // (a gathered patch whose volume has no truth reads as label 0 everywhere; n3d_patch_batch never gets here without truth)
-  const int l = (in && truth) ? (int)truth[sv] : 0;
-  // generator.py:241-243 -- the inclusive "whole tumour" channel is labels {1, 2}: np.logical_or's third argument
-  // is its OUT array there, so label 4 does not enter (reproduced, not corrected)
-  const TT c0 = inclusive ? (TT)(l == 1 || l == 4) : (TT)(l == 1);
-  const TT c1 = inclusive ? (TT)(l == 1 || l == 2) : (TT)(l == 2);
-  const TT c2 = (TT)(l == 4);
-  TT* to = t_out + (int64_t)b * 3 * P3 + v;
-  to[0] = c0; to[P3] = c1; to[2 * (int64_t)P3] = c2;
-}
 
 // the loads, the stores and the label expansion of output voxel v of patch b, given its source voxel s of the volume (ok = false:
 // the patch voxel has no source -- resampled from outside the patch -- and reads as outside the volume does: zero, label 0)
@@ -61,19 +31,6 @@ __device__ __forceinline__ void patch_voxel_store(const float* __restrict__ vol,
   const int64_t XYZ = (int64_t)X * Y * Z;
   patch_data_store(Cv, b, v, P3, x_out, xld, [=](int c) { return in ? vol[c * XYZ + sv] : 0.f; });
   if (t_out) patch_label_store<TT>(truth, in, sv, b, v, P3, inclusive, t_out);
-}
-
-// patch index of output voxel v on source axis a under the isometry of d: j_a = i[perm[a]], or P-1-i[perm[a]] with flip[a]
-__device__ __forceinline__ void patch_index(const n3d_patch_desc& d, uint32_t v, int P, FastDiv fP, FastDiv fPP, int (&j)[3]) {
-  uint32_t i0, r, i1, i2;
-  fPP.divmod(v, i0, r);
-  fP.divmod(r, i1, i2);
-  const int idx[3] = {(int)i0, (int)i1, (int)i2};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int t = d.perm[a] == 0 ? idx[0] : (d.perm[a] == 1 ? idx[1] : idx[2]);
-    j[a] = d.flip[a] ? P - 1 - t : t;
-  }
 }
 
 // one output voxel (b, i0, i1, i2) of patch d drawn from the volume (vol, truth, X, Y, Z): the index mapping shared by
@@ -157,22 +114,6 @@ __global__ __launch_bounds__(256) void patch_gather_aug_kernel(const n3d_patch_v
 // waits for is their latency: 2 x 4 x 64^3 rotated by 15 degrees takes 12.7 us at order 0 and 27.2 us at order 1, 27.6 us at order 1
 // without a rotation (profiles/warp_probe.log; the plain gather: 11.4 us).
 struct WarpDescs { n3d_patch_wdesc d[N3D_PATCH_WARP_MAX_BATCH]; };
-
-// the warp rule's coordinate of patch index j
-__device__ __forceinline__ void patch_warp_coordinate(const n3d_patch_wdesc& w, const int (&j)[3], double (&c)[3]) {
-  if (w.mode == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = ((double)j[a] + w.k[3 + a]) * w.k[a];
-  } else {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      double t = w.k[3 * a] * (double)j[0];
-      t = t + w.k[3 * a + 1] * (double)j[1];
-      t = t + w.k[3 * a + 2] * (double)j[2];
-      c[a] = t + w.k[9 + a];
-    }
-  }
-}
 
 // everything of the warp rule downstream of the coordinate c of output voxel v of patch b: bounds, nearest voxel, order 0 / 1, aflip,
 // the crop's zero padding, the intensity map, the stores
@@ -280,20 +221,7 @@ __global__ __launch_bounds__(256) void patch_gather_warp_kernel(const n3d_patch_
 // and 441 fp64 operations (some 6 us).  2 x 4 x 64^3, both patches deformed: 27.2 us at cells 4 and order 0, 37.0 / 40.3 us at order 1
 // and cells 4 / 8; with no patch deformed 13.4 us against the warp kernel's 11.5 (168 registers and the LDS leave fewer waves to
 // hide the gather's loads): profiles/elastic_probe.log.  Not examined with counters.
-struct ElasticDescs { n3d_patch_edesc d[N3D_PATCH_ELASTIC_MAX_BATCH]; };
-constexpr int kElasticMaxG = N3D_PATCH_ELASTIC_MAX_CELLS + 3;
-constexpr int kElasticMaxG3 = kElasticMaxG * kElasticMaxG * kElasticMaxG;
-
-// the four uniform cubic B-spline weights of f
-__device__ __forceinline__ void bspline_weights(double f, double (&bw)[4]) {
-  const double S = 1.0 / 6.0;
-  const double g = 1.0 - f;
-  bw[0] = ((g * g) * g) * S;
-  bw[1] = ((((3.0 * f - 6.0) * f) * f) + 4.0) * S;
-  bw[2] = ((((3.0 - 3.0 * f) * f + 3.0) * f) + 1.0) * S;
-  bw[3] = ((f * f) * f) * S;
-}
-
+// (ElasticDescs, the lattice and the displacement: patch_gather.h)
 template <typename TT>
 __global__ __launch_bounds__(256) void patch_gather_elastic_kernel(const n3d_patch_volume* __restrict__ vols, int Cv, ElasticDescs descs, int P,
                                                                    int inclusive, float* __restrict__ x_out, int64_t xld, TT* __restrict__ t_out,
@@ -304,17 +232,8 @@ __global__ __launch_bounds__(256) void patch_gather_elastic_kernel(const n3d_pat
   const n3d_patch_wdesc& w = e.w;
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
   const bool elastic = e.elastic != 0;
-  const int n = e.cells, G = n + 3, G3 = G * G * G;        // the host checked 1 <= n <= N3D_PATCH_ELASTIC_MAX_CELLS
   if (elastic) {
-    const int L = e.lock;
-    for (int l = threadIdx.x; l < G3; l += 256) {
-      const int l0 = l / (G * G), l1 = (l / G) % G, l2 = l % G;
-      const bool locked = l0 < L || l0 >= G - L || l1 < L || l1 >= G - L || l2 < L || l2 >= G - L;
-      uint32_t r[4];
-      philox4x32_10((uint32_t)l, 1, 0, 0, e.key[0], e.key[1], r);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) lattice[a * G3 + l] = locked ? 0.0 : 2.0 * ((double)r[a] * 0x1p-32) - 1.0;
-    }
+    elastic_lattice_fill(e, lattice);
     __syncthreads();      // every thread of the workgroup gets here: the ones past the patch's end leave only below
   }
   if (v >= (uint32_t)P * P * P) return;
@@ -323,43 +242,7 @@ __global__ __launch_bounds__(256) void patch_gather_elastic_kernel(const n3d_pat
   patch_index(w.g.d, v, P, fP, fPP, j);
   double c[3];
   patch_warp_coordinate(w, j, c);
-  if (elastic) {
-    double bw[3][4];
-    int cell[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double s = (double)j[a] * e.inv_h;
-      cell[a] = (int)fmin(floor(s), (double)(n - 1));       // s >= 0 (inv_h >= 0 was checked): 0 <= cell <= n - 1, cell + 3 <= G - 1
-      bspline_weights(s - (double)cell[a], bw[a]);
-    }
-    const int base = (cell[0] * G + cell[1]) * G + cell[2];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double* __restrict__ D = lattice + a * G3 + base;
-      double U[4];
-#pragma unroll
-      for (int m0 = 0; m0 < 4; ++m0) {
-        double T[4];
-#pragma unroll
-        for (int m1 = 0; m1 < 4; ++m1) {
-          const double* d = D + (m0 * G + m1) * G;
-          double t = bw[2][0] * d[0];
-          t = t + bw[2][1] * d[1];
-          t = t + bw[2][2] * d[2];
-          T[m1] = t + bw[2][3] * d[3];
-        }
-        double u = bw[1][0] * T[0];
-        u = u + bw[1][1] * T[1];
-        u = u + bw[1][2] * T[2];
-        U[m0] = u + bw[1][3] * T[3];
-      }
-      double acc = bw[0][0] * U[0];
-      acc = acc + bw[0][1] * U[1];
-      acc = acc + bw[0][2] * U[2];
-      acc = acc + bw[0][3] * U[3];
-      c[a] = c[a] + e.amp[a] * acc;
-    }
-  }
+  if (elastic) elastic_displace(e, lattice, j, c);
   patch_warp_resample<TT>(r, w, c, Cv, b, v, P, inclusive, x_out, xld, t_out);
 }
 
@@ -465,26 +348,6 @@ extern "C" int n3d_patch_gather_aug(const n3d_patch_volume* vols, int nvol, int 
   return N3D_OK;
 }
 
-// the checks of one n3d_patch_wdesc, for the entry point `fn`
-static int patch_wdesc_check(const char* fn, const n3d_patch_wdesc& d, int i, int nvol, int Cv) {
-  N3D_CHECK_ARG(d.g.vol >= 0 && d.g.vol < nvol, "%s: descriptor %d names volume %d of a set of %d", fn, i, d.g.vol, nvol);
-  int seen = 0;
-  for (int a = 0; a < 3; ++a) {
-    N3D_CHECK_ARG(d.g.d.perm[a] >= 0 && d.g.d.perm[a] < 3, "%s: perm entries must be 0..2", fn);
-    seen |= 1 << d.g.d.perm[a];
-  }
-  N3D_CHECK_ARG(seen == 7, "%s: perm must be a permutation of (0,1,2)", fn);
-  N3D_CHECK_ARG(d.mode == 0 || d.mode == 1, "%s: descriptor %d: mode must be 0 or 1 (got %d)", fn, i, d.mode);
-  N3D_CHECK_ARG(d.order == 0 || d.order == 1, "%s: descriptor %d: order must be 0 or 1 (got %d)", fn, i, d.order);
-  for (int n = 0; n < 12; ++n) N3D_CHECK_ARG(std::isfinite(d.k[n]), "%s: descriptor %d: coefficient %d must be finite (got %g)", fn, i, n, d.k[n]);
-  for (int a = 0; a < 3 && d.mode == 0; ++a) N3D_CHECK_ARG(d.k[a] != 0.0, "%s: descriptor %d axis %d: A must be nonzero in mode 0", fn, i, a);
-  for (int c = 0; c < 4; ++c)
-    N3D_CHECK_ARG(std::isfinite(d.gain[c]) && std::isfinite(d.bias[c]), "%s: descriptor %d channel %d: gain and bias must be finite (got %g, %g)", fn,
-                  i, c, d.gain[c], d.bias[c]);
-  N3D_CHECK_ARG(!d.intensity || Cv <= 4, "%s: descriptor %d: the intensity map supports at most 4 channels (got %d)", fn, i, Cv);
-  return N3D_OK;
-}
-
 extern "C" int n3d_patch_gather_warp(const n3d_patch_volume* vols, int nvol, int Cv, const n3d_patch_wdesc* descs, int B, int P, int flags,
                                      float* x_out, int64_t xld, void* t_out, void* stream) {
   N3D_CHECK_ARG(vols && descs && x_out && nvol >= 1 && Cv >= 1 && P > 0 && B >= 1 && xld >= Cv, "patch_gather_warp: bad args");
@@ -525,16 +388,7 @@ extern "C" int n3d_patch_gather_elastic(const n3d_patch_volume* vols, int nvol, 
     const n3d_patch_edesc& d = descs[i];
     ed.d[i] = d;
     if (int rc = patch_wdesc_check("patch_gather_elastic", d.w, i, nvol, Cv)) return rc;
-    N3D_CHECK_ARG(d.cells >= 1 && d.cells <= N3D_PATCH_ELASTIC_MAX_CELLS, "patch_gather_elastic: descriptor %d: cells must be 1..%d (got %d)", i,
-                  N3D_PATCH_ELASTIC_MAX_CELLS, d.cells);
-    N3D_CHECK_ARG(d.lock >= 0 && d.lock <= 3, "patch_gather_elastic: descriptor %d: lock must be 0..3 (got %d)", i, d.lock);
-    N3D_CHECK_ARG(d.cells + 3 - 2 * d.lock >= 1, "patch_gather_elastic: descriptor %d: lock %d leaves no free control point on a lattice of %d", i,
-                  d.lock, d.cells + 3);
-    for (int a = 0; a < 3; ++a)
-      N3D_CHECK_ARG(std::isfinite(d.amp[a]) && d.amp[a] >= 0.0, "patch_gather_elastic: descriptor %d axis %d: amp must be finite and >= 0 (got %g)",
-                    i, a, d.amp[a]);
-    N3D_CHECK_ARG(std::isfinite(d.inv_h) && d.inv_h >= 0.0, "patch_gather_elastic: descriptor %d: inv_h must be finite and >= 0 (got %g)", i,
-                  d.inv_h);
+    if (int rc = patch_edesc_check("patch_gather_elastic", d, i)) return rc;
   }
   for (int i = B; i < N3D_PATCH_ELASTIC_MAX_BATCH; ++i) ed.d[i] = ed.d[0];
   N3D_CHECK_ARG((flags & ~(N3D_PATCH_INCLUSIVE | N3D_PATCH_T_U8)) == 0, "patch_gather_elastic: unknown flag bits %d", flags);

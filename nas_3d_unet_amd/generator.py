@@ -53,6 +53,7 @@ from . import _lib, appearance, datastep, predict, preprocess
 from . import artefact as artefact_mod
 from . import elastic as elastic_mod
 from . import sampling as sampling_mod
+from . import spline as spline_mod
 from . import kernels as K
 from ._lib import AugDesc, ElasticDesc, GatherDesc, N3DError, PatchDesc, PatchVolume, WarpDesc, check
 
@@ -64,6 +65,7 @@ AUG_MAX_BATCH = 32  # N3D_PATCH_AUG_MAX_BATCH: the widened descriptors of an aug
 WARP_MAX_BATCH = 16  # N3D_PATCH_WARP_MAX_BATCH
 WARP_MAX_CHANNELS = 4  # gain[4], bias[4] of n3d_patch_wdesc
 ELASTIC_MAX_BATCH = elastic_mod.MAX_BATCH  # N3D_PATCH_ELASTIC_MAX_BATCH
+INTERPOLATION_ORDER = {"nearest": 0, "linear": 1, "spline3": spline_mod.ORDER}   # augment_interpolation -> order of n3d_patch_wdesc
 
 _ISO = {None: ([0, 1, 2], [False, False, False])}
 
@@ -253,6 +255,7 @@ class VolumeSet:
         self.line_indexes = []     # per volume: its n3d_volume_line_index table, built by line_index(i) when first asked for
         self.index_ptrs = None     # device array of their addresses, 0 where none is built (rebuilt by index_table)
         self._index_ptrs_of = None
+        self._spline_scratch = {}  # (B, Cv, P) -> the scratch of n3d_patch_gather_spline, allocated at the first such batch and reused
 
     def __len__(self):
         return len(self.volumes)
@@ -421,8 +424,8 @@ class VolumeSet:
             A, sh, identity, axes = a
             aflip = [int(n in axes) for n in range(3)] if axes else [0, 0, 0]
             matrix, order, gain, bias = warp[i] if warp[i] is not None else (None, 0, None, None)
-            if int(order) not in (0, 1):
-                raise N3DError("VolumeSet.patch_batch: the interpolation order is 0 (nearest) or 1 (linear)")
+            if int(order) not in (0, 1, 3):
+                raise N3DError("VolumeSet.patch_batch: the interpolation order is 0 (nearest), 1 (linear) or 3 (cubic B-spline)")
             if matrix is not None:
                 M, off = (np.asarray(m, np.float64) for m in matrix)
                 if M.shape != (3, 3) or off.shape != (3,):
@@ -443,6 +446,10 @@ class VolumeSet:
                 bs[:self.channels] = [float(x) for x in np.asarray(bias, np.float64).reshape(self.channels)]
             descs[i] = WarpDesc(g, (C.c_int32 * 3)(*aflip), mode, int(order), int(intensity), (C.c_double * 12)(*k),
                                 (C.c_float * 4)(*gn), (C.c_float * 4)(*bs))
+        orders = {int(d.order) for d in descs}
+        if 3 in orders and len(orders) > 1:
+            raise N3DError("VolumeSet.patch_batch: order 3 (cubic B-spline) takes the whole batch through its own launches: every warp "
+                           "entry of the batch has order 3, or none (got the orders %s)" % sorted(orders))
         return descs
 
     def _elastic_descs(self, refs, P, augment, warp, elastic):
@@ -487,7 +494,12 @@ class VolumeSet:
         n3d_patch_edesc (cells per axis, locked border layers, the Philox key (k0, k1) of the control values, the largest displacement
         in voxels -- a scalar or one per axis) is added to that ref's coordinate, whatever augment and warp make of it.  With some entry
         not None the batch is ONE n3d_patch_gather_elastic launch (at most 8 patches).  Otherwise the launches are exactly the ones
-        above."""
+        above.
+        Order 3 in a warp entry: the data is interpolated by a cubic B-spline, scipy's map_coordinates(order=3, mode="constant") on the
+        crop, stored as 0 where order 0 would read 0 (include/n3d.h, n3d_patch_gather_spline).  Then EVERY entry of the batch has
+        order 3 (a None entry counts as order 0; mixing raises), the batch holds at most 8 patches of at least 4 voxels an edge and is
+        five launches (crop, three prefilter passes, gather), with or without elastic entries, over a scratch of 12 bytes per voxel and
+        channel that the set allocates at the first batch of a (B, Cv, P) and reuses."""
         if target_dtype not in (torch.float32, torch.uint8):
             raise N3DError("VolumeSet.patch_batch: targets are float32 or uint8")
         B, P = len(refs), int(patch)
@@ -500,7 +512,15 @@ class VolumeSet:
             raise N3DError("VolumeSet.patch_batch: one augmentation (or None) per ref")
         if augmented and B > AUG_MAX_BATCH:
             raise N3DError("VolumeSet.patch_batch: an augmented batch holds at most %d patches (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
-        if deformed:
+        spline = warp is not None and any(w is not None and int(w[1]) == spline_mod.ORDER for w in warp)
+        if spline:
+            if B > ELASTIC_MAX_BATCH:
+                raise N3DError("VolumeSet.patch_batch: a batch interpolated at order 3 holds at most %d patches "
+                               "(N3D_PATCH_ELASTIC_MAX_BATCH)" % ELASTIC_MAX_BATCH)
+            if P < spline_mod.MIN_PATCH:
+                raise N3DError("VolumeSet.patch_batch: order 3 needs a patch of at least %d voxels an edge (got %d)" % (spline_mod.MIN_PATCH, P))
+            descs = self._elastic_descs(refs, P, augment, warp, elastic if elastic is not None else [None] * B)
+        elif deformed:
             descs = self._elastic_descs(refs, P, augment, warp, elastic)
         else:
             descs = self._warp_descs(refs, P, augment, warp) if warped else ((AugDesc if augmented else GatherDesc) * B)()
@@ -536,7 +556,15 @@ class VolumeSet:
             t = torch.empty((B, 3, P, P, P), dtype=target_dtype, device=self.device) if self.has_truth else None
             xv = K.as_view(x)
         flags = (_lib.PATCH_INCLUSIVE if inclusive_label else 0) | (_lib.PATCH_T_U8 if target_dtype == torch.uint8 else 0)
-        if deformed:
+        if spline:
+            lib = _lib.load()
+            scratch = self._spline_scratch.get((B, Cv, P))
+            if scratch is None:
+                scratch = self._spline_scratch[(B, Cv, P)] = torch.empty(int(lib.n3d_patch_spline_scratch_bytes(B, Cv, P)), dtype=torch.uint8,
+                                                                         device=self.device)
+            check(lib.n3d_patch_gather_spline(K.ptr(self.records), len(self), Cv, descs, B, P, flags, K.ptr(scratch), scratch.numel(), xv.p,
+                                              xv.ld, K.ptr(t), K.stream_ptr()), "n3d_patch_gather_spline")
+        elif deformed:
             check(_lib.load().n3d_patch_gather_elastic(K.ptr(self.records), len(self), Cv, descs, B, P, flags, xv.p, xv.ld, K.ptr(t),
                                                        K.stream_ptr()), "n3d_patch_gather_elastic")
         elif warped:
@@ -573,6 +601,12 @@ class Generator:
     patch's voxel centre, in voxel space, ahead of the scale map (rotation_matrix, warp_transform);
     augment_interpolation="linear": the data is interpolated linearly over the eight voxels around the coordinate; the truth stays
     nearest neighbour;
+    augment_interpolation="spline3": the data is interpolated by a cubic B-spline -- scipy's map_coordinates(order=3, mode="constant")
+    on the crop, nnU-Net's / batchgenerators' / TorchIO's default -- and stored as exactly 0 where nearest neighbour would read 0, so
+    the background stays background; no clamping, the spline overshoots at edges as scipy's does; the truth stays nearest neighbour.
+    The draws are those of "linear".  Every batch is then n3d_patch_gather_spline's five launches (include/n3d.h) over a scratch of 12
+    bytes per voxel and channel that the volume set keeps; batch_size at most 8 (N3D_PATCH_ELASTIC_MAX_BATCH), patches of at least
+    4 voxels an edge;
     augment_intensity_scale=g / augment_intensity_shift=s: every modality's NONZERO voxels are multiplied by a factor uniform in
     [1 - g, 1 + g] and shifted by a normal(0, s) offset, per patch and modality (at most 4 channels); background stays exactly 0.
     np_rng then sees, per kept patch and after draw_augment's calls: uniform(-r, r, 3), uniform(1 - g, 1 + g, Cv), normal(0, s, Cv),
@@ -634,8 +668,8 @@ class Generator:
             raise N3DError("Generator: targets are float32 or uint8")
         if augment and int(batch_size) > AUG_MAX_BATCH:
             raise N3DError("Generator: batch_size must be 1..%d with augment=True (N3D_PATCH_AUG_MAX_BATCH)" % AUG_MAX_BATCH)
-        if augment_interpolation not in ("nearest", "linear"):
-            raise N3DError("Generator: augment_interpolation is 'nearest' or 'linear' (got %r)" % (augment_interpolation,))
+        if augment_interpolation not in INTERPOLATION_ORDER:
+            raise N3DError("Generator: augment_interpolation is 'nearest', 'linear' or 'spline3' (got %r)" % (augment_interpolation,))
         intensity = augment_intensity_scale is not None or augment_intensity_shift is not None
         warped = augment_rotation is not None or augment_interpolation != "nearest" or intensity
         if warped and not augment:
@@ -644,6 +678,13 @@ class Generator:
         if warped and int(batch_size) > WARP_MAX_BATCH:
             raise N3DError("Generator: batch_size must be 1..%d with a rotation, linear interpolation or an intensity map "
                            "(N3D_PATCH_WARP_MAX_BATCH)" % WARP_MAX_BATCH)
+        if augment_interpolation == "spline3":
+            if int(batch_size) > ELASTIC_MAX_BATCH:
+                raise N3DError("Generator: batch_size must be 1..%d with augment_interpolation='spline3' (N3D_PATCH_ELASTIC_MAX_BATCH)"
+                               % ELASTIC_MAX_BATCH)
+            if ps[0] < spline_mod.MIN_PATCH:
+                raise N3DError("Generator: augment_interpolation='spline3' needs patches of at least %d voxels an edge (got %d)" % (
+                    spline_mod.MIN_PATCH, ps[0]))
         if augment_rotation is not None:
             r = np.asarray(augment_rotation, np.float64)
             if r.shape not in ((), (3,)) or not np.isfinite(r).all() or (r < 0).any():
@@ -827,7 +868,7 @@ class Generator:
     def _warped_epoch(self, out, draws):
         """epoch() with one of the rotation / interpolation / intensity options set: every batch is one n3d_patch_gather_warp launch"""
         cand, P = self.candidates, self.patch
-        order = 1 if self.augment_interpolation == "linear" else 0
+        order = INTERPOLATION_ORDER[self.augment_interpolation]
         wdraws = (self.np_rng, self.augment_rotation, self.augment_intensity_scale, self.augment_intensity_shift, self.volumes.channels)
         for batch in epoch_order(self.flags, self.batch_size, self.rng, self._skip_health(), self.shuffle_index_list, self.permute,
                                  augment=draws, warp=wdraws, appearance=self._appearance_draws(), **self._elastic_draws(),
