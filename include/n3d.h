@@ -371,6 +371,18 @@ size_t n3d_bwd_small_scratch_bytes(int B, int G);
 int n3d_affine_act_bwd_small(const float* dout, int64_t dld, const float* dout1, int64_t dld1, const n3d_gn_bwd_term* t0,
                              const n3d_gn_bwd_term* t1, int B, int64_t N, int C, int G, void* scratch, size_t scratch_bytes,
                              uint32_t* tickets, void* stream);
+/* n3d_affine_act_bwd_small (mode 1, two terms, one output gradient) + n3d_conv_bwd_data2 of a searched-cell node in ONE launch: call c_i
+ * is the data gradient of the conv that produced raw of term t_i (c_i->dy == t_i->draw, c_i->dyld == t_i->drld).  Every workgroup of the
+ * K-split pair kernel rebuilds d(raw) of its own term for the one or two samples its rows draw from and multiplies it out of LDS; d(raw),
+ * dgamma, dbeta, dbias_conv and both dx come out bit for bit as from the two calls (d(raw) is still written: weight gradients read it).
+ * Taken for fp32 storage, n3d_bwd_small2_ok shapes with C / G == 16, G <= 4 and B * G * ceil(N / 16) <= 32, no dalpha, both convs dense
+ * on the 16-way K-split plan with distinct dx, without N3D_MM_BF16 / N3D_NO_MFMA; relu_src, out_gate and N3D_ACCUMULATE of the calls
+ * work as in n3d_conv_bwd_data2.  n3d_gn_bwd_conv_data2_ok answers 1 / 0 from the same decision code without launching; where it says 0
+ * the entry point returns N3D_ERR_UNSUPPORTED and has touched nothing: keep the two calls. */
+int n3d_gn_bwd_conv_data2_ok(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C,
+                             int G, const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1);
+int n3d_gn_bwd_conv_data2(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C, int G,
+                          const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream);
 /* the same pairing for tensors with more partial rows than the fused prologues accept (the 32^3 / 64^3 levels):
  * n3d_gn_coeffs2 = two n3d_gn_coeffs in one launch (fills a_out, b_out, mean_rstd_out, sumraw of both terms);
  * n3d_affine_act2 = two n3d_affine_act into one output (reads a_out / b_out as the coefficients; stats unused);

@@ -2770,6 +2770,32 @@ int n3d_conv_bwd_data2_folds(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_cal
   return mfma_vox_multi_folds(2, cc);
 }
 
+// n3d_gn_bwd_conv_data2 and its query: one walk over the arguments, one decision (mfma_gn_fold_pair)
+static int gn_bwd_conv_data2_impl(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C,
+                                  int G, const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream, bool launch) {
+  if (!dout || !t0 || !t1 || !c0 || !c1 || !c0->g || !c1->g) return 0;
+  const n3d_conv_bwd_call* cs[2] = {c0, c1};
+  for (int i = 0; i < 2; ++i) {      // n3d_conv_bwd_data2's own conditions
+    const n3d_conv_bwd_call* c = cs[i];
+    if (check_geom(c->g, "gn_bwd_conv_data2") || !c->dy || !c->w || !c->dx) return 0;
+    if (c->transposed && (c->relu_src || c->out_gate)) return 0;
+  }
+  return mfma_gn_fold_pair(dout, dld, t0, t1, B, N, C, G, conv_call_bwd(c0), conv_call_bwd(c1), (hipStream_t)stream, launch);
+}
+
+int n3d_gn_bwd_conv_data2_ok(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C,
+                             int G, const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1) {
+  return gn_bwd_conv_data2_impl(dout, dld, t0, t1, B, N, C, G, c0, c1, nullptr, false) == 1 ? 1 : 0;
+}
+
+int n3d_gn_bwd_conv_data2(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C, int G,
+                          const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream) {
+  const int r = gn_bwd_conv_data2_impl(dout, dld, t0, t1, B, N, C, G, c0, c1, stream, true);
+  if (r < 0) return r;
+  if (r == 0) N3D_UNSUPPORTED("gn_bwd_conv_data2: not taken (n3d_gn_bwd_conv_data2_ok); call n3d_affine_act_bwd_small + n3d_conv_bwd_data2");
+  return N3D_OK;
+}
+
 int n3d_conv_bwd_both2(const n3d_conv_bwd_call* c0, const n3d_conv_bwd_call* c1, void* stream) {
   N3D_CHECK_ARG(c0 && c1 && c0->g && c1->g, "conv_bwd_both2: bad args");
   const n3d_conv_bwd_call* cs[2] = {c0, c1};

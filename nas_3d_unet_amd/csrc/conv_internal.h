@@ -43,6 +43,10 @@ int mfma_conv_stats_rows(const n3d_conv_geom* g, bool data_grad, int flags);
 int mfma_pack_layout(const n3d_conv_geom* g, bool data_grad, int flags);  // 1 gemm16, 2 vox64, 3 vox_up, 0 none
 void mfma_pack16(const float* w, float* wp, int Co, int Ci, int taps, int data_grad, hipStream_t s);
 int mfma_conv_pair_try(const ConvCall& c0, const ConvCall& c1, hipStream_t s);
+// the data-gradient pair of a node with its GroupNorm-epilogue backward rebuilt in the launch (c_i multiplies d(raw) of term t_i):
+// 1 = taken (launched unless `launch` is false: the query and the entry point share the decision), 0 = declined, nothing touched
+int mfma_gn_fold_pair(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C, int G,
+                      const ConvCall& c0, const ConvCall& c1, hipStream_t s, bool launch);
 int mfma_conv_multi_try(int n, const ConvCall* c, hipStream_t s);
 int mfma_vox_multi_try(int n, const ConvCall* c, hipStream_t s);
 int mfma_vox_multi_folds(int n, const ConvCall* c);      // 1 = mfma_vox_multi_try would launch (the same decision code)

@@ -13,6 +13,7 @@
 //   src coordinate = (dst*sn + off + tap*dt) / den   (valid iff divisible and in range).
 #include <stdlib.h>
 #include "conv_internal.h"
+#include "gn_bwd_small.h"
 #include <type_traits>
 #include <atomic>
 // cache policy of the weight-gradient kernels' LDS-DMA loads (cpol bits: 1 = sc0, 2 = nt, 16 = sc1).  These kernels run on the side
@@ -71,8 +72,12 @@ __global__ void pack16_kernel(const float* __restrict__ w, float* __restrict__ w
   wp[i] = w[((int64_t)co * Ci + ci) * taps + tap];
 }
 
-template <int MT, int NT, int KSPLIT, bool BF = false>
-__device__ __forceinline__ void gemm16_body_t(const MfArgs& a, const int bx, const int by, float* lds) {
+// LSRC: the source operand is an LDS tile the caller has filled (conv_gemm16_gnpair_kernel: d(raw) of the samples this workgroup's rows
+// draw from, rebuilt in its prologue) instead of a tensor in memory: `ltile` = [sample - lsb0][source voxel] rows of `lpitch` floats,
+// `lzero` = byte offset of a row of zeros for the lanes whose tap is outside the volume, of the wrong parity, or whose row does not exist
+template <int MT, int NT, int KSPLIT, bool BF = false, bool LSRC = false>
+__device__ __forceinline__ void gemm16_body_t(const MfArgs& a, const int bx, const int by, float* lds, const float* ltile = nullptr,
+                                              const int lpitch = 0, const int lsb0 = 0, const int lzero = 0) {
   N3D_CHAIN_PRIO();
   // the wave index as a SCALAR: the K-slice a wave owns (tap, channel block, their offsets) is then computed on the scalar unit
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -165,8 +170,8 @@ __device__ __forceinline__ void gemm16_body_t(const MfArgs& a, const int bx, con
     ph[t] = den2 ? rh[t] >> 1 : rh[t] * a.sn;
     pw[t] = den2 ? rw[t] >> 1 : rw[t] * a.sn;
     lpar[t] = den2 ? ((rd[t] & 1) | ((rh[t] & 1) << 1) | ((rw[t] & 1) << 2)) : 0;
-    const int vox = ((rb[t] * a.Ds + pd[t]) * a.Hs + ph[t]) * a.Ws + pw[t];
-    voffA[t] = rvalid[t] ? (uint32_t)((vox * (int)a.sld + kk * 4) * 4) : OOB;
+    const int vox = (((LSRC ? rb[t] - lsb0 : rb[t]) * a.Ds + pd[t]) * a.Hs + ph[t]) * a.Ws + pw[t];
+    voffA[t] = rvalid[t] ? (uint32_t)((vox * (LSRC ? lpitch : (int)a.sld) + kk * 4) * 4) : OOB;
   }
   const uint32_t voffB = (uint32_t)((kk * a.Cd + n0 + m) * 16);
   // The tap part, ONE table per workgroup: thread g works out group g (tap = g / (Cs/16), its three offsets, the stride-2 halves and
@@ -176,7 +181,7 @@ __device__ __forceinline__ void gemm16_body_t(const MfArgs& a, const int bx, con
   // sd | sh << 8 | sw << 16 | parity << 24 }.  The source resource starts BIAS bytes in front of the tensor so that the scalar offset
   // of a tap that reaches backwards stays non-negative; only lanes whose voxel exists add it.
   __shared__ int gtab[256 * 4];
-  const int bias_el = ((4 * a.Hs + 4) * a.Ws + 4) * (int)a.sld;      // |tap offset| <= 4 voxels per axis (pad, dilation <= 2)
+  const int bias_el = LSRC ? 0 : ((4 * a.Hs + 4) * a.Ws + 4) * (int)a.sld;      // |tap offset| <= 4 voxels per axis (pad, dilation <= 2)
   for (int g = threadIdx.x; g < ngroups; g += blockDim.x) {
     const int tap = (int)a.fC16.div((uint32_t)g), c16 = g - tap * c16n;
     // k is 1 or 3: constant divisors
@@ -185,7 +190,7 @@ __device__ __forceinline__ void gemm16_body_t(const MfArgs& a, const int bx, con
     // tap part of the voxel coordinate: the offset itself, or its upper half for the stride-2 data gradient
     const int sd = den2 ? (od + (od & 1)) >> 1 : od, sh = den2 ? (oh + (oh & 1)) >> 1 : oh, sw = den2 ? (ow + (ow & 1)) >> 1 : ow;
     const int spar = den2 ? ((od & 1) | ((oh & 1) << 1) | ((ow & 1) << 2)) : 0;
-    const int soff = ((sd * a.Hs + sh) * a.Ws + sw) * (int)a.sld + c16 * 16;
+    const int soff = ((sd * a.Hs + sh) * a.Ws + sw) * (LSRC ? lpitch : (int)a.sld) + c16 * 16;
     int4 e;
     e.x = (soff + bias_el) * 4;
     e.y = g * 4 * a.Cd * 16;
@@ -211,8 +216,15 @@ __device__ __forceinline__ void gemm16_body_t(const MfArgs& a, const int bx, con
       const int nd = pd[t] + sd, nh = ph[t] + sh, nw = pw[t] + sw;
       // unsigned compares fold the two-sided range tests (bitwise &: a short-circuit && becomes control flow)
       const bool ok = ((unsigned)nd < (unsigned)a.Ds) & ((unsigned)nh < (unsigned)a.Hs) & ((unsigned)nw < (unsigned)a.Ws) & (lpar[t] == spar);
-      const v4i_t raw = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)(ok ? voffA[t] : OOB), soffA, 0);
-      float4 v = __builtin_bit_cast(float4, raw);
+      float4 v;
+      if constexpr (LSRC) {
+        // one ds_read_b128 per lane; the tap part of the address is a (signed) byte offset inside the tile of the lane's own sample
+        const int off = (ok & rvalid[t]) ? (int)voffA[t] + soffA : lzero + kk * 16;
+        v = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(ltile) + off);
+      } else {
+        const v4i_t raw = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)(ok ? voffA[t] : OOB), soffA, 0);
+        v = __builtin_bit_cast(float4, raw);
+      }
       // (the input ReLU and the gate are applied in mfma_group: anything that touches the loaded value HERE makes the compiler
       // wait for it between the groups' requests -- s_waitcnt vmcnt(2) in the middle of the load phase -- and the round trips of
       // a wave's groups then follow each other instead of overlapping)
@@ -573,6 +585,152 @@ __global__ __launch_bounds__(KS == 16 ? 1024 : 256, KS == 16 ? 4 : 2) void conv_
   const int L = blockIdx.x;
   if (L < q.n0) gemm16_body<1, 1, KS>(q.a0, L % q.gx0, L / q.gx0, lds);
   else gemm16_body<1, 1, KS>(q.a1, (L - q.n0) % q.gx1, (L - q.n0) / q.gx1, lds);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The data-gradient pair of a searched-cell node on the levels with <= 64 voxels per sample, with the node's GroupNorm-epilogue
+// backward rebuilt inside the launch (n3d_gn_bwd_conv_data2): job i multiplies d(raw) of term i, and instead of reading it from a
+// tensor that gn_bwd_small2_kernel wrote one launch earlier, every workgroup forms it itself -- dout and raw of its own term for the
+// one or two samples its 16 rows draw from (<= 16 KB per sample) in one round trip of contiguous loads, the small kernel's
+// reduction and coefficient math (gn_bwd_small.h: same lane layout inside a wave, same order across the waves, so the same bits),
+// d(raw) into an LDS tile -- and runs its K loop out of LDS.  No workgroup waits for another one.
+// A wave takes (sample, group, slot) units in turn: slot = 64 consecutive quads of the group's [N][cg / 4] walk of one sample (cg =
+// 16), samples padded to whole waves, exactly the quads one wave of gn_bwd_small2_kernel holds; two units per wave at most.
+// The weight-gradient stream still reads d(raw) from memory: of the workgroups with by == 0, the one whose rows hold a sample's
+// first row stores that sample's d(raw).  Workgroup (0, 0) of a job covers ALL samples and writes the parameter gradients of its term,
+// summed over the samples in sample order, as the small kernel's tail does.
+// LDS: [0, GNF_SCRATCH) the prologue's scratch, which the K-split reduction of the body reuses (the barrier behind the body's tap
+// table lies between the last read of the one and the first write of the other); behind it the tile, [2][N] rows of C + 4 floats
+// (the pad keeps the 16 voxel rows of a wave off each other's banks) and one row of zeros.
+// ------------------------------------------------------------------------------------------------
+struct GnFoldJob { MfArgs a; GnBwdTerm t; };
+struct GnFoldArgs {
+  GnFoldJob j0, j1;
+  const float* dout; int64_t dld;
+  int n0, gx0, gx1;
+  int B, N, C, G, lgC, lgG, lgS;      // N voxels per sample of d(raw); C = 16 G channels; slots per (sample, group) = 1 << lgS
+  double count;
+  int pitch;
+};
+constexpr int GNF_UNITS = 32;          // (sample, group, slot) units of a workgroup: two per wave
+constexpr int GNF_SG = 16;             // (sample, group) pairs: B <= 4, G <= 4
+constexpr int GNF_OFF_TOT = 0;                                        // double [GNF_SG][32]
+constexpr int GNF_OFF_CONTRIB = GNF_OFF_TOT + GNF_SG * 32 * 8;        // double [4][3][64]
+constexpr int GNF_OFF_RED = GNF_OFF_CONTRIB + 4 * 3 * 64 * 8;         // float [GNF_UNITS][32]
+constexpr int GNF_OFF_FCO = GNF_OFF_RED + GNF_UNITS * 32 * 4;         // float [4][2][64]
+constexpr int GNF_OFF_COEF = GNF_OFF_FCO + 4 * 2 * 64 * 4;            // float [4][3][64]
+constexpr int GNF_SCRATCH = GNF_OFF_COEF + 4 * 3 * 64 * 4;
+constexpr int GNF_BODY_LDS = 15 * 256 * 4 + 16 * 16 * 2 * 8;          // what gemm16_body<1, 1, 16> uses of the dynamic LDS
+static_assert(GNF_SCRATCH <= GNF_BODY_LDS, "the prologue's scratch lives in the body's K-split area");
+
+__device__ __forceinline__ void gn_fold_prologue(const GnFoldJob& j, const GnFoldArgs& q, const int bx, const int by, char* scratch,
+                                                 float* tile, const int sb0, const int nsm) {
+  double (*tot)[32] = reinterpret_cast<double (*)[32]>(scratch + GNF_OFF_TOT);
+  double (*contrib)[3][64] = reinterpret_cast<double (*)[3][64]>(scratch + GNF_OFF_CONTRIB);
+  float (*red)[32] = reinterpret_cast<float (*)[32]>(scratch + GNF_OFF_RED);
+  float (*fco)[2][64] = reinterpret_cast<float (*)[2][64]>(scratch + GNF_OFF_FCO);
+  float (*coef)[3][64] = reinterpret_cast<float (*)[3][64]>(scratch + GNF_OFF_COEF);
+  const GnBwdTerm& tm = j.t;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int N = q.N, C = q.C, G = q.G, B = q.B;
+  const int real_b = N * 4;                                   // quads of one (sample, group): cg / 4 = 4 per voxel
+  const bool lead = (bx | by) == 0;
+  const int s_lo = lead ? 0 : sb0, s_n = lead ? B : nsm;      // the samples this workgroup sums over
+  const int nunits = s_n << (q.lgG + q.lgS);
+  const float thr = tm.relu ? 0.f : -INFINITY;
+  const int64_t Nd = (int64_t)j.a.Dd * j.a.Hd * j.a.Wd;
+  if (t < (s_n << (q.lgC + 1))) {
+    const int s = t >> (q.lgC + 1), ab = (t >> q.lgC) & 1, c = t & (C - 1);
+    fco[s][ab][c] = (ab ? tm.b : tm.a)[(s_lo + s) * C + c];
+  }
+  if (t < q.pitch) tile[2 * N * q.pitch + t] = 0.f;            // the row of zeros
+  // ---- every request of the workgroup before the first use
+  float4 d4[2], r4[2];
+  bool uok[2], ok[2];
+  int us[2], uc0[2], uv[2], uu[2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int u = wave + 16 * p;
+    uok[p] = u < nunits;
+    uu[p] = uok[p] ? u : 0;
+    const int s = uu[p] >> (q.lgG + q.lgS), g = (uu[p] >> q.lgS) & (G - 1), sl = uu[p] & ((1 << q.lgS) - 1);
+    const int er = sl * 64 + lane;
+    ok[p] = uok[p] && er < real_b;
+    us[p] = s;
+    uv[p] = ok[p] ? er >> 2 : 0;
+    uc0[p] = g * 16 + (lane & 3) * 4;
+    const int64_t vox = (int64_t)(s_lo + s) * N + uv[p];
+    d4[p] = ld4(q.dout + vox * q.dld + uc0[p]);
+    r4[p] = ld4(tm.raw + vox * tm.rld + uc0[p]);
+  }
+  __syncthreads();
+  // ---- pass 1: S1 = sum g, S2 = sum g * raw per (sample, channel): the wave sums of each unit
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    if (uok[p]) {
+      const float dd[4] = {d4[p].x, d4[p].y, d4[p].z, d4[p].w}, ra[4] = {r4[p].x, r4[p].y, r4[p].z, r4[p].w};
+      const float4 fa = ld4(&fco[us[p]][0][uc0[p]]), fb = ld4(&fco[us[p]][1][uc0[p]]);
+      float gmv[4], grv[4];
+      gn_small_masked(dd, ra, fa, fb, ok[p], thr, gmv, grv);
+      gn_small_wave_sums<4>(gmv, grv, lane, &red[uu[p]][0]);
+    }
+  }
+  __syncthreads();
+  // fixed-order fp64 sum of the slots of each (sample, group)
+  if (t < (s_n << (q.lgG + 5))) {
+    const int sg = t >> 5, idx = t & 31;
+    double s = 0;
+    const int nsl = 1 << q.lgS, u0 = sg << q.lgS;
+    for (int sl = u0; sl < u0 + nsl; ++sl) s += (double)red[sl][idx];
+    tot[sg][idx] = s;
+  }
+  __syncthreads();
+  // ---- coefficients of d(raw) = A * g + B + C * raw and the per-sample parameter-gradient contributions
+  if (t < (s_n << q.lgC)) {
+    const int s = t >> q.lgC, c = t & (C - 1), g = c >> 4;
+    const GnSmallCoef r = gn_small_coeffs(tm, &tot[(s << q.lgG) + g][0], s_lo + s, g, c & 15, 16, C, G, q.count);
+    coef[s][0][c] = r.A; coef[s][1][c] = r.B; coef[s][2][c] = r.C;
+    contrib[s][0][c] = r.cdg; contrib[s][1][c] = r.cdb; contrib[s][2][c] = r.cdc;
+  }
+  __syncthreads();
+  // ---- pass 2: d(raw) from the registers into the tile (and, for the workgroup that owns the sample's first row, into memory)
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    if (!ok[p]) continue;
+    const int sgl = s_lo + us[p], ls = sgl - sb0;
+    if (ls < 0 || ls >= nsm) continue;
+    const float dd[4] = {d4[p].x, d4[p].y, d4[p].z, d4[p].w}, ra[4] = {r4[p].x, r4[p].y, r4[p].z, r4[p].w};
+    const float4 fa = ld4(&fco[us[p]][0][uc0[p]]), fb = ld4(&fco[us[p]][1][uc0[p]]);
+    const float4 qA = ld4(&coef[us[p]][0][uc0[p]]), qB = ld4(&coef[us[p]][1][uc0[p]]), qC = ld4(&coef[us[p]][2][uc0[p]]);
+    const float4 o = gn_small_draw4(dd, ra, fa, fb, qA, qB, qC, thr);
+    st4(tile + (ls * N + uv[p]) * q.pitch + uc0[p], o);
+    const int64_t first = (int64_t)sgl * Nd;
+    if (by == 0 && first >= (int64_t)bx * 16 && first < (int64_t)bx * 16 + 16) st4(tm.draw + ((int64_t)sgl * N + uv[p]) * tm.drld + uc0[p], o);
+  }
+  // ---- parameter gradients: sums over the samples in sample order
+  if (lead && t < C) {
+    double dg = 0, db = 0, dbc = 0;
+    for (int b = 0; b < B; ++b) { dg += contrib[b][0][t]; db += contrib[b][1][t]; dbc += contrib[b][2][t]; }
+    if (tm.dgamma) tm.dgamma[t] = (float)dg;
+    if (tm.dbeta) tm.dbeta[t] = (float)db;
+    if (tm.dbias_conv) tm.dbias_conv[t] = (float)dbc;
+  }
+}
+
+__global__ __launch_bounds__(1024, 4) void conv_gemm16_gnpair_kernel(GnFoldArgs q, EntrySignal es) {
+  entry_signal(es);
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const bool second = (int)blockIdx.x >= q.n0;
+  const GnFoldJob& j = second ? q.j1 : q.j0;
+  const int L = second ? blockIdx.x - q.n0 : blockIdx.x, gx = second ? q.gx1 : q.gx0;
+  const int bx = L % gx, by = L / gx;
+  // the sample(s) the 16 rows of this tile draw from: two on the 2^3 level, and wherever a tile spans a sample boundary
+  const uint32_t Mtot = (uint32_t)q.B * j.a.fNd.d;
+  const uint32_t last = min((uint32_t)bx * 16 + 15, Mtot - 1);
+  const int sb0 = (int)j.a.fNd.div((uint32_t)bx * 16), nsm = (int)j.a.fNd.div(last) - sb0 + 1;
+  float* tile = lds + GNF_BODY_LDS / 4;
+  gn_fold_prologue(j, q, bx, by, reinterpret_cast<char*>(lds), tile, sb0, nsm);
+  gemm16_body_t<1, 1, 16, false, true>(j.a, bx, by, lds, tile, q.pitch, sb0, 2 * q.N * q.pitch * 4);
 }
 
 // up to four independent small convs in one launch (the plain-conv primitives of a supernet node, cell.py:76-81): the
@@ -3021,6 +3179,71 @@ int mfma_conv_pair_try(const ConvCall& c0, const ConvCall& c1, hipStream_t s) {
   else N3D_LAUNCH(conv_gemm16_pair_kernel<4>, dim3((unsigned)(q.n0 + n1)), dim3(256), shm, s, q, es);
   g_fold_launches[1] += 1;
   N3D_LAUNCH_CHECK_AS("conv(pair)");
+  return 1;
+}
+
+// THE decision whether the data-gradient pair rebuilds the node's GroupNorm-epilogue backward in its own launch
+// (n3d_gn_bwd_conv_data2_ok asks it, n3d_gn_bwd_conv_data2 acts on it); c_i multiplies d(raw) of term i
+static bool gn_fold_ok(const float* dout, int64_t dld, const n3d_gn_bwd_term* const* ts, int B, int64_t N, int C, int G, const ConvCall* cs) {
+  if (G < 1 || G > 4 || C != 16 * G || (G & (G - 1)) || B < 1 || N < 1) return false;      // 16 channels per group
+  if (!n3d_bwd_small2_ok(B, N, C, G)) return false;
+  const int64_t spb = (N * 4 + 63) / 64;                  // wave slots of one (sample, group)
+  if ((spb & (spb - 1)) || (int64_t)B * G * spb > GNF_UNITS) return false;
+  if ((size_t)GNF_BODY_LDS + (size_t)(2 * N + 1) * (C + 4) * 4 + 4096 > 65536) return false;
+  if (!dout || dld % 4 != 0 || dld < C || !aligned16(dout)) return false;
+  for (int i = 0; i < 2; ++i) {
+    const n3d_gn_bwd_term* t = ts[i];
+    const ConvCall& c = cs[i];
+    if (t->dtype != N3D_F32 || !t->raw || !t->a || !t->b || !t->gamma || !t->mean_rstd || !t->draw || t->dalpha) return false;
+    if (t->dbias_conv && !t->sumraw) return false;
+    if (t->rld % 4 != 0 || t->rld < C || t->drld % 4 != 0 || t->drld < C || !aligned16(t->raw) || !aligned16(t->draw)) return false;
+    if (c.flags & (N3D_MM_BF16 | N3D_SRC_BF16 | N3D_DST_BF16 | N3D_NO_MFMA)) return false;
+    if (c.in_gate || c.stats || c.bias || c.src != t->draw || c.sld != t->drld || !c.w || !c.dst) return false;
+    const n3d_conv_geom* g = c.g;
+    if (g->depthwise || g->B != B || vx_plan(g).ok || tile32_tiles(g)) return false;
+    const GatherGeom m = gather_geom(g, c.data_grad);
+    if ((int64_t)m.Ds * m.Hs * m.Ws != N || m.Cs != C) return false;
+    const int64_t Nd = (int64_t)m.Dd * m.Hd * m.Wd;
+    if (Nd % 8 != 0) return false;                        // a 16-row tile then draws from two samples at most
+    const G16Plan p = g16_plan(g, c.data_grad);
+    if (!p.ok || p.ksplit != 16) return false;
+    if (!c.ws || c.ws_bytes < (size_t)g->k * g->k * g->k * m.Cs * m.Cd * 4) return false;
+  }
+  if (cs[0].dst == cs[1].dst || ts[0]->draw == ts[1]->draw) return false;
+  if (cs[0].ws == cs[1].ws && !((cs[0].flags & cs[1].flags) & N3D_PREPACKED)) return false;      // (as mfma_conv_pair_try)
+  return true;
+}
+
+// 1 = taken (launched unless `launch` is false), 0 = declined (nothing launched, nothing packed), < 0 error
+int mfma_gn_fold_pair(const float* dout, int64_t dld, const n3d_gn_bwd_term* t0, const n3d_gn_bwd_term* t1, int B, int64_t N, int C, int G,
+                      const ConvCall& c0, const ConvCall& c1, hipStream_t s, bool launch) {
+  const n3d_gn_bwd_term* ts[2] = {t0, t1};
+  const ConvCall cs[2] = {c0, c1};
+  if (!gn_fold_ok(dout, dld, ts, B, N, C, G, cs)) return 0;
+  if (!launch) return 1;
+  GnFoldArgs q;
+  GnFoldJob* js[2] = {&q.j0, &q.j1};
+  for (int i = 0; i < 2; ++i) {
+    G16Plan p;
+    const int r = g16_prepare(cs[i], s, &js[i]->a, &p);
+    if (r <= 0) return r < 0 ? r : N3D_ERR_INVALID;
+    const n3d_gn_bwd_term* t = ts[i];
+    js[i]->t = GnBwdTerm{t->raw, t->rld, t->a, t->b, nullptr, 0, t->gamma, t->mean_rstd, t->wptr, t->sumraw, t->draw, t->drld,
+                         t->dgamma, t->dbeta, nullptr, t->dbias_conv, t->relu, nullptr, nullptr, nullptr};
+  }
+  auto lg = [](int64_t v) { int l = 0; while ((1ll << l) < v) ++l; return l; };
+  q.dout = dout; q.dld = dld;
+  q.B = B; q.N = (int)N; q.C = C; q.G = G; q.lgC = lg(C); q.lgG = lg(G); q.lgS = lg((N * 4 + 63) / 64);
+  q.count = (double)N;
+  q.pitch = C + 4;
+  const int64_t M0 = (int64_t)B * q.j0.a.Dd * q.j0.a.Hd * q.j0.a.Wd, M1 = (int64_t)B * q.j1.a.Dd * q.j1.a.Hd * q.j1.a.Wd;
+  q.gx0 = (int)cdiv(M0, 16); q.gx1 = (int)cdiv(M1, 16);
+  q.n0 = q.gx0 * (q.j0.a.Cd / 16);
+  const int n1 = q.gx1 * (q.j1.a.Cd / 16);
+  const size_t shm = (size_t)GNF_BODY_LDS + (size_t)(2 * N + 1) * q.pitch * sizeof(float);
+  const EntrySignal es = entry_take(s);
+  N3D_LAUNCH(conv_gemm16_gnpair_kernel, dim3((unsigned)(q.n0 + n1)), dim3(1024), shm, s, q, es);
+  N3D_LAUNCH_CHECK_AS("conv(gn pair)");
   return 1;
 }
 

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "n3d_common.h"
+#include "gn_bwd_small.h"
 
 namespace n3d {
 
@@ -683,11 +684,7 @@ __global__ __launch_bounds__(256) void affine_act_gn_kernel(const T* __restrict_
 // All global loads of the prologue (parameter vectors and every partial row this workgroup needs) are issued
 // before the first use, so the prologue costs ONE memory round trip; everything after it is LDS work.
 #define GNF_MAXB 4
-struct GnBwdTerm {
-  const float* raw; int64_t rld; const float* a; const float* b; const double* sums; int rows; const float* gamma; const float* mean_rstd;
-  const float* wptr; const double* sumraw; float* draw; int64_t drld; float* dgamma; float* dbeta; float* dalpha; float* dbias_conv; int relu;
-  const float* cA; const float* cB; const float* cC;   // PRE variant: coefficients from n3d_gn_bwd_coeffs2
-};
+// (GnBwdTerm, the argument record of one term: gn_bwd_small.h)
 
 // GroupNorm-backward coefficients of BOTH terms of a pair, wave level (see affine_bwd_apply_gn_kernel); strip[k][0..2][c] = A, B, C.
 // Everything a wave needs from memory -- the partial rows of the two terms (same row count: they come out of one reduce2 launch),
@@ -1421,21 +1418,10 @@ __global__ __launch_bounds__(1024) void gn_bwd_small2_kernel(const T* __restrict
     for (int k = 0; k < NT; ++k) {
       const float thr = k ? thr1 : thr0;
       const float4 fa = ld4(&fco[bi[i]][k][0][q * 4]), fb = ld4(&fco[bi[i]][k][1][q * 4]);
-      const float aa[4] = {fa.x, fa.y, fa.z, fa.w}, bb[4] = {fb.x, fb.y, fb.z, fb.w};
       float gmv[4], grv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float z = fmaf(aa[j], ra[k][j], bb[j]);
-        gmv[j] = (ok[i] && z > thr) ? dd[k][j] : 0.f;
-        grv[j] = gmv[j] * ra[k][j];
-      }
-      // the four channels of the quad reduced together (wave_classsum4_f): row r of the wave ends up with channel {0,2,1,3}[r]
-      class_dispatch16(cpg4, [&](auto cc) {
-        constexpr int CPB = decltype(cc)::value;
-        const float s1 = wave_classsum4_f<CPB>(gmv[0], gmv[1], gmv[2], gmv[3]), s2 = wave_classsum4_f<CPB>(grv[0], grv[1], grv[2], grv[3]);
-        const int l16 = lane & 15, j = classsum4_sel(lane);
-        if (l16 < CPB) { red[i * 16 + wave][k][l16 * 4 + j] = s1; red[i * 16 + wave][k][16 + l16 * 4 + j] = s2; }
-      });
+      gn_small_masked(dd[k], ra[k], fa, fb, ok[i], thr, gmv, grv);
+      // (the pieces shared with the data-gradient launch that rebuilds d(raw) itself: gn_bwd_small.h)
+      class_dispatch16(cpg4, [&](auto cc) { gn_small_wave_sums<decltype(cc)::value>(gmv, grv, lane, &red[i * 16 + wave][k][0]); });
     }
   }
   __syncthreads();
@@ -1456,23 +1442,9 @@ __global__ __launch_bounds__(1024) void gn_bwd_small2_kernel(const T* __restrict
     if (c < cg && k < NT) {
       const GnBwdTerm& tm = k ? t1 : t0;
       const int gb = b0 + b;
-      const double w = tm.wptr ? (double)*tm.wptr : 1.0;
-      const double mn = tm.mean_rstd[(gb * G + g) * 2], rsd = tm.mean_rstd[(gb * G + g) * 2 + 1];
-      double c1 = 0, c2 = 0;
-      for (int cc = 0; cc < cg; ++cc) {
-        const double gm = (double)tm.gamma[g * cg + cc];
-        const double S1 = tot[b][k][cc], S2 = tot[b][k][16 + cc];
-        c1 += gm * w * S1;
-        c2 += gm * w * rsd * (S2 - mn * S1);
-      }
-      const double n = count * cg;
-      c1 /= n; c2 /= n;
-      const double gam = (double)tm.gamma[g * cg + c];
-      const double S1 = tot[b][k][c], S2 = tot[b][k][16 + c];
-      const double Av = rsd * gam * w, Bv = -rsd * c1 + rsd * rsd * c2 * mn, Cv = -rsd * rsd * c2;
-      coef[b][k][0][c] = (float)Av; coef[b][k][1][c] = (float)Bv; coef[b][k][2][c] = (float)Cv;
-      const double cdg = w * rsd * (S2 - mn * S1), cdb = w * S1;
-      const double cdc = tm.dbias_conv ? Av * S1 + count * Bv + Cv * tm.sumraw[gb * C + g * cg + c] : 0.0;
+      const GnSmallCoef r = gn_small_coeffs(tm, &tot[b][k][0], gb, g, c, cg, C, G, count);
+      coef[b][k][0][c] = r.A; coef[b][k][1][c] = r.B; coef[b][k][2][c] = r.C;
+      const double cdg = r.cdg, cdb = r.cdb, cdc = r.cdc;
       contrib[b][k][0][c] = cdg; contrib[b][k][1][c] = cdb; contrib[b][k][2][c] = cdc;
       if (SPLIT) {
         double* sc = scratch + ((((int64_t)g * B + gb) * 2 + k) * 3) * 16 + c;
@@ -1502,17 +1474,8 @@ __global__ __launch_bounds__(1024) void gn_bwd_small2_kernel(const T* __restrict
       const float4 fa = ld4(&fco[bi[i]][k][0][q * 4]), fb = ld4(&fco[bi[i]][k][1][q * 4]);
       const float4 qA = ld4(&coef[bi[i]][k][0][q * 4]), qB = ld4(&coef[bi[i]][k][1][q * 4]),
                    qC = ld4(&coef[bi[i]][k][2][q * 4]);
-      const float aa[4] = {fa.x, fa.y, fa.z, fa.w}, bb[4] = {fb.x, fb.y, fb.z, fb.w};
-      const float A4[4] = {qA.x, qA.y, qA.z, qA.w}, B4[4] = {qB.x, qB.y, qB.z, qB.w}, C4[4] = {qC.x, qC.y, qC.z, qC.w};
-      float o[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float z = fmaf(aa[j], ra[k][j], bb[j]);
-        const float gm = z > thr ? dd[k][j] : 0.f;
-        o[j] = fmaf(A4[j], gm, fmaf(C4[j], ra[k][j], B4[j]));
-      }
       T* op = (k ? reinterpret_cast<T*>(t1.draw) + vox[i] * t1.drld : reinterpret_cast<T*>(t0.draw) + vox[i] * t0.drld) + c0;
-      st4(op, make_float4(o[0], o[1], o[2], o[3]));
+      st4(op, gn_small_draw4(dd[k], ra[k], fa, fb, qA, qB, qC, thr));
     }
   }
   // ---- parameter gradients: sums over the samples in sample order

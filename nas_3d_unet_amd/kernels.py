@@ -1074,13 +1074,8 @@ def small_backward_mode(B, N, Cc, G):
     return m
 
 
-def affine_act_bwd_small(dout: View, terms, G, dout1: View | None = None):
-    """The whole GroupNorm-epilogue backward of one or two terms (dicts as affine_act_bwd_gn2) in ONE launch; the caller has checked
-    small_backward_mode().  Returns [(dgamma, dbeta, dconv_bias | None)] per term."""
-    raw0 = terms[0]["raw"]
-    dev = raw0.t.device
-    B, Cc, N = raw0.B, raw0.C, raw0.N
-    lib = _lib.load()
+def _small_bwd_terms(terms):
+    """the n3d_gn_bwd_term records of the one-launch epilogue backward and the gradient targets [(dgamma, dbeta, dconv_bias | None)]"""
     ts, outs = [], []
     for t in terms:
         dgamma, dbeta = grad_target(t["gamma"]), grad_target(t["beta"])
@@ -1091,6 +1086,42 @@ def affine_act_bwd_small(dout: View, terms, G, dout1: View | None = None):
                             t["gamma"].data_ptr(), t["mr"].data_ptr(), _vp(t.get("wptr")), _vp(t["sumraw"]), draw.p.value, draw.ld,
                             _vp(dgamma), _vp(dbeta), None, _vp(dcb), None, None, None, raw.dt, 0))
         outs.append((dgamma, dbeta, dcb))
+    return ts, outs
+
+
+GN_BWD_FOLD = True   # a node's epilogue backward rebuilt inside its data-gradient pair launch (n3d_gn_bwd_conv_data2); off: two launches
+
+
+class GnBwdFold:
+    """A searched-cell node's epilogue backward and its two data gradients as ONE launch (n3d_gn_bwd_conv_data2), where libn3d takes
+    the pair: terms = the node's two term dicts (affine_act_bwd_gn2), calls[i] = the data gradient of the conv that produced raw of
+    terms[i], (g, dy, w, dx, flags, relu_src, out_gate, transposed) with dy = terms[i]["draw"].  `ok` asks the library's own decision
+    without launching; launch() returns [(dgamma, dbeta, dconv_bias | None)] per term like affine_act_bwd_small."""
+
+    def __init__(self, dout: View, terms, G, calls):
+        self.ok = False
+        raw0 = terms[0]["raw"]
+        views = [dout] + [v for t in terms for v in (t["raw"], t["draw"])] + [v for c in calls for v in (c[1], c[3])]
+        if not GN_BWD_FOLD or any(v.dt != _lib.F32 for v in views) or any(t.get("dalpha_ptr") is not None for t in terms):
+            return
+        self.ts, self.outs = _small_bwd_terms(terms)
+        self.cs, self.keep = _bwd_data2_calls(calls)
+        self.args = (dout.p, dout.ld, C.byref(self.ts[0]), C.byref(self.ts[1]), raw0.B, raw0.N, raw0.C, G, C.byref(self.cs[0]), C.byref(self.cs[1]))
+        self.ok = bool(_lib.load().n3d_gn_bwd_conv_data2_ok(*self.args))
+
+    def launch(self):
+        check(_lib.load().n3d_gn_bwd_conv_data2(*self.args, stream_ptr()), "n3d_gn_bwd_conv_data2")
+        return self.outs
+
+
+def affine_act_bwd_small(dout: View, terms, G, dout1: View | None = None):
+    """The whole GroupNorm-epilogue backward of one or two terms (dicts as affine_act_bwd_gn2) in ONE launch; the caller has checked
+    small_backward_mode().  Returns [(dgamma, dbeta, dconv_bias | None)] per term."""
+    raw0 = terms[0]["raw"]
+    dev = raw0.t.device
+    B, Cc, N = raw0.B, raw0.C, raw0.N
+    lib = _lib.load()
+    ts, outs = _small_bwd_terms(terms)
     d1p, d1ld = (dout1.p, dout1.ld) if dout1 is not None else (None, 0)
     scratch, sbytes, tick = None, 0, None
     if small_backward_mode(B, N, Cc, G) == 2:

@@ -752,11 +752,50 @@ def pair_backward(segA, sA, segB, sB, dout, argsA, argsB, doutB=None, alphaA=Non
         ra = seg_backward(segA, sA, dout, *argsA, aA[0], aA[1], aA[2])
         return ra, rb
     terms = [_gn_bwd_term(segA, sA, aA), _gn_bwd_term(segB, sB, aB)]
+    if K.GN_BWD_FOLD and doutB is None and K.deferring():
+        folded = _fold_gn_pair(segA, sA, segB, sB, dout, terms, argsA, argsB)
+        if folded is not None:
+            return folded
     outs = K.affine_act_bwd_gn2(dout, terms, sA.G, doutB)
     # weight-op backward in reverse forward order (B then A), as the unpaired path does
     order = ((segB, sB, terms[1], outs[1], argsB), (segA, sA, terms[0], outs[0], argsA))
     results = _weight_backward(order, fold_data)
     return results[1], results[0]
+
+
+def _fold_gn_pair(segA, sA, segB, sB, dout, terms, argsA, argsB):
+    """pair_backward in the side-stream schedule on the levels with <= 64 voxels per sample: the epilogue backward of the node and the two
+    data gradients in ONE launch where libn3d takes them (K.GnBwdFold), the two weight gradients queued for the weight-gradient stream
+    as K.conv_bwd_both2 queues them -- they read d(raw), which the launch has written before any later cut.  None: not such a node
+    (the caller keeps the epilogue launch and the pair launch)."""
+    if not (isinstance(segA.weight, DenseConvW) and isinstance(segB.weight, DenseConvW)):
+        return None
+    raw = sA.raw
+    if K.small_backward_mode(raw.B, raw.N, raw.C, sA.G) != 1:
+        return None
+    items = ((segB, sB, terms[1], argsB), (segA, sA, terms[0], argsA))      # B then A, the order of _weight_backward
+    dcbs = [t.get("conv_bias") is not None and t["sumraw"] is not None and t["conv_bias"].requires_grad for _, _, t, _ in items]
+    cands = [seg.weight.bwd_call(s.ws, t["draw"], a[0], a[1], a[2], dcb) for (seg, s, t, a), dcb in zip(items, dcbs)]
+    if any(c is None for c in cands) or cands[0][1].p.value == cands[1][1].p.value:
+        return None
+    calls = [c[0] for c in cands]
+    data = [(g, dy, w, dx, flags_data, relu_src, out_gate, transposed)
+            for (g, x, dy, w, dx, dw, dbias, flags_data, relu_src, out_gate, flags_weight, in_gate, transposed) in calls]
+    fold = K.GnBwdFold(dout, [terms[1], terms[0]], sA.G, data)
+    if not fold.ok:
+        return None
+    for (g, x, dy, w, dx, dw, dbias, flags_data, relu_src, out_gate, flags_weight, in_gate, transposed) in calls:
+        K.conv_bwd_weight(g, x, dy, dw, dbias, flags_weight, in_gate, transposed)      # queued
+    outs = fold.launch()
+    res = []
+    for (seg, _, t, _), c, (dgamma, dbeta, dcb) in zip(items, cands, outs):
+        wg = list(c[2])
+        if dcb is not None:
+            for j, p in enumerate(seg.weight.params()):
+                if p is t["conv_bias"]:
+                    wg[j] = dcb
+        res.append((c[1].t, wg + [dgamma, dbeta]))
+    return res[1], res[0]
 
 
 def pair_backward_epilogue(segA, sA, segB, sB, dout, argsA, argsB):

@@ -24,7 +24,7 @@ PEAK_HBM_GBS = 8000.0
 
 
 # entry points that launch nothing (queries)
-HOST_ONLY = {"n3d_conv_workspace_bytes", "n3d_conv_stats_rows", "n3d_conv_pack_info", "n3d_stats_rows", "n3d_fused_max_rows", "n3d_bwd_small2_ok",
+HOST_ONLY = {"n3d_conv_workspace_bytes", "n3d_conv_stats_rows", "n3d_conv_pack_info", "n3d_stats_rows", "n3d_fused_max_rows", "n3d_bwd_small2_ok", "n3d_gn_bwd_conv_data2_ok",
              "n3d_head_rows", "n3d_head_workspace_bytes", "n3d_dice_rows", "n3d_last_error", "n3d_version", "n3d_device_ok", "n3d_comm_available",
              "n3d_dropout3d_uniform", "n3d_comm_unique_id", "n3d_comm_init", "n3d_comm_destroy", "n3d_entry_signal_pending",
              "n3d_entry_signal_counts", "n3d_cc_workspace_bytes", "n3d_target_sdt_workspace_bytes"}
@@ -147,6 +147,14 @@ def describe(name, args):
                     ff, bb = _conv_cost(g, "bwd_both", 0)
                 else:
                     ff, bb = _conv_cost(g, "bwd_data", 0)
+                sig.append(_gtuple(g)); f += ff; b += bb
+            return tuple(sig), f, b
+        if name == "n3d_gn_bwd_conv_data2":    # the node's epilogue backward (5 passes over B x N x C) + its two data gradients
+            B, N, Cc = v[4], v[5], v[6]
+            sig, f, b = [name], 0, ew(B, N, Cc, 5, False)[1]
+            for c in (_struct(args[8]), _struct(args[9])):
+                g = c.g.contents
+                ff, bb = _conv_cost(g, "bwd_data", 0)
                 sig.append(_gtuple(g)); f += ff; b += bb
             return tuple(sig), f, b
         if name == "n3d_conv_fwdN":
